@@ -15,13 +15,19 @@ Workloads (BASELINE.json configs):
   c2            16 859 items x 4096-d (Games-sized)
 Items shard across ranks with no data-path collective (weak scaling: fixed items per GPU).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP events on the launch
-stream) and, at N=1, `cpu_baseline` (the torch-CPU restatement of the reference path timed on
-this host's cores).  lcrec_encode_assign runs one chunk pipeline by default: the hipEvent brackets
-of the timed region are then un-overlapped launches and `roofline` is measured in the timed region
-itself.  With `--pipelines 2` (opt-in, see include/lcrec.h) launches of the two pipelines overlap;
-the kernel's own rate is then taken in a short untimed pass with one pipeline and the in-region
-figures are reported next to it (`roofline.in_region`).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps passes and prints the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration).
+`--dump-outputs DIR` writes the index matrix of the last timed pass to DIR/indices.npy (float32);
+the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else, measured after the timed region: `roofline` (dominant kernel, HIP
+events on the launch stream), the near-tie audit, rank checksums, and at N=1 the parity spot check,
+`cpu_baseline` (the torch-CPU restatement of the reference path timed on this host's cores) and
+`secondary`.  lcrec_encode_assign runs one chunk pipeline by default: with --full the hipEvent
+brackets of the timed region are then un-overlapped launches and `roofline` is measured in the timed
+region itself.  With `--pipelines 2` (opt-in, see include/lcrec.h) launches of the two pipelines
+overlap; the kernel's own rate is then taken in a short untimed pass with one pipeline and the
+in-region figures are reported next to it (`roofline.in_region`).
 """
 import argparse
 import json
@@ -80,6 +86,54 @@ def synth_model(in_dim, device, seed=2024, codes=None):
         _, xq, _, _ = lcrec_amd.ops.rq_assign(z, flat, ks, want_xq=True)
         resid = z - xq
     return dims, Ws, bs, cbs
+
+
+def make_inputs(wl, n, device, rank=0):
+    """The model and rank `rank`'s shard of n items, both drawn from fixed seeds: the same arguments give the same inputs on
+    every run."""
+    from lcrec_amd import ops
+    dims, Ws, bs, cbs = synth_model(wl["in_dim"], device, codes=wl.get("codes"))
+    flat, ks = ops.flatten_codebooks(cbs)
+    g = torch.Generator(device=device)
+    g.manual_seed(2024 + rank)
+    x = torch.randn((n, wl["in_dim"]), generator=g, device=device, dtype=torch.float32)
+    return dims, Ws, bs, cbs, flat, ks, x
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, idx, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives -- the [n, L] index matrix -- as float32 (every code is below
+    2**24, so exact) in path/indices.npy.  Above `limit` bytes a fixed, seeded sample of rows is written instead, in
+    ascending order, and their row numbers go to path/indices_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = idx.cpu().numpy()
+    n, L = a.shape
+    rows_file = os.path.join(path, "indices_rows.npy")
+    if n * L * 4 > limit:
+        rows = np.sort(np.random.RandomState(0).choice(n, limit // (L * 4 + 8), replace=False))
+        np.save(rows_file, rows.astype(np.float64))
+        a = a[rows]
+    elif os.path.exists(rows_file):
+        os.remove(rows_file)                               # a sample's row numbers from an earlier run would mislabel this one
+    np.save(os.path.join(path, "indices.npy"), a.astype(np.float32))
+
+
+def headline(wl, n, dims, ks, world, args, elapsed, pipelines):
+    """The result line of every run: what the timed region measured and on what."""
+    macs_all = sum(dims[l] * dims[l + 1] for l in range(len(dims) - 1)) + sum(E_DIM * k for k in ks)
+    return {
+        "metric": f"item-embeddings/sec through {len(ks)}-level RQ encode+assign", "value": n * world * args.steps / elapsed,
+        "unit": "items/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": wl["name"], "items_per_gpu": n, "in_dim": wl["in_dim"], "mlp": HIDDEN,
+                   "e_dim": E_DIM, "levels": len(ks), "codes_per_level": ks[0], "sharding": f"items/{world}",
+                   "chunk_pipelines": pipelines,
+                   "flop_per_item": 2 * macs_all, "bytes_per_item": 4 * wl["in_dim"] + 8 * len(ks)},
+    }
 
 
 def host_cores():
@@ -278,10 +332,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--items", type=int, default=0, help="override items per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the quantizer-only and training-step figures (N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the index matrix of the last one to DIR/indices.npy (float32; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline, near-tie audit, rank checksums, "
+                         "parity spot check, cpu_baseline and the secondary figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the quantizer-only and training-step figures (N=1 only)")
     ap.add_argument("--trace-pass", choices=["auto", "timed", "separate"], default="auto",
-                    help="where the per-launch hipEvent brackets behind `roofline` are taken: inside the timed region (default), or "
+                    help="with --full: where the per-launch hipEvent brackets behind `roofline` are taken: inside the timed region (default), or "
                          "in an untimed pass of the same launches right after it (default for --workload c2, whose launches are short)")
     ap.add_argument("--pipelines", type=int, default=0,
                     help="chunk pipelines of lcrec_encode_assign (lcrec_context_set_pipelines); 0 = the library's default (1)")
@@ -296,6 +356,8 @@ def main():
                     help="nccl = RCCL over xGMI (the real multi-GPU run); gloo = rehearsal of the N>1 code path, "
                          "ranks may then share one GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -333,11 +395,7 @@ def main():
 
     wl = WORKLOADS[args.workload]
     n = args.items or wl["items"]
-    dims, Ws, bs, cbs = synth_model(wl["in_dim"], device, codes=wl.get("codes"))
-    flat, ks = ops.flatten_codebooks(cbs)
-    g = torch.Generator(device=device)
-    g.manual_seed(2024 + rank)
-    x = torch.randn((n, wl["in_dim"]), generator=g, device=device, dtype=torch.float32)
+    dims, Ws, bs, cbs, flat, ks, x = make_inputs(wl, n, device, rank)
 
     def step():
         return ops.encode_assign(x, Ws, bs, flat, ks)[0]
@@ -354,13 +412,28 @@ def main():
     # 0.1-20 ms per pass -- that is nothing; at C2 a pass is 11 launches in 2.7 ms and the markers cost it ~4 % (measured:
     # --trace-pass timed vs separate).  "separate" keeps the timed region free of them and brackets the same launches in an
     # untimed pass right after it (the default for c2 only; the headline workloads are bracketed inside the timed region).
+    # Only --full brackets anything: a plain run's timed region carries no markers.
     trace_pass = args.trace_pass if args.trace_pass != "auto" else ("separate" if args.workload == "c2" else "timed")
-    ops.trace_enable(trace_pass == "timed")
+    ops.trace_enable(args.full and trace_pass == "timed")
     t0 = time.perf_counter()
     for _ in range(args.steps):
         idx = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if use_dist:
+        cdev = device if args.backend == "nccl" else "cpu"
+        t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(wl, n, dims, ks, world, args, elapsed, pipelines)), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     trace = ops.trace_collect()
     ops.trace_enable(False)
     # With more than one chunk pipeline two layers' kernels share the chip, so the hipEvent brackets of the timed region
@@ -391,10 +464,6 @@ def main():
     checksum = int(idx.sum())                        # per-rank: proves every rank computed, and what
     ranks_seen, checksums = 1, [checksum]
     if use_dist:
-        cdev = device if args.backend == "nccl" else "cpu"
-        t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
         # one all-gather of (rank, index checksum, near-tie rows) through the collective backend: `ranks_seen` is the
         # number of distinct ranks RCCL actually delivered data from
         mine = torch.tensor([rank, checksum, neartie_rows], dtype=torch.int64, device=cdev)
@@ -507,17 +576,9 @@ def main():
 
     out = None
     if rank == 0:
-        total_items = n * world * args.steps
-        value = total_items / elapsed
-        out = {
-            "metric": f"item-embeddings/sec through {len(ks)}-level RQ encode+assign", "value": value, "unit": "items/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": wl["name"], "items_per_gpu": n, "in_dim": wl["in_dim"], "mlp": HIDDEN,
-                       "e_dim": E_DIM, "levels": len(ks), "codes_per_level": ks[0], "sharding": f"items/{world}",
-                       "chunk_pipelines": pipelines,
-                       "flop_per_item": 2 * macs_all, "bytes_per_item": 4 * wl["in_dim"] + 8 * len(ks)},
+        out = headline(wl, n, dims, ks, world, args, elapsed, pipelines)
+        value = out["value"]
+        out.update({
             "roofline": roofline, "roofline_rq_assign": roofline_rq,
             "e2e_mfma_frac": value / world * 2 * macs_all / 1e12 / PEAK_F32_MFMA_TFLOPS,
             "ranks_seen": ranks_seen, "idx_checksums": checksums,
@@ -526,7 +587,7 @@ def main():
                             "on which the reference's CPU arithmetic can differ from the canonical order this library and "
                             "its oracle implement (measured: 33 of 1 M at C3, 0 of 16 859 at C2; DESIGN.md section 2)",
             "io_gbps": value / world * (4 * wl["in_dim"] + 8 * len(ks)) / 1e9,
-        }
+        })
         if world == 1:
             # parity spot check (not timed): 1024 rows against the bit-exact C oracle
             from oracle import cpu_oracle

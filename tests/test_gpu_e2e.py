@@ -173,14 +173,15 @@ def test_nan_loss_is_reported_with_and_without_the_per_step_sync(hip, tmp_path, 
 
 
 def test_bench_line_and_its_collective_path_over_a_one_rank_rccl_group(hip):
-    """bench.py end to end on a small shard: the JSON contract (metric, roofline, near-tie and rank fields) and -- with
+    """bench.py --full end to end on a small shard: the JSON contract (metric, roofline, near-tie and rank fields) and -- with
     --rehearse-rccl -- the N>1 code path (barrier, MAX all-reduce of the time, all-gather of the per-rank checksums) through
     a real RCCL communicator of one rank."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--items", "150000", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--rehearse-rccl", "--dp-graph"], capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--rehearse-rccl", "--dp-graph"], capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1 and len(line["idx_checksums"]) == 1
@@ -196,6 +197,28 @@ def test_bench_line_and_its_collective_path_over_a_one_rank_rccl_group(hip):
     assert "error" not in dp and dp["train_ranks_seen"] == 1 and dp["dp_collectives_per_step"] >= 20
     assert dp["train_param_checksums_agree_eager"] and dp["train_param_checksums_agree_graph"]
     assert 0.3 < dp["dp_train_step_ms_eager"] < 50 and dp["dp_train_graph_replays_graph"] > 0 and dp["dp_train_graph_replays_eager"] == 0
+
+
+def test_plain_bench_line_and_its_dumped_outputs(hip, tmp_path):
+    """A plain bench.py run prints the headline alone, and --dump-outputs writes the index matrix of the last timed pass:
+    the same matrix the library computes in another process from make_inputs' seeded inputs."""
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 150000
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--items", str(n), "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["unit"] == "items/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 3
+    assert line["value"] > 1e6 and abs(line["value"] * line["ms_per_step"] * 1e-3 - n) < 1e-6 * n
+    assert not {"roofline", "neartie_rows", "idx_checksums", "parity_mismatch_rows", "cpu_baseline", "secondary"} & set(line)
+    got = np.load(tmp_path / "indices.npy")
+    assert got.dtype == np.float32 and got.shape == (n, 4) and not (tmp_path / "indices_rows.npy").exists()
+    dims, Ws, bs, cbs, flat, ks, x = bench.make_inputs(bench.WORKLOADS["c3"], n, torch.device("cuda:0"))
+    want = hip.ops.encode_assign(x, Ws, bs, flat, ks)[0]
+    assert np.array_equal(got, want.cpu().numpy().astype(np.float32))
 
 
 @pytest.mark.parametrize("dtype,mmap", [(np.float32, True), (np.float16, True), (np.float64, False)])

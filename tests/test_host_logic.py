@@ -374,3 +374,21 @@ def test_recheck_neartie_reproduces_the_references_batch64_tuples_on_the_recorde
     assert done == 33 and changed == int((f["ref64_rows"] != f["oracle_rows"]).any(1).sum())
     early = (f["ref64_rows"][:, :3] != f["oracle_rows"][:, :3]).any(1)
     assert bool((resid_last[rows[early]].abs().sum(1) > 0).all()) and float(resid_last[rows[~early]].abs().sum()) == 0.0
+
+
+# ------------------------------------------------------------------ bench.py --dump-outputs
+def test_bench_dump_outputs_writes_exact_float32_indices_and_a_seeded_sample_above_the_limit(tmp_path):
+    import bench
+    idx = torch.arange(4000 * 4, dtype=torch.int64).reshape(4000, 4) % 1024
+    bench.dump_outputs(str(tmp_path), idx)
+    got = np.load(tmp_path / "indices.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, idx.numpy()) and not (tmp_path / "indices_rows.npy").exists()
+    limit = 16_000                                   # 16 B of float32 indices + 8 B of row number per sampled row
+    bench.dump_outputs(str(tmp_path), idx, limit=limit)
+    rows, got = np.load(tmp_path / "indices_rows.npy"), np.load(tmp_path / "indices.npy")
+    assert rows.dtype == np.float64 and len(rows) == limit // 24 and bool((np.diff(rows) > 0).all())
+    assert np.array_equal(got, idx.numpy()[rows.astype(np.int64)]) and got.nbytes + rows.nbytes <= limit
+    bench.dump_outputs(str(tmp_path), idx, limit=limit)
+    assert np.array_equal(np.load(tmp_path / "indices_rows.npy"), rows)       # the same sample every time
+    bench.dump_outputs(str(tmp_path), idx)           # a full dump drops the row numbers of an earlier sample
+    assert not (tmp_path / "indices_rows.npy").exists()

@@ -450,6 +450,38 @@ int lcrec_adamw_step(float *params, float *grads, float *exp_avg, float *exp_avg
                      int decoupled, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
                      unsigned int *ticket, const unsigned char *skip_flag, void *stream);
 
+/* The reference's other learners (index/trainer.py:49-81,118-120) on flat fp32 buffers, each with everything
+ * lcrec_adamw_step does around its rule: grads *= clip[1] first (stored back when clip[1] != 1; clip may be NULL), the
+ * learning rate lr(*step) from `schedule` / warmup_steps / total_steps, lr_out, the increment of *step (by the last
+ * workgroup with a ticket, else by a second launch), and skip_flag (non-zero: update nothing, leave *step).  Per element,
+ * g = grads * clip[1], then g += weight_decay * param when weight_decay != 0; the rules are torch 2.10's
+ * _single_tensor_{sgd,adagrad,rmsprop}, with each op rounded as torch's CPU kernel rounds it (add with alpha and addcmul
+ * fused, addcdiv as x + (value * y) / z, IEEE sqrt and division).  State is fp32, hyper-parameters are double.
+ *
+ * torch.optim.SGD: with momentum != 0, momentum_buffer[count] and momentum_ready (device byte) are required, otherwise
+ * both are NULL.  momentum_ready == 0: buf = g (torch's first step) and the byte is set to 1 with the step increment;
+ * else buf = momentum * buf + (1 - dampening) * g.  g = nesterov ? g + momentum * buf : buf.  param -= lr * g.
+ * nesterov needs momentum > 0 and dampening == 0. */
+int lcrec_sgd_step(float *params, float *grads, float *momentum_buffer, unsigned char *momentum_ready, int64_t count,
+                   const float *clip, int64_t *step, double base_lr, double momentum, double dampening, int nesterov,
+                   double weight_decay, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
+                   unsigned int *ticket, const unsigned char *skip_flag, void *stream);
+
+/* torch.optim.Adagrad: clr = lr / (1 + *step * lr_decay) (torch's step counts this step), state_sum += g * g,
+ * param += -clr * g / (sqrt(state_sum) + eps).  state_sum starts at initial_accumulator_value (the caller's fill). */
+int lcrec_adagrad_step(float *params, float *grads, float *state_sum, int64_t count, const float *clip, int64_t *step,
+                       double base_lr, double lr_decay, double eps, double weight_decay, int schedule, int64_t warmup_steps,
+                       int64_t total_steps, float *lr_out, unsigned int *ticket, const unsigned char *skip_flag, void *stream);
+
+/* torch.optim.RMSprop: square_avg = alpha * square_avg + (1 - alpha) * g * g; centered (grad_avg[count] given, else
+ * NULL): grad_avg = lerp(grad_avg, g, 1 - alpha), avg = sqrt(square_avg - grad_avg^2) + eps; else avg = sqrt(square_avg)
+ * + eps.  momentum > 0 (momentum_buffer[count] given, else NULL): buf = momentum * buf + g / avg, param -= lr * buf;
+ * else param -= lr * g / avg. */
+int lcrec_rmsprop_step(float *params, float *grads, float *square_avg, float *momentum_buffer, float *grad_avg, int64_t count,
+                       const float *clip, int64_t *step, double base_lr, double alpha, double eps, double weight_decay,
+                       double momentum, int centered, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
+                       unsigned int *ticket, const unsigned char *skip_flag, void *stream);
+
 /* Which items share an identical index tuple.  Replaces the Python string-set / dict passes of
  * index/trainer.py:139-150 (collision rate) and index/generate_indices.py:18-42
  * (check_collision, get_indices_count, get_collision_item), keeping get_collision_item's order:

@@ -27,7 +27,8 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "sinkhorn_small", "rq_apply_level", "code_stats", "ema_update",
                                            "collision_groups", "linear_fwd_pp_256x128", "linear_fwd_64x64", "sinkhorn_slab",
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
-                                           "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64"};
+                                           "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
+                                           "optim_step"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -434,6 +435,32 @@ LCREC_API int lcrec_adamw_step(float *params, float *grads, float *exp_avg, floa
 {
     return adamw_step(params, grads, exp_avg, exp_avg_sq, count, clip, step, base_lr, beta1, beta2, eps, weight_decay, decoupled,
                       schedule, warmup_steps, total_steps, lr_out, ticket, skip_flag, (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_sgd_step(float *params, float *grads, float *momentum_buffer, unsigned char *momentum_ready, int64_t count,
+                             const float *clip, int64_t *step, double base_lr, double momentum, double dampening, int nesterov,
+                             double weight_decay, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
+                             unsigned int *ticket, const unsigned char *skip_flag, void *stream)
+{
+    return sgd_step(params, grads, momentum_buffer, momentum_ready, count, clip, step, base_lr, momentum, dampening, nesterov,
+                    weight_decay, schedule, warmup_steps, total_steps, lr_out, ticket, skip_flag, (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_adagrad_step(float *params, float *grads, float *state_sum, int64_t count, const float *clip, int64_t *step,
+                                 double base_lr, double lr_decay, double eps, double weight_decay, int schedule, int64_t warmup_steps,
+                                 int64_t total_steps, float *lr_out, unsigned int *ticket, const unsigned char *skip_flag, void *stream)
+{
+    return adagrad_step(params, grads, state_sum, count, clip, step, base_lr, lr_decay, eps, weight_decay, schedule, warmup_steps,
+                        total_steps, lr_out, ticket, skip_flag, (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_rmsprop_step(float *params, float *grads, float *square_avg, float *momentum_buffer, float *grad_avg, int64_t count,
+                                 const float *clip, int64_t *step, double base_lr, double alpha, double eps, double weight_decay,
+                                 double momentum, int centered, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
+                                 unsigned int *ticket, const unsigned char *skip_flag, void *stream)
+{
+    return rmsprop_step(params, grads, square_avg, momentum_buffer, grad_avg, count, clip, step, base_lr, alpha, eps, weight_decay,
+                        momentum, centered, schedule, warmup_steps, total_steps, lr_out, ticket, skip_flag, (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_codebook_grad(const float *count, const float *sum, const float *codebook, int K, int e, float scale,

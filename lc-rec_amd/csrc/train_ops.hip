@@ -9,6 +9,8 @@
 //   grad_norm_clip     global L2 norm of all gradients + clip coefficient (clip_grad_norm_(.., 1.0), trainer.py:118)
 //   adamw_step         clipped AdamW / Adam update with the warm-up schedule evaluated on the device
 //                      (trainer.py:49-92,119-120)
+//   sgd_step, adagrad_step, rmsprop_step
+//                      the same for the reference's other learners (trainer.py:49-81)
 //
 // All of it is HBM/L2-bound streaming over [batch][features] or over the flat parameter buffer; no MFMA.  Column
 // reductions (BatchNorm statistics, bias gradients) are done by one 1024-thread workgroup per strip of 8-32 columns
@@ -840,7 +842,8 @@ struct AdamParams {
 
 // learning rate of optimiser step `s` (0-based): base_lr * lambda(s), the python-double arithmetic of
 // transformers' get_{linear,constant}_schedule_with_warmup (reference index/trainer.py:83-92)
-__device__ __forceinline__ double lr_at(const AdamParams &a, int64_t s)
+template <class P>
+__device__ __forceinline__ double lr_at(const P &a, int64_t s)
 {
     if (a.schedule < 0) return a.base_lr;
     double f;
@@ -919,6 +922,139 @@ __global__ __launch_bounds__(ADAM_THREADS) void adamw_step_kernel(AdamParams a)
 }
 
 __global__ void step_advance_kernel(int64_t *step, const unsigned char *skip) { if (!(skip && *skip)) *step += 1; }
+
+// torch.optim.SGD / Adagrad / RMSprop (the other learners of reference index/trainer.py:49-81), single-tensor
+// formulation, on the flat buffers, with everything adamw_step_kernel does around the rule itself: the clip coefficient
+// on the way in (stored back when it changed the gradient), the learning rate from the device step counter, lr_out, the
+// step advance (ticket) and the NaN skip.  State in fp32, hyper-parameters in double folded to float once.  Element by
+// element the arithmetic is that of torch's CPU kernels for each op of _single_tensor_{sgd,adagrad,rmsprop}:
+//   x.add(y, alpha=a)          fma(a, y, x)
+//   x.addcmul(y, z, value=a)   fma(a * y, z, x)
+//   x.addcdiv(y, z, value=a)   x + (a * y) / z
+//   x.lerp(y, w)               |w| < 0.5: fma(w, y - x, x), else fma(w - 1, y - x, y)
+//   x.mul(a), sqrt, add        one rounding each (IEEE sqrt and division, no approximations)
+enum OptimRule { RULE_SGD = 0, RULE_ADAGRAD = 1, RULE_RMSPROP = 2 };
+
+struct OptimParams {
+    float *p, *g;
+    float *buf;              // momentum buffer: SGD / RMSprop with momentum != 0, else NULL
+    float *sq;               // Adagrad: state_sum; RMSprop: square_avg
+    float *gavg;             // RMSprop centered: grad_avg, else NULL
+    unsigned char *buf_ready;    // SGD with momentum: device byte, 0 until a step has set buf = g (torch's first step)
+    int64_t count;
+    const float *clip;       // [2]: norm, coefficient; or NULL (no clipping)
+    int64_t *step;           // device step counter, as in AdamParams
+    double base_lr, weight_decay, momentum, dampening, lr_decay, alpha, eps;
+    int nesterov, centered;
+    int schedule;
+    int64_t warmup_steps, total_steps;
+    float *lr_out;
+    unsigned *ticket;
+    const unsigned char *skip;
+};
+
+template <int RULE>
+__global__ __launch_bounds__(ADAM_THREADS) void optim_step_kernel(OptimParams a)
+{
+    const bool skip = a.skip && *a.skip;              // uniform over the launch
+    const int64_t s = *a.step;                       // steps taken before this one
+    const bool first = RULE == RULE_SGD && a.buf && !*a.buf_ready;
+    const double lr = lr_at(a, s);
+    const float coef = a.clip ? a.clip[1] : 1.0f;
+    const bool decay = a.weight_decay != 0.0;
+    const float wd = (float)a.weight_decay, mom = (float)a.momentum, epsf = (float)a.eps;
+    const float neg_lr = (float)(-lr);
+    // SGD: buf.mul_(momentum).add_(grad, alpha=1 - dampening).  Adagrad: clr = lr / (1 + (step - 1) * lr_decay), step the
+    // post-increment count.  RMSprop: square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha), grad_avg.lerp_(grad, 1 - alpha).
+    const float one_m_damp = (float)(1.0 - a.dampening);
+    const float neg_clr = (float)(-(lr / (1.0 + (double)s * a.lr_decay)));
+    const float alphaf = (float)a.alpha, one_m_alpha = (float)(1.0 - a.alpha);
+    const bool lerp_small = __builtin_fabsf(one_m_alpha) < 0.5f;
+    const float lerp_w = lerp_small ? one_m_alpha : one_m_alpha - 1.0f;
+    if (!skip) {
+        // one element: returns the clipped gradient, updates p and the rule's state (b: momentum buffer, q: sum of squares,
+        // ga: RMSprop's grad_avg) in place
+        auto one = [&](float &p, float g0, float &b, float &q, float &ga) {
+            const float gc = g0 * coef;
+            float g = gc;
+            if (decay) g = __builtin_fmaf(wd, p, g);                      // grad.add(param, alpha=weight_decay)
+            if (RULE == RULE_SGD) {
+                if (a.buf) {
+                    b = first ? g : __builtin_fmaf(one_m_damp, g, b * mom);
+                    g = a.nesterov ? __builtin_fmaf(mom, b, g) : b;      // grad.add(buf, alpha=momentum) | buf
+                }
+                p = __builtin_fmaf(neg_lr, g, p);                        // param.add_(grad, alpha=-lr)
+            } else if (RULE == RULE_ADAGRAD) {
+                q = __builtin_fmaf(g, g, q);                             // state_sum.addcmul_(grad, grad, value=1)
+                const float std = __builtin_sqrtf(q) + epsf;
+                p = p + (neg_clr * g) / std;                             // param.addcdiv_(grad, std, value=-clr)
+            } else {
+                q = __builtin_fmaf(one_m_alpha * g, g, q * alphaf);
+                float avg;
+                if (a.centered) {
+                    ga = __builtin_fmaf(lerp_w, g - ga, lerp_small ? ga : g);
+                    avg = __builtin_sqrtf(__builtin_fmaf(-ga, ga, q));   // square_avg.addcmul(grad_avg, grad_avg, value=-1).sqrt_()
+                } else {
+                    avg = __builtin_sqrtf(q);
+                }
+                avg = avg + epsf;
+                if (a.buf) {
+                    b = b * mom + g / avg;                               // buf.mul_(momentum).addcdiv_(grad, avg)
+                    p = __builtin_fmaf(neg_lr, b, p);                    // param.add_(buf, alpha=-lr)
+                } else {
+                    p = p + (neg_lr * g) / avg;                          // param.addcdiv_(grad, avg, value=-lr)
+                }
+            }
+            return gc;
+        };
+        // the buffers this rule reads and writes (the others are NULL and never touched)
+        float *const B = a.buf, *const Q = RULE == RULE_SGD ? nullptr : a.sq, *const GA = RULE == RULE_RMSPROP ? a.gavg : nullptr;
+        const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)B | (uintptr_t)Q | (uintptr_t)GA) & 15) == 0;
+        const bool write_g = coef != 1.0f;
+        const int64_t quads = vec ? a.count / 4 : 0;
+        for (int64_t i = (int64_t)blockIdx.x * ADAM_THREADS + threadIdx.x; i < quads; i += (int64_t)gridDim.x * ADAM_THREADS) {
+            float4 p = reinterpret_cast<float4 *>(a.p)[i];
+            const float4 g = reinterpret_cast<const float4 *>(a.g)[i];
+            float4 b = B ? reinterpret_cast<float4 *>(B)[i] : float4{};
+            float4 q = Q ? reinterpret_cast<float4 *>(Q)[i] : float4{};
+            float4 ga = GA ? reinterpret_cast<float4 *>(GA)[i] : float4{};
+            float4 gc;
+            gc.x = one(p.x, g.x, b.x, q.x, ga.x); gc.y = one(p.y, g.y, b.y, q.y, ga.y);
+            gc.z = one(p.z, g.z, b.z, q.z, ga.z); gc.w = one(p.w, g.w, b.w, q.w, ga.w);
+            if (write_g) reinterpret_cast<float4 *>(a.g)[i] = gc;
+            reinterpret_cast<float4 *>(a.p)[i] = p;
+            if (B) reinterpret_cast<float4 *>(B)[i] = b;
+            if (Q) reinterpret_cast<float4 *>(Q)[i] = q;
+            if (GA) reinterpret_cast<float4 *>(GA)[i] = ga;
+        }
+        for (int64_t i = quads * 4 + (int64_t)blockIdx.x * ADAM_THREADS + threadIdx.x; i < a.count; i += (int64_t)gridDim.x * ADAM_THREADS) {
+            float p = a.p[i], b = B ? B[i] : 0.f, q = Q ? Q[i] : 0.f, ga = GA ? GA[i] : 0.f;
+            const float gc = one(p, a.g[i], b, q, ga);
+            if (write_g) a.g[i] = gc;
+            a.p[i] = p;
+            if (B) B[i] = b;
+            if (Q) Q[i] = q;
+            if (GA) GA[i] = ga;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0 && a.lr_out) *a.lr_out = (float)lr;
+    }
+    if (a.ticket) {
+        // as in adamw_step_kernel: the last workgroup, past everyone's reads of *step and *buf_ready, advances both
+        __syncthreads();
+        if (threadIdx.x == 0 && ticket_is_last(a.ticket, gridDim.x) && !skip) {
+            *a.step = s + 1;
+            if (first) *a.buf_ready = 1;
+        }
+    }
+}
+
+// the ticket-less form's second launch: step counter and (SGD momentum) the buffer-holds-a-value byte
+__global__ void optim_advance_kernel(int64_t *step, unsigned char *buf_ready, const unsigned char *skip)
+{
+    if (skip && *skip) return;
+    *step += 1;
+    if (buf_ready) *buf_ready = 1;
+}
 
 // The scalar tail of a step, one thread: level losses and their mean (vq.py:90-92, rq.py:53), total loss (rqvae.py:83),
 // the trainer's running sums (trainer.py:122-123) and its NaN check (trainer.py:116) as a sticky device flag.
@@ -1315,6 +1451,68 @@ int adamw_step(float *p, float *g, float *m, float *v, int64_t count, const floa
     hipLaunchKernelGGL(adamw_step_kernel, dim3((unsigned)blocks), dim3(ADAM_THREADS), 0, stream, a);
     if (!ticket) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, stream, step, skip);
     return check_launch("adamw_step_kernel");
+}
+
+template <int RULE>
+static int launch_optim_step(const OptimParams &a, const char *what, hipStream_t stream)
+{
+    if (!a.p || !a.g || !a.step) return fail(LCREC_EINVAL, "%s: NULL pointer", what);
+    if (a.count < 1) return fail(LCREC_EINVAL, "%s: empty parameter buffer", what);
+    if (a.schedule < -1 || a.schedule > 1) return fail(LCREC_EINVAL, "%s: schedule %d (supported: -1 none, 0 constant, 1 linear)", what, a.schedule);
+    if (!(a.base_lr >= 0.0) || !(a.weight_decay >= 0.0)) return fail(LCREC_EINVAL, "%s: lr and weight_decay must be >= 0", what);
+    int64_t blocks = (a.count + ADAM_THREADS * 8 - 1) / (ADAM_THREADS * 8);
+    if (blocks > TICKET_MAX_WORKGROUPS) blocks = TICKET_MAX_WORKGROUPS;
+    TraceScope trace(K_OPTIM_STEP, stream);
+    hipLaunchKernelGGL(optim_step_kernel<RULE>, dim3((unsigned)blocks), dim3(ADAM_THREADS), 0, stream, a);
+    if (!a.ticket) hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(1), 0, stream, a.step, a.buf_ready, a.skip);
+    return check_launch(what);
+}
+
+int sgd_step(float *p, float *g, float *buf, unsigned char *buf_ready, int64_t count, const float *clip, int64_t *step, double base_lr,
+             double momentum, double dampening, int nesterov, double weight_decay, int schedule, int64_t warmup_steps,
+             int64_t total_steps, float *lr_out, unsigned *ticket, const unsigned char *skip, hipStream_t stream)
+{
+    if (!(momentum >= 0.0)) return fail(LCREC_EINVAL, "sgd_step: momentum %g (must be >= 0)", momentum);
+    if (momentum != 0.0 && (!buf || !buf_ready))
+        return fail(LCREC_EINVAL, "sgd_step: momentum != 0 needs momentum_buffer and momentum_ready");
+    if (momentum == 0.0 && (buf || buf_ready)) return fail(LCREC_EINVAL, "sgd_step: momentum_buffer given with momentum 0");
+    if (nesterov && (momentum <= 0.0 || dampening != 0.0))
+        return fail(LCREC_EINVAL, "sgd_step: nesterov momentum requires a momentum and zero dampening");
+    OptimParams a = {};
+    a.p = p; a.g = g; a.buf = buf; a.buf_ready = buf_ready; a.count = count; a.clip = clip; a.step = step;
+    a.base_lr = base_lr; a.weight_decay = weight_decay; a.momentum = momentum; a.dampening = dampening; a.nesterov = nesterov != 0;
+    a.schedule = schedule; a.warmup_steps = warmup_steps; a.total_steps = total_steps; a.lr_out = lr_out; a.ticket = ticket; a.skip = skip;
+    return launch_optim_step<RULE_SGD>(a, "sgd_step", stream);
+}
+
+int adagrad_step(float *p, float *g, float *state_sum, int64_t count, const float *clip, int64_t *step, double base_lr, double lr_decay,
+                 double eps, double weight_decay, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
+                 unsigned *ticket, const unsigned char *skip, hipStream_t stream)
+{
+    if (!state_sum) return fail(LCREC_EINVAL, "adagrad_step: NULL pointer");
+    if (!(lr_decay >= 0.0) || !(eps >= 0.0)) return fail(LCREC_EINVAL, "adagrad_step: lr_decay and eps must be >= 0");
+    OptimParams a = {};
+    a.p = p; a.g = g; a.sq = state_sum; a.count = count; a.clip = clip; a.step = step;
+    a.base_lr = base_lr; a.weight_decay = weight_decay; a.lr_decay = lr_decay; a.eps = eps;
+    a.schedule = schedule; a.warmup_steps = warmup_steps; a.total_steps = total_steps; a.lr_out = lr_out; a.ticket = ticket; a.skip = skip;
+    return launch_optim_step<RULE_ADAGRAD>(a, "adagrad_step", stream);
+}
+
+int rmsprop_step(float *p, float *g, float *square_avg, float *buf, float *grad_avg, int64_t count, const float *clip, int64_t *step,
+                 double base_lr, double alpha, double eps, double weight_decay, double momentum, int centered, int schedule,
+                 int64_t warmup_steps, int64_t total_steps, float *lr_out, unsigned *ticket, const unsigned char *skip, hipStream_t stream)
+{
+    if (!square_avg) return fail(LCREC_EINVAL, "rmsprop_step: NULL pointer");
+    if (!(alpha >= 0.0) || !(eps >= 0.0) || !(momentum >= 0.0)) return fail(LCREC_EINVAL, "rmsprop_step: alpha, eps and momentum must be >= 0");
+    if ((momentum > 0.0) != (buf != nullptr))
+        return fail(LCREC_EINVAL, "rmsprop_step: momentum_buffer must be given exactly when momentum > 0");
+    if ((centered != 0) != (grad_avg != nullptr))
+        return fail(LCREC_EINVAL, "rmsprop_step: grad_avg must be given exactly when centered");
+    OptimParams a = {};
+    a.p = p; a.g = g; a.sq = square_avg; a.buf = buf; a.gavg = grad_avg; a.count = count; a.clip = clip; a.step = step;
+    a.base_lr = base_lr; a.weight_decay = weight_decay; a.alpha = alpha; a.eps = eps; a.momentum = momentum; a.centered = centered != 0;
+    a.schedule = schedule; a.warmup_steps = warmup_steps; a.total_steps = total_steps; a.lr_out = lr_out; a.ticket = ticket; a.skip = skip;
+    return launch_optim_step<RULE_RMSPROP>(a, "rmsprop_step", stream);
 }
 
 }  // namespace lcrec

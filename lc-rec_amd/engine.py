@@ -16,14 +16,16 @@ the same lcrec_* entry points the module API uses, so forward values and GEMM gr
                                                                        lcrec_linear_backward (dX), and ONE grouped launch
                                                                        for all weight gradients, written straight into the
                                                                        flat gradient buffer (lcrec_linear_backward_weights)
-    clip 1.0 + AdamW + warm-up schedule                                lcrec_grad_norm_clip, lcrec_adamw_step (learning
-                                                                       rate and bias corrections from a device step counter)
+    clip 1.0 + optimiser + warm-up schedule                            lcrec_grad_norm_clip, lcrec_adamw_step (Adam/AdamW) or
+                                                                       lcrec_{sgd,adagrad,rmsprop}_step (learning rate and
+                                                                       bias corrections from a device step counter)
     loss sums, NaN flag                                                device accumulators, read once per epoch
 
 and captures it with torch.cuda.CUDAGraph (a hipGraph) once per batch size: a step is then one index_select, one copy
-and one graph launch on the host.  Parameters, gradients and both Adam moments live in four flat fp32 buffers; the
-module's nn.Parameters (and the torch optimizer's state entries, so checkpoints keep the reference's layout) are views
-into them.
+and one graph launch on the host.  Parameters, gradients and the optimiser's state (both Adam moments; SGD's momentum
+buffer; Adagrad's sum; RMSprop's square_avg, momentum_buffer, grad_avg -- only those the rule keeps) live in flat fp32
+buffers; the module's nn.Parameters (and the torch optimizer's state entries, under torch's own keys, so checkpoints keep
+the reference's layout) are views into them.
 
 Measured and dropped: weight gradients (leaves of the dependency graph) and the per-code statistics on a second stream,
 i.e. parallel branches in the captured graph, so that the narrow layers' GEMMs run beside the dX chain: 26 fork/join
@@ -35,7 +37,8 @@ branches' under-filled kernels side by side to any useful degree.
 The EMA codebook update of index_improve/ is part of the captured step (lcrec_ema_update); the steps on which a dead-code
 reset is due run eagerly.  Data-parallel runs use the same line with the exchanges in it.  What the
 engine does not cover falls back to the autograd path in trainer.py, unchanged: dropout > 0, activations other than ReLU,
-optimisers other than Adam/AdamW, --strict_nan_check (the reference's per-step host sync).
+optimisers other than Adam/AdamW/SGD/Adagrad/RMSprop (and those with maximize, differentiable, Adam's amsgrad, more than
+one param group or sparse gradients), --strict_nan_check (the reference's per-step host sync).
 """
 import os
 
@@ -52,11 +55,27 @@ _ALIGN = 64     # floats: every parameter starts on a 256-byte boundary of the f
 # rule; LCREC_DW_SPLITS, tuning)
 DW_SPLITS = int(os.environ.get("LCREC_DW_SPLITS", "1"))
 
+# the hyper-parameters (torch's param_group keys) each of the other rules' kernels reads
+_HYPER = {"sgd": ("momentum", "dampening", "nesterov"), "adagrad": ("lr_decay", "eps", "initial_accumulator_value"),
+          "rmsprop": ("alpha", "eps", "momentum", "centered")}
+
+
+def _rule(optimizer):
+    """The update rule the engine runs for `optimizer` ("adam" for Adam and AdamW), or None."""
+    if isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW)):
+        return "adam"
+    for cls, rule in ((torch.optim.SGD, "sgd"), (torch.optim.Adagrad, "adagrad"), (torch.optim.RMSprop, "rmsprop")):
+        if isinstance(optimizer, cls):
+            return rule
+    return None
+
 
 class TrainEngine:
     def __init__(self, model, optimizer, schedule, warmup_steps, total_steps, max_norm=1.0, use_graph=True, use_ema=False,
-                 dist=None, dp_graph="auto", fuse_bn=None):
+                 dist=None, dp_graph="auto", fuse_bn=None, scheduler=None):
         """schedule: "linear" | "constant" (index/trainer.py:83-92) or None (fixed learning rate).
+        scheduler: the LambdaLR driving `optimizer`, if any: SGD keeps no step count in its state, so the steps taken before
+        the engine takes over are its last_epoch.
         use_ema: the improve fork's EMA codebook update after every step (index_improve/trainer.py:119).
         dist: an enabled dist.DistContext for item-sharded data parallel (the caller sets dist.set_batch before a step).
         dp_graph: "on" captures the data-parallel step with its RCCL collectives; "off" launches the same line eagerly;
@@ -80,14 +99,20 @@ class TrainEngine:
         self.schedule = {"linear": 1, "constant": 0, None: -1}[schedule]
         self.warmup_steps, self.total_steps = int(warmup_steps), int(total_steps)
         group = optimizer.param_groups[0]
+        self.rule = _rule(optimizer)
         self.base_lr = float(group.get("initial_lr", group["lr"]))
-        self.betas = tuple(group["betas"])
-        self.eps = float(group["eps"])
         self.weight_decay = float(group["weight_decay"])
-        self.decoupled = isinstance(optimizer, torch.optim.AdamW)
+        if self.rule == "adam":
+            self.betas = tuple(group["betas"])
+            self.eps = float(group["eps"])
+            self.decoupled = isinstance(optimizer, torch.optim.AdamW)
+        else:
+            self.hyper = {k: group[k] for k in _HYPER[self.rule]}
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         self.device = self.params[0].device
         self._prior_steps = 0
+        if self.rule == "sgd" and scheduler is not None:
+            self._prior_steps = int(scheduler.last_epoch)
         self._flatten()
         dev = self.device
         self.step_count = torch.full((), self._prior_steps, dtype=torch.int64, device=dev)   # optimiser steps taken (device side)
@@ -105,14 +130,26 @@ class TrainEngine:
         self._bn_pending = 0                                                 # ... and the steps not yet added to them
         # whoever reads the state dict (a checkpoint, a test) sees the host-side bookkeeping brought up to date first
         model.register_state_dict_pre_hook(lambda _m, _prefix, _keep: self.sync_host_state())
+        optimizer.register_state_dict_pre_hook(lambda _opt: self.sync_host_state())
 
     # ------------------------------------------------------------------ support matrix
     @staticmethod
     def unsupported_reason(model, optimizer, args=None, dist=None, use_ema=False):
-        if not isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW)):
+        rule = _rule(optimizer)
+        if rule is None:
             return f"optimizer {type(optimizer).__name__}"
-        if len(optimizer.param_groups) != 1 or optimizer.param_groups[0].get("amsgrad") or optimizer.param_groups[0].get("maximize"):
-            return "optimizer options"
+        if rule == "adam":
+            if len(optimizer.param_groups) != 1 or optimizer.param_groups[0].get("amsgrad") or optimizer.param_groups[0].get("maximize"):
+                return "optimizer options"
+        else:
+            name = type(optimizer).__name__
+            if len(optimizer.param_groups) != 1:
+                return f"optimizer options ({name}: more than one param group)"
+            for key in ("maximize", "differentiable"):
+                if optimizer.param_groups[0].get(key):
+                    return f"optimizer options ({name}: {key})"
+            if any(isinstance(mod, nn.Embedding) and mod.sparse for mod in model.modules()):
+                return f"optimizer options ({name}: sparse gradients)"
         if args is not None and getattr(args, "strict_nan_check", False):
             return "--strict_nan_check"
         p0 = next(model.parameters())
@@ -146,9 +183,27 @@ class TrainEngine:
         dev = self.device
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
-        self._step_f32 = torch.zeros((), dtype=torch.float32, device=dev)
+        if self.rule == "adam":
+            self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
+            self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
+            self._step_f32 = torch.zeros((), dtype=torch.float32, device=dev)
+            self._exposed = True
+        else:
+            h = self.hyper
+            if self.rule == "sgd":
+                keys = ["momentum_buffer"] if h["momentum"] != 0 else []
+            elif self.rule == "adagrad":
+                keys = ["sum"]
+            else:
+                keys = ["square_avg"] + (["momentum_buffer"] if h["momentum"] > 0 else []) + (["grad_avg"] if h["centered"] else [])
+            # torch's state keys -> flat buffers: only what the rule keeps (plain SGD: nothing)
+            self.flat_state = {k: torch.zeros(total, dtype=torch.float32, device=dev) for k in keys}
+            # SGD's first step sets buf = g: whether the buffer holds a value is a device byte of its own (set by the kernel)
+            self._buf_ready = torch.zeros((), dtype=torch.uint8, device=dev) if self.rule == "sgd" and self.flat_state else None
+            self._steps_f32 = None
+            self._state_views = []
+            self._exposed = False
+            held, step_dev = False, None
         self.grad_view = {}
         # spans of the flat buffers for the data-parallel gradient exchange: the decoder's parameters (contiguous in
         # parameter order) and whatever lies before / after them
@@ -169,6 +224,19 @@ class TrainEngine:
                 p.data = view(self.flat_p)
                 p.grad = view(self.flat_g)
                 self.grad_view[p] = p.grad
+                if self.rule != "adam":
+                    state = self.optimizer.state.get(p, {})         # (.get: plain SGD keeps no per-parameter state at all)
+                    for k, flat in self.flat_state.items():
+                        if k in state:                               # the autograd path has been here before the engine
+                            view(flat).copy_(state[k])
+                            held = True
+                        elif k == "sum":
+                            view(flat).fill_(float(self.hyper["initial_accumulator_value"]))
+                    if torch.is_tensor(state.get("step")):
+                        self._prior_steps = int(float(state["step"]))
+                        step_dev = state["step"].device
+                    self._state_views.append({k: view(flat) for k, flat in self.flat_state.items()})
+                    continue
                 state = self.optimizer.state[p]
                 if "exp_avg" in state:                                   # steps were taken before the engine took over
                     view(self.flat_m).copy_(state["exp_avg"])
@@ -177,6 +245,28 @@ class TrainEngine:
                 state["step"] = self._step_f32
                 state["exp_avg"] = view(self.flat_m)
                 state["exp_avg_sq"] = view(self.flat_v)
+        if self.rule in ("adagrad", "rmsprop"):
+            # torch keeps a float32 `step` per parameter (Adagrad's clr reads it): one element each of a buffer that
+            # sync_host_state fills -- on the host, as torch keeps it, unless it already lives elsewhere or is capturable
+            if step_dev is None:
+                step_dev = dev if self.optimizer.param_groups[0].get("capturable") else torch.device("cpu")
+            self._steps_f32 = torch.zeros(len(self.params), dtype=torch.float32, device=step_dev)
+        if self.rule != "adam" and held:
+            if self._buf_ready is not None:
+                self._buf_ready.fill_(1)
+            self._expose_state()
+
+    def _expose_state(self):
+        """The optimizer's state entries of the rules other than Adam become views of the flat buffers, under torch's keys and
+        in its order -- when torch itself would have them: at construction for Adagrad, after the first step otherwise."""
+        self._exposed = True
+        for i, (p, views) in enumerate(zip(self.params, self._state_views)):
+            if not views and self._steps_f32 is None:
+                continue                                             # plain SGD: the state stays empty
+            state = self.optimizer.state[p]
+            if self._steps_f32 is not None:
+                state["step"] = self._steps_f32[i]
+            state.update(views)
 
     # ------------------------------------------------------------------ the step, as library calls
     def _mlp_forward(self, mlp, h):
@@ -344,10 +434,30 @@ class TrainEngine:
                 ops.ema_update(lvl._ema_cluster_size, lvl._ema_w, lvl.embedding.weight.data, stats[t][0], stats[t][1],
                                lvl.ema_decay, lvl.epsilon, skip_flag=self.bad[0])
         ops.grad_norm_clip(self.flat_g, self.max_norm, out=self.clip)
-        ops.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.step_count, self.base_lr, self.betas, self.eps,
-                       self.weight_decay, self.decoupled, clip=self.clip, schedule=self.schedule,
-                       warmup_steps=self.warmup_steps, total_steps=self.total_steps, lr_out=self.lr_used,
-                       skip_flag=self.bad[0])            # a NaN loss (sticky) leaves parameters, moments and step at the last good step
+        if self.rule == "adam":
+            ops.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.step_count, self.base_lr, self.betas, self.eps,
+                           self.weight_decay, self.decoupled, clip=self.clip, schedule=self.schedule,
+                           warmup_steps=self.warmup_steps, total_steps=self.total_steps, lr_out=self.lr_used,
+                           skip_flag=self.bad[0])        # a NaN loss (sticky) leaves parameters, moments and step at the last good step
+        else:
+            self._update()
+
+    def _update(self):
+        """The update of SGD / Adagrad / RMSprop, with everything around it as for Adam: clipped gradient, device step counter
+        and schedule, the learning rate used, and the NaN flag that freezes parameters, state and counter."""
+        h, st = self.hyper, self.flat_state
+        common = dict(clip=self.clip, schedule=self.schedule, warmup_steps=self.warmup_steps, total_steps=self.total_steps,
+                      lr_out=self.lr_used, skip_flag=self.bad[0])
+        if self.rule == "sgd":
+            ops.sgd_step(self.flat_p, self.flat_g, self.step_count, self.base_lr, h["momentum"], h["dampening"], h["nesterov"],
+                         self.weight_decay, momentum_buffer=st.get("momentum_buffer"), momentum_ready=self._buf_ready, **common)
+        elif self.rule == "adagrad":
+            ops.adagrad_step(self.flat_p, self.flat_g, st["sum"], self.step_count, self.base_lr, h["lr_decay"], h["eps"],
+                             self.weight_decay, **common)
+        else:
+            ops.rmsprop_step(self.flat_p, self.flat_g, st["square_avg"], self.step_count, self.base_lr, h["alpha"], h["eps"],
+                             self.weight_decay, h["momentum"], h["centered"], momentum_buffer=st.get("momentum_buffer"),
+                             grad_avg=st.get("grad_avg"), **common)
 
     # ------------------------------------------------------------------ driving it
     def step_selected(self, data, index):
@@ -369,6 +479,8 @@ class TrainEngine:
             rows = (rows, held[1])                                           # a graph per (local, global) batch shape
         self.host_steps += 1
         self._bn_pending += 1
+        if not self._exposed:
+            self._expose_state()
         # a step on which a level's dead-code reset is due (host logic, random draws, data-dependent shapes) runs eagerly
         reset_due = any((q.step_count + 1) % q.reset_interval == 0 for q in self.ema_levels)
         entry = self._graphs.get(rows)
@@ -462,9 +574,12 @@ class TrainEngine:
         return float(vals[0]), float(vals[1])
 
     def sync_host_state(self, scheduler=None):
-        """Make what the host can see agree with the device: the optimizer's per-parameter `step` entries (checkpoints)
-        and the LambdaLR scheduler's counters and `lr` (logging, get_last_lr)."""
-        self._step_f32.fill_(float(self.host_steps))
+        """Make what the host can see agree with the device: the optimizer's per-parameter `step` entries (checkpoints; Adam,
+        Adagrad, RMSprop) and the LambdaLR scheduler's counters and `lr` (logging, get_last_lr)."""
+        if self.rule == "adam":
+            self._step_f32.fill_(float(self.host_steps))
+        elif self._steps_f32 is not None:
+            self._steps_f32.fill_(float(self.host_steps))
         if self._bn_pending and self._bn_counters:
             torch._foreach_add_(self._bn_counters, self._bn_pending)
         self._bn_pending = 0

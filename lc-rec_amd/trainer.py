@@ -186,7 +186,7 @@ class Trainer(object):
                 kind = "linear" if self.lr_scheduler_type.lower() == "linear" else "constant"
                 self.engine = TrainEngine(self.model, self.optimizer, kind, self.warmup_steps, self.max_steps,
                                           use_ema=self.use_ema, dist=self.dist,
-                                          dp_graph=getattr(self.args, "dp_graph", "auto"))
+                                          dp_graph=getattr(self.args, "dp_graph", "auto"), scheduler=self.scheduler)
                 self.logger.info("training step: %s (lcrec_amd.engine)", "one captured hipGraph per batch size"
                                  if self.engine.use_graph else "the engine's straight line, launched eagerly")
             else:

@@ -2,7 +2,7 @@
 """Secondary metric: RQ-VAE training-step throughput on one MI355X (reference index/trainer.py:111-120;
 the reference's CPU path does ~7-12 k items/s at batch 2048).
 
-    python tools/train_probe.py [--in_dim 768] [--batch 2048] [--steps 30] [--bn] [--ema]
+    python tools/train_probe.py [--in_dim 768] [--batch 2048] [--steps 30] [--bn] [--ema] [--learner AdamW|Adam|SGD|Adagrad|RMSprop]
 """
 import argparse
 import os
@@ -28,7 +28,8 @@ def trainer_probe(a):
         argv = ["--data_path", "unused", "--ckpt_dir", tmp, "--device", dev, "--batch_size", str(a.batch), "--epochs", "4",
                 "--no_kmeans_init", "--num_emb_list", "256", "256", "256", "256",          # run.sh: 4 levels, Sinkhorn on the last
                 "--sk_epsilons", "0.0", "0.0", "0.0", "0.0" if a.no_sk else "0.003"] \
-            + (["--bn", "True"] if a.bn else ["--no_bn"]) + (["--strict_nan_check"] if a.strict else []) + ["--train_engine", a.engine]
+            + (["--bn", "True"] if a.bn else ["--no_bn"]) + (["--strict_nan_check"] if a.strict else []) + ["--train_engine", a.engine] \
+            + ["--learner", a.learner]
         args = cli.parse_args(argv)
         ctx = None
         if a.rccl1:
@@ -66,7 +67,7 @@ def trainer_probe(a):
         if ctx is not None:
             ldist.shutdown(ctx)
         print(f"Trainer._train_epoch{' [one-rank RCCL group, %d collectives/step]' % (eng.collectives // 2 if eng is not None else -1) if a.rccl1 else ''}: "
-              f"in_dim {a.in_dim} batch {a.batch} levels 4 sinkhorn {not a.no_sk} bn {a.bn} strict_nan_check {a.strict} "
+              f"in_dim {a.in_dim} batch {a.batch} levels 4 sinkhorn {not a.no_sk} bn {a.bn} strict_nan_check {a.strict} learner {a.learner} "
               f"engine {'hipGraph (%d replays)' % eng.graph_replays if eng is not None else 'off (autograd path)'}: "
               f"{dt / steps * 1e3:.3f} ms/step, {a.batch * steps / dt:,.0f} items/s")
 
@@ -83,6 +84,8 @@ def main():
     ap.add_argument("--cprofile", action="store_true", help="with --trainer: cProfile of the timed epochs")
     ap.add_argument("--engine", default="auto", choices=["auto", "off"], help="with --trainer: --train_engine of lcrec_amd.main")
     ap.add_argument("--rccl1", action="store_true", help="with --trainer: data-parallel step on a one-rank RCCL group")
+    ap.add_argument("--learner", default="AdamW", choices=["AdamW", "Adam", "SGD", "Adagrad", "RMSprop"],
+                    help="the optimiser (--learner of lcrec_amd.main)")
     ap.add_argument("--trainer", action="store_true",
                     help="time lcrec_amd.trainer.Trainer._train_epoch itself (loader, NaN check, fused AdamW, schedule)")
     a = ap.parse_args()
@@ -99,7 +102,9 @@ def main():
         for q in model.rq.vq_layers:
             q.embedding.weight.copy_(z[torch.randperm(a.batch, device=dev)[:256]] * 0.5)
     model.train()
-    opt = torch.optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-4, fused=True)      # what Trainer builds on a HIP device
+    # what Trainer builds on a HIP device (trainer.py, _build_optimizer)
+    fused = {"fused": True} if a.learner in ("AdamW", "Adam") else {}
+    opt = getattr(torch.optim, a.learner)(model.parameters(), lr=1e-3, weight_decay=1e-4, **fused)
     sched = linear_schedule_with_warmup(opt, 10, 10000)
 
     def step():
@@ -123,7 +128,7 @@ def main():
     dt = time.perf_counter() - t0
     tr = ops.trace_collect()
     ops.trace_enable(False)
-    print(f"in_dim {a.in_dim} batch {a.batch} bn {a.bn} ema {a.ema}: {dt / a.steps * 1e3:.3f} ms/step, "
+    print(f"in_dim {a.in_dim} batch {a.batch} bn {a.bn} ema {a.ema} learner {a.learner}: {dt / a.steps * 1e3:.3f} ms/step, "
           f"{a.batch * a.steps / dt:,.0f} items/s, loss {loss.item():.4f}")
     lib_ms = sum(v[1] for v in tr.values()) / a.steps
     print(f"  lcrec kernels: {lib_ms:.3f} ms/step ->", {k: (v[0] // a.steps, round(v[1] / a.steps, 3)) for k, v in tr.items()})

@@ -444,15 +444,17 @@ int lcrec_quantizer_input_grad_bias(const float *z, const float *codebook0, cons
  * then increments it -- so a captured hipGraph of a training step replays without any host-side scalar.
  * lr_out: device float receiving the learning rate used, or NULL.
  * ticket: NULL, or see "ticket arguments": the increment is then made by the last workgroup of the update launch.
- * skip_flag: NULL, or a device byte; non-zero = update nothing and leave *step (see lcrec_ema_update). */
+ * skip_flag: NULL, or a device byte; non-zero = update nothing and leave *step (see lcrec_ema_update).
+ * base_lr and weight_decay must be >= 0, as for the other learners below (all four share one launcher; torch refuses
+ * such an optimiser at construction). */
 int lcrec_adamw_step(float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t count, const float *clip,
                      int64_t *step, double base_lr, double beta1, double beta2, double eps, double weight_decay,
                      int decoupled, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
                      unsigned int *ticket, const unsigned char *skip_flag, void *stream);
 
-/* The reference's other learners (index/trainer.py:49-81,118-120) on flat fp32 buffers, each with everything
- * lcrec_adamw_step does around its rule: grads *= clip[1] first (stored back when clip[1] != 1; clip may be NULL), the
- * learning rate lr(*step) from `schedule` / warmup_steps / total_steps, lr_out, the increment of *step (by the last
+/* The reference's other learners (index/trainer.py:49-81,118-120) on flat fp32 buffers: the same kernel with another
+ * rule, so around the rule everything is as for lcrec_adamw_step: grads *= clip[1] first (stored back when
+ * clip[1] != 1; clip may be NULL), the learning rate lr(*step) from `schedule` / warmup_steps / total_steps, lr_out, the increment of *step (by the last
  * workgroup with a ticket, else by a second launch), and skip_flag (non-zero: update nothing, leave *step).  Per element,
  * g = grads * clip[1], then g += weight_decay * param when weight_decay != 0; the rules are torch 2.10's
  * _single_tensor_{sgd,adagrad,rmsprop}, with each op rounded as torch's CPU kernel rounds it (add with alpha and addcmul

@@ -826,13 +826,20 @@ __global__ __launch_bounds__(RED_THREADS) void grad_norm_finish_kernel(const dou
     if (threadIdx.x == 0) norm_and_coef(s, max_norm, norm_out);
 }
 
-struct AdamParams {
-    float *p, *g, *m, *v;
+enum OptimRule { RULE_SGD = 0, RULE_ADAGRAD = 1, RULE_RMSPROP = 2, RULE_ADAM = 3 };
+
+struct OptimParams {
+    float *p, *g;
+    float *buf;              // momentum buffer: SGD / RMSprop with momentum != 0, else NULL; Adam: exp_avg
+    float *sq;               // Adagrad: state_sum; RMSprop: square_avg; Adam: exp_avg_sq
+    float *gavg;             // RMSprop centered: grad_avg, else NULL
+    unsigned char *buf_ready;    // SGD with momentum: device byte, 0 until a step has set buf = g (torch's first step)
     int64_t count;
     const float *clip;       // [2]: norm, coefficient; or NULL (no clipping)
     int64_t *step;           // device step counter: optimiser steps taken so far (incremented by the kernel's last act)
-    double base_lr, beta1, beta2, eps, weight_decay;
-    int decoupled;           // 1 = AdamW, 0 = Adam (L2 added to the gradient)
+    double base_lr, weight_decay, momentum, dampening, lr_decay, alpha, eps, beta1, beta2;
+    int nesterov, centered;
+    int decoupled;           // Adam: 1 = AdamW, 0 = Adam (L2 added to the gradient)
     int schedule;            // 0 = constant after warm-up, 1 = linear decay to 0 at total_steps, -1 = no schedule (lr = base_lr)
     int64_t warmup_steps, total_steps;
     float *lr_out;           // device float: the learning rate this step used (logging / tests), or NULL
@@ -842,8 +849,7 @@ struct AdamParams {
 
 // learning rate of optimiser step `s` (0-based): base_lr * lambda(s), the python-double arithmetic of
 // transformers' get_{linear,constant}_schedule_with_warmup (reference index/trainer.py:83-92)
-template <class P>
-__device__ __forceinline__ double lr_at(const P &a, int64_t s)
+__device__ __forceinline__ double lr_at(const OptimParams &a, int64_t s)
 {
     if (a.schedule < 0) return a.base_lr;
     double f;
@@ -859,102 +865,22 @@ __device__ __forceinline__ double lr_at(const P &a, int64_t s)
     return a.base_lr * f;
 }
 
-// torch.optim.AdamW / Adam, single-tensor formulation (the fused kernel's arithmetic: state in fp32, hyper-parameters in
-// double), on the flat parameter buffer, with the clip coefficient applied to the gradient on the way in (and stored back,
-// as clip_grad_norm_ leaves it).
-constexpr int ADAM_THREADS = 1024;
-__global__ __launch_bounds__(ADAM_THREADS) void adamw_step_kernel(AdamParams a)
-{
-    const bool skip = a.skip && *a.skip;              // uniform over the launch
-    const int64_t s = *a.step;                       // steps taken before this one
-    const double lr = lr_at(a, s);
-    const double t = (double)(s + 1);
-    const double bc1 = 1.0 - pow(a.beta1, t);
-    const double bc2_sqrt = sqrt(1.0 - pow(a.beta2, t));
-    const float coef = a.clip ? a.clip[1] : 1.0f;
-    const float step_size = (float)(lr / bc1);
-    const float b2 = (float)a.beta2, one_m_b1 = (float)(1.0 - a.beta1), one_m_b2 = (float)(1.0 - a.beta2);
-    const float epsf = (float)a.eps, bc2s = (float)bc2_sqrt;
-    const float decay = (float)(lr * a.weight_decay), wd = (float)a.weight_decay;
-    if (!skip) {
-        // one element: returns the clipped gradient (what clip_grad_norm_ leaves in .grad), updates p, m, v in place
-        auto one = [&](float &p, float g0, float &m, float &v) {
-            const float gc = g0 * coef;
-            float g = gc;
-            if (a.weight_decay != 0.0) {
-                if (a.decoupled) p -= decay * p;
-                else g += p * wd;
-            }
-            m = m + one_m_b1 * (g - m);                  // lerp(m, g, 1 - beta1)
-            v = b2 * v + one_m_b2 * g * g;
-            const float denom = __builtin_sqrtf(v) / bc2s + epsf;
-            p -= step_size * m / denom;
-            return gc;
-        };
-        // 16-byte accesses (the four flat buffers are 256-byte aligned; a caller's unaligned or ragged end goes by scalars): a
-        // quarter of the memory instructions of the dword form -- 8.9 M parameters x 8 streams were 1.1 M wave-level
-        // instructions on the address path.  The clipped gradient is written back only when clipping changed it (coef != 1).
-        const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0;
-        const bool write_g = coef != 1.0f;
-        const int64_t quads = vec ? a.count / 4 : 0;
-        for (int64_t q = (int64_t)blockIdx.x * ADAM_THREADS + threadIdx.x; q < quads; q += (int64_t)gridDim.x * ADAM_THREADS) {
-            float4 p = reinterpret_cast<float4 *>(a.p)[q], m = reinterpret_cast<float4 *>(a.m)[q], v = reinterpret_cast<float4 *>(a.v)[q];
-            const float4 g = reinterpret_cast<const float4 *>(a.g)[q];
-            float4 gc;
-            gc.x = one(p.x, g.x, m.x, v.x); gc.y = one(p.y, g.y, m.y, v.y); gc.z = one(p.z, g.z, m.z, v.z); gc.w = one(p.w, g.w, m.w, v.w);
-            if (write_g) reinterpret_cast<float4 *>(a.g)[q] = gc;
-            reinterpret_cast<float4 *>(a.p)[q] = p; reinterpret_cast<float4 *>(a.m)[q] = m; reinterpret_cast<float4 *>(a.v)[q] = v;
-        }
-        for (int64_t i = quads * 4 + (int64_t)blockIdx.x * ADAM_THREADS + threadIdx.x; i < a.count; i += (int64_t)gridDim.x * ADAM_THREADS) {
-            float p = a.p[i], m = a.m[i], v = a.v[i];
-            const float gc = one(p, a.g[i], m, v);
-            if (write_g) a.g[i] = gc;
-            a.p[i] = p; a.m[i] = m; a.v[i] = v;
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0 && a.lr_out) *a.lr_out = (float)lr;
-    }
-    if (a.ticket) {
-        // every workgroup read *step on entry; the one that finishes last -- after all the others have taken their tickets,
-        // i.e. are past that read -- advances it
-        __syncthreads();
-        if (threadIdx.x == 0 && ticket_is_last(a.ticket, gridDim.x) && !skip) *a.step = s + 1;
-    }
-}
-
-__global__ void step_advance_kernel(int64_t *step, const unsigned char *skip) { if (!(skip && *skip)) *step += 1; }
-
-// torch.optim.SGD / Adagrad / RMSprop (the other learners of reference index/trainer.py:49-81), single-tensor
-// formulation, on the flat buffers, with everything adamw_step_kernel does around the rule itself: the clip coefficient
-// on the way in (stored back when it changed the gradient), the learning rate from the device step counter, lr_out, the
-// step advance (ticket) and the NaN skip.  State in fp32, hyper-parameters in double folded to float once.  Element by
-// element the arithmetic is that of torch's CPU kernels for each op of _single_tensor_{sgd,adagrad,rmsprop}:
+// torch.optim.AdamW / Adam / SGD / Adagrad / RMSprop (the learners of reference index/trainer.py:49-81), single-tensor
+// formulation, on the flat buffers: one kernel, the rule a template parameter.  Around the rule: the clip coefficient
+// applied to the gradient on the way in (and stored back when it changed it, as clip_grad_norm_ leaves it), the learning
+// rate from the device step counter, lr_out, the step advance (ticket) and the NaN skip.  State in fp32,
+// hyper-parameters in double folded to float once.
+// Adam is the fused torch kernel's arithmetic, written out op by op (the file is built with -ffp-contract=off).  For the
+// other three, element by element the arithmetic is that of torch's CPU kernels for each op of
+// _single_tensor_{sgd,adagrad,rmsprop}:
 //   x.add(y, alpha=a)          fma(a, y, x)
 //   x.addcmul(y, z, value=a)   fma(a * y, z, x)
 //   x.addcdiv(y, z, value=a)   x + (a * y) / z
 //   x.lerp(y, w)               |w| < 0.5: fma(w, y - x, x), else fma(w - 1, y - x, y)
 //   x.mul(a), sqrt, add        one rounding each (IEEE sqrt and division, no approximations)
-enum OptimRule { RULE_SGD = 0, RULE_ADAGRAD = 1, RULE_RMSPROP = 2 };
-
-struct OptimParams {
-    float *p, *g;
-    float *buf;              // momentum buffer: SGD / RMSprop with momentum != 0, else NULL
-    float *sq;               // Adagrad: state_sum; RMSprop: square_avg
-    float *gavg;             // RMSprop centered: grad_avg, else NULL
-    unsigned char *buf_ready;    // SGD with momentum: device byte, 0 until a step has set buf = g (torch's first step)
-    int64_t count;
-    const float *clip;       // [2]: norm, coefficient; or NULL (no clipping)
-    int64_t *step;           // device step counter, as in AdamParams
-    double base_lr, weight_decay, momentum, dampening, lr_decay, alpha, eps;
-    int nesterov, centered;
-    int schedule;
-    int64_t warmup_steps, total_steps;
-    float *lr_out;
-    unsigned *ticket;
-    const unsigned char *skip;
-};
-
+constexpr int OPTIM_THREADS = 1024;
 template <int RULE>
-__global__ __launch_bounds__(ADAM_THREADS) void optim_step_kernel(OptimParams a)
+__global__ __launch_bounds__(OPTIM_THREADS) void optim_step_kernel(OptimParams a)
 {
     const bool skip = a.skip && *a.skip;              // uniform over the launch
     const int64_t s = *a.step;                       // steps taken before this one
@@ -962,24 +888,55 @@ __global__ __launch_bounds__(ADAM_THREADS) void optim_step_kernel(OptimParams a)
     const double lr = lr_at(a, s);
     const float coef = a.clip ? a.clip[1] : 1.0f;
     const bool decay = a.weight_decay != 0.0;
-    const float wd = (float)a.weight_decay, mom = (float)a.momentum, epsf = (float)a.eps;
-    const float neg_lr = (float)(-lr);
-    // SGD: buf.mul_(momentum).add_(grad, alpha=1 - dampening).  Adagrad: clr = lr / (1 + (step - 1) * lr_decay), step the
-    // post-increment count.  RMSprop: square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha), grad_avg.lerp_(grad, 1 - alpha).
-    const float one_m_damp = (float)(1.0 - a.dampening);
-    const float neg_clr = (float)(-(lr / (1.0 + (double)s * a.lr_decay)));
-    const float alphaf = (float)a.alpha, one_m_alpha = (float)(1.0 - a.alpha);
-    const bool lerp_small = __builtin_fabsf(one_m_alpha) < 0.5f;
-    const float lerp_w = lerp_small ? one_m_alpha : one_m_alpha - 1.0f;
+    const float wd = (float)a.weight_decay, epsf = (float)a.eps;
+    // the rule's constants; each instantiation computes its own only (Adam alone has the pow and sqrt in double)
+    float step_size = 0.f, bc2s = 0.f, b2 = 0.f, one_m_b1 = 0.f, one_m_b2 = 0.f, lr_wd = 0.f;
+    float mom = 0.f, neg_lr = 0.f, one_m_damp = 0.f, neg_clr = 0.f, alphaf = 0.f, one_m_alpha = 0.f, lerp_w = 0.f;
+    bool lerp_small = false;
+    if constexpr (RULE == RULE_ADAM) {
+        // bias corrections of step s + 1
+        const double t = (double)(s + 1);
+        const double bc1 = 1.0 - pow(a.beta1, t);
+        const double bc2_sqrt = sqrt(1.0 - pow(a.beta2, t));
+        step_size = (float)(lr / bc1);
+        b2 = (float)a.beta2; one_m_b1 = (float)(1.0 - a.beta1); one_m_b2 = (float)(1.0 - a.beta2);
+        bc2s = (float)bc2_sqrt;
+        lr_wd = (float)(lr * a.weight_decay);
+    } else {
+        // SGD: buf.mul_(momentum).add_(grad, alpha=1 - dampening).  Adagrad: clr = lr / (1 + (step - 1) * lr_decay), step the
+        // post-increment count.  RMSprop: square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha), grad_avg.lerp_(grad, 1 - alpha).
+        mom = (float)a.momentum;
+        neg_lr = (float)(-lr);
+        one_m_damp = (float)(1.0 - a.dampening);
+        neg_clr = (float)(-(lr / (1.0 + (double)s * a.lr_decay)));
+        alphaf = (float)a.alpha; one_m_alpha = (float)(1.0 - a.alpha);
+        lerp_small = __builtin_fabsf(one_m_alpha) < 0.5f;
+        lerp_w = lerp_small ? one_m_alpha : one_m_alpha - 1.0f;
+    }
+    // the buffers this rule reads and writes (the others are NULL and never touched); which ones is known at compile time,
+    // except for the optional momentum buffer of SGD / RMSprop and RMSprop's grad_avg
+    float *const B = a.buf, *const Q = RULE == RULE_SGD ? nullptr : a.sq, *const GA = RULE == RULE_RMSPROP ? a.gavg : nullptr;
+    const bool has_b = RULE == RULE_ADAM || B, has_q = RULE != RULE_SGD, has_ga = GA != nullptr;
     if (!skip) {
-        // one element: returns the clipped gradient, updates p and the rule's state (b: momentum buffer, q: sum of squares,
-        // ga: RMSprop's grad_avg) in place
+        // one element: returns the clipped gradient (what clip_grad_norm_ leaves in .grad), updates p and the rule's state
+        // (b: momentum buffer | exp_avg, q: sum of squares | exp_avg_sq, ga: RMSprop's grad_avg) in place
         auto one = [&](float &p, float g0, float &b, float &q, float &ga) {
             const float gc = g0 * coef;
             float g = gc;
+            if (RULE == RULE_ADAM) {
+                if (decay) {
+                    if (a.decoupled) p -= lr_wd * p;
+                    else g += p * wd;
+                }
+                b = b + one_m_b1 * (g - b);                  // lerp(exp_avg, g, 1 - beta1)
+                q = b2 * q + one_m_b2 * g * g;
+                const float denom = __builtin_sqrtf(q) / bc2s + epsf;
+                p -= step_size * b / denom;
+                return gc;
+            }
             if (decay) g = __builtin_fmaf(wd, p, g);                      // grad.add(param, alpha=weight_decay)
             if (RULE == RULE_SGD) {
-                if (a.buf) {
+                if (has_b) {
                     b = first ? g : __builtin_fmaf(one_m_damp, g, b * mom);
                     g = a.nesterov ? __builtin_fmaf(mom, b, g) : b;      // grad.add(buf, alpha=momentum) | buf
                 }
@@ -998,7 +955,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void optim_step_kernel(OptimParams a)
                     avg = __builtin_sqrtf(q);
                 }
                 avg = avg + epsf;
-                if (a.buf) {
+                if (has_b) {
                     b = b * mom + g / avg;                               // buf.mul_(momentum).addcdiv_(grad, avg)
                     p = __builtin_fmaf(neg_lr, b, p);                    // param.add_(buf, alpha=-lr)
                 } else {
@@ -1007,39 +964,42 @@ __global__ __launch_bounds__(ADAM_THREADS) void optim_step_kernel(OptimParams a)
             }
             return gc;
         };
-        // the buffers this rule reads and writes (the others are NULL and never touched)
-        float *const B = a.buf, *const Q = RULE == RULE_SGD ? nullptr : a.sq, *const GA = RULE == RULE_RMSPROP ? a.gavg : nullptr;
+        // 16-byte accesses (the engine's flat buffers are 256-byte aligned; a caller's unaligned or ragged end goes by
+        // scalars): a quarter of the memory instructions of the dword form -- for Adam 8.9 M parameters x 8 streams were
+        // 1.1 M wave-level instructions on the address path.  The clipped gradient is written back only when clipping
+        // changed it (coef != 1).
         const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)B | (uintptr_t)Q | (uintptr_t)GA) & 15) == 0;
         const bool write_g = coef != 1.0f;
         const int64_t quads = vec ? a.count / 4 : 0;
-        for (int64_t i = (int64_t)blockIdx.x * ADAM_THREADS + threadIdx.x; i < quads; i += (int64_t)gridDim.x * ADAM_THREADS) {
+        for (int64_t i = (int64_t)blockIdx.x * OPTIM_THREADS + threadIdx.x; i < quads; i += (int64_t)gridDim.x * OPTIM_THREADS) {
             float4 p = reinterpret_cast<float4 *>(a.p)[i];
+            float4 b = has_b ? reinterpret_cast<float4 *>(B)[i] : float4{};
+            float4 q = has_q ? reinterpret_cast<float4 *>(Q)[i] : float4{};
+            float4 ga = has_ga ? reinterpret_cast<float4 *>(GA)[i] : float4{};
             const float4 g = reinterpret_cast<const float4 *>(a.g)[i];
-            float4 b = B ? reinterpret_cast<float4 *>(B)[i] : float4{};
-            float4 q = Q ? reinterpret_cast<float4 *>(Q)[i] : float4{};
-            float4 ga = GA ? reinterpret_cast<float4 *>(GA)[i] : float4{};
             float4 gc;
             gc.x = one(p.x, g.x, b.x, q.x, ga.x); gc.y = one(p.y, g.y, b.y, q.y, ga.y);
             gc.z = one(p.z, g.z, b.z, q.z, ga.z); gc.w = one(p.w, g.w, b.w, q.w, ga.w);
             if (write_g) reinterpret_cast<float4 *>(a.g)[i] = gc;
             reinterpret_cast<float4 *>(a.p)[i] = p;
-            if (B) reinterpret_cast<float4 *>(B)[i] = b;
-            if (Q) reinterpret_cast<float4 *>(Q)[i] = q;
-            if (GA) reinterpret_cast<float4 *>(GA)[i] = ga;
+            if (has_b) reinterpret_cast<float4 *>(B)[i] = b;
+            if (has_q) reinterpret_cast<float4 *>(Q)[i] = q;
+            if (has_ga) reinterpret_cast<float4 *>(GA)[i] = ga;
         }
-        for (int64_t i = quads * 4 + (int64_t)blockIdx.x * ADAM_THREADS + threadIdx.x; i < a.count; i += (int64_t)gridDim.x * ADAM_THREADS) {
-            float p = a.p[i], b = B ? B[i] : 0.f, q = Q ? Q[i] : 0.f, ga = GA ? GA[i] : 0.f;
+        for (int64_t i = quads * 4 + (int64_t)blockIdx.x * OPTIM_THREADS + threadIdx.x; i < a.count; i += (int64_t)gridDim.x * OPTIM_THREADS) {
+            float p = a.p[i], b = has_b ? B[i] : 0.f, q = has_q ? Q[i] : 0.f, ga = has_ga ? GA[i] : 0.f;
             const float gc = one(p, a.g[i], b, q, ga);
             if (write_g) a.g[i] = gc;
             a.p[i] = p;
-            if (B) B[i] = b;
-            if (Q) Q[i] = q;
-            if (GA) GA[i] = ga;
+            if (has_b) B[i] = b;
+            if (has_q) Q[i] = q;
+            if (has_ga) GA[i] = ga;
         }
         if (blockIdx.x == 0 && threadIdx.x == 0 && a.lr_out) *a.lr_out = (float)lr;
     }
     if (a.ticket) {
-        // as in adamw_step_kernel: the last workgroup, past everyone's reads of *step and *buf_ready, advances both
+        // every workgroup read *step (and *buf_ready) on entry; the one that finishes last -- after all the others have
+        // taken their tickets, i.e. are past those reads -- advances them
         __syncthreads();
         if (threadIdx.x == 0 && ticket_is_last(a.ticket, gridDim.x) && !skip) {
             *a.step = s + 1;
@@ -1436,36 +1396,41 @@ int codebook_grad(const float *count, const float *sum, const float *cb, int K, 
     return check_launch("codebook_grad_kernel");
 }
 
-int adamw_step(float *p, float *g, float *m, float *v, int64_t count, const float *clip, int64_t *step, double base_lr,
-               double beta1, double beta2, double eps, double weight_decay, int decoupled, int schedule, int64_t warmup_steps,
-               int64_t total_steps, float *lr_out, unsigned *ticket, const unsigned char *skip, hipStream_t stream)
+// The arguments every rule's entry point has, as launch parameters; the entry point adds its rule's own.
+static OptimParams optim_params(float *p, float *g, int64_t count, const float *clip, int64_t *step, double base_lr, double weight_decay,
+                                int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out, unsigned *ticket,
+                                const unsigned char *skip)
 {
-    if (!p || !g || !m || !v || !step) return fail(LCREC_EINVAL, "adamw_step: NULL pointer");
-    if (count < 1) return fail(LCREC_EINVAL, "adamw_step: empty parameter buffer");
-    if (schedule < -1 || schedule > 1) return fail(LCREC_EINVAL, "adamw_step: schedule %d (supported: -1 none, 0 constant, 1 linear)", schedule);
-    AdamParams a = {p, g, m, v, count, clip, step, base_lr, beta1, beta2, eps, weight_decay, decoupled, schedule, warmup_steps,
-                    total_steps, lr_out, ticket, skip};
-    int64_t blocks = (count + ADAM_THREADS * 8 - 1) / (ADAM_THREADS * 8);
-    if (blocks > TICKET_MAX_WORKGROUPS) blocks = TICKET_MAX_WORKGROUPS;
-    TraceScope trace(K_ADAMW, stream);
-    hipLaunchKernelGGL(adamw_step_kernel, dim3((unsigned)blocks), dim3(ADAM_THREADS), 0, stream, a);
-    if (!ticket) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, stream, step, skip);
-    return check_launch("adamw_step_kernel");
+    OptimParams a = {};
+    a.p = p; a.g = g; a.count = count; a.clip = clip; a.step = step; a.base_lr = base_lr; a.weight_decay = weight_decay;
+    a.schedule = schedule; a.warmup_steps = warmup_steps; a.total_steps = total_steps; a.lr_out = lr_out; a.ticket = ticket; a.skip = skip;
+    return a;
 }
 
+// `what`: the entry point, for error texts; `label`: its trace label (K_ADAMW | K_OPTIM_STEP)
 template <int RULE>
-static int launch_optim_step(const OptimParams &a, const char *what, hipStream_t stream)
+static int launch_optim_step(const OptimParams &a, const char *what, int label, hipStream_t stream)
 {
     if (!a.p || !a.g || !a.step) return fail(LCREC_EINVAL, "%s: NULL pointer", what);
     if (a.count < 1) return fail(LCREC_EINVAL, "%s: empty parameter buffer", what);
     if (a.schedule < -1 || a.schedule > 1) return fail(LCREC_EINVAL, "%s: schedule %d (supported: -1 none, 0 constant, 1 linear)", what, a.schedule);
     if (!(a.base_lr >= 0.0) || !(a.weight_decay >= 0.0)) return fail(LCREC_EINVAL, "%s: lr and weight_decay must be >= 0", what);
-    int64_t blocks = (a.count + ADAM_THREADS * 8 - 1) / (ADAM_THREADS * 8);
+    int64_t blocks = (a.count + OPTIM_THREADS * 8 - 1) / (OPTIM_THREADS * 8);
     if (blocks > TICKET_MAX_WORKGROUPS) blocks = TICKET_MAX_WORKGROUPS;
-    TraceScope trace(K_OPTIM_STEP, stream);
-    hipLaunchKernelGGL(optim_step_kernel<RULE>, dim3((unsigned)blocks), dim3(ADAM_THREADS), 0, stream, a);
+    TraceScope trace(label, stream);
+    hipLaunchKernelGGL(optim_step_kernel<RULE>, dim3((unsigned)blocks), dim3(OPTIM_THREADS), 0, stream, a);
     if (!a.ticket) hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(1), 0, stream, a.step, a.buf_ready, a.skip);
     return check_launch(what);
+}
+
+int adamw_step(float *p, float *g, float *m, float *v, int64_t count, const float *clip, int64_t *step, double base_lr,
+               double beta1, double beta2, double eps, double weight_decay, int decoupled, int schedule, int64_t warmup_steps,
+               int64_t total_steps, float *lr_out, unsigned *ticket, const unsigned char *skip, hipStream_t stream)
+{
+    if (!m || !v) return fail(LCREC_EINVAL, "adamw_step: NULL pointer");
+    OptimParams a = optim_params(p, g, count, clip, step, base_lr, weight_decay, schedule, warmup_steps, total_steps, lr_out, ticket, skip);
+    a.buf = m; a.sq = v; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.decoupled = decoupled;
+    return launch_optim_step<RULE_ADAM>(a, "adamw_step", K_ADAMW, stream);
 }
 
 int sgd_step(float *p, float *g, float *buf, unsigned char *buf_ready, int64_t count, const float *clip, int64_t *step, double base_lr,
@@ -1478,11 +1443,9 @@ int sgd_step(float *p, float *g, float *buf, unsigned char *buf_ready, int64_t c
     if (momentum == 0.0 && (buf || buf_ready)) return fail(LCREC_EINVAL, "sgd_step: momentum_buffer given with momentum 0");
     if (nesterov && (momentum <= 0.0 || dampening != 0.0))
         return fail(LCREC_EINVAL, "sgd_step: nesterov momentum requires a momentum and zero dampening");
-    OptimParams a = {};
-    a.p = p; a.g = g; a.buf = buf; a.buf_ready = buf_ready; a.count = count; a.clip = clip; a.step = step;
-    a.base_lr = base_lr; a.weight_decay = weight_decay; a.momentum = momentum; a.dampening = dampening; a.nesterov = nesterov != 0;
-    a.schedule = schedule; a.warmup_steps = warmup_steps; a.total_steps = total_steps; a.lr_out = lr_out; a.ticket = ticket; a.skip = skip;
-    return launch_optim_step<RULE_SGD>(a, "sgd_step", stream);
+    OptimParams a = optim_params(p, g, count, clip, step, base_lr, weight_decay, schedule, warmup_steps, total_steps, lr_out, ticket, skip);
+    a.buf = buf; a.buf_ready = buf_ready; a.momentum = momentum; a.dampening = dampening; a.nesterov = nesterov != 0;
+    return launch_optim_step<RULE_SGD>(a, "sgd_step", K_OPTIM_STEP, stream);
 }
 
 int adagrad_step(float *p, float *g, float *state_sum, int64_t count, const float *clip, int64_t *step, double base_lr, double lr_decay,
@@ -1491,11 +1454,9 @@ int adagrad_step(float *p, float *g, float *state_sum, int64_t count, const floa
 {
     if (!state_sum) return fail(LCREC_EINVAL, "adagrad_step: NULL pointer");
     if (!(lr_decay >= 0.0) || !(eps >= 0.0)) return fail(LCREC_EINVAL, "adagrad_step: lr_decay and eps must be >= 0");
-    OptimParams a = {};
-    a.p = p; a.g = g; a.sq = state_sum; a.count = count; a.clip = clip; a.step = step;
-    a.base_lr = base_lr; a.weight_decay = weight_decay; a.lr_decay = lr_decay; a.eps = eps;
-    a.schedule = schedule; a.warmup_steps = warmup_steps; a.total_steps = total_steps; a.lr_out = lr_out; a.ticket = ticket; a.skip = skip;
-    return launch_optim_step<RULE_ADAGRAD>(a, "adagrad_step", stream);
+    OptimParams a = optim_params(p, g, count, clip, step, base_lr, weight_decay, schedule, warmup_steps, total_steps, lr_out, ticket, skip);
+    a.sq = state_sum; a.lr_decay = lr_decay; a.eps = eps;
+    return launch_optim_step<RULE_ADAGRAD>(a, "adagrad_step", K_OPTIM_STEP, stream);
 }
 
 int rmsprop_step(float *p, float *g, float *square_avg, float *buf, float *grad_avg, int64_t count, const float *clip, int64_t *step,
@@ -1508,11 +1469,9 @@ int rmsprop_step(float *p, float *g, float *square_avg, float *buf, float *grad_
         return fail(LCREC_EINVAL, "rmsprop_step: momentum_buffer must be given exactly when momentum > 0");
     if ((centered != 0) != (grad_avg != nullptr))
         return fail(LCREC_EINVAL, "rmsprop_step: grad_avg must be given exactly when centered");
-    OptimParams a = {};
-    a.p = p; a.g = g; a.sq = square_avg; a.buf = buf; a.gavg = grad_avg; a.count = count; a.clip = clip; a.step = step;
-    a.base_lr = base_lr; a.weight_decay = weight_decay; a.alpha = alpha; a.eps = eps; a.momentum = momentum; a.centered = centered != 0;
-    a.schedule = schedule; a.warmup_steps = warmup_steps; a.total_steps = total_steps; a.lr_out = lr_out; a.ticket = ticket; a.skip = skip;
-    return launch_optim_step<RULE_RMSPROP>(a, "rmsprop_step", stream);
+    OptimParams a = optim_params(p, g, count, clip, step, base_lr, weight_decay, schedule, warmup_steps, total_steps, lr_out, ticket, skip);
+    a.sq = square_avg; a.buf = buf; a.gavg = grad_avg; a.alpha = alpha; a.eps = eps; a.momentum = momentum; a.centered = centered != 0;
+    return launch_optim_step<RULE_RMSPROP>(a, "rmsprop_step", K_OPTIM_STEP, stream);
 }
 
 }  // namespace lcrec

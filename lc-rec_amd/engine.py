@@ -16,14 +16,14 @@ the same lcrec_* entry points the module API uses, so forward values and GEMM gr
                                                                        lcrec_linear_backward (dX), and ONE grouped launch
                                                                        for all weight gradients, written straight into the
                                                                        flat gradient buffer (lcrec_linear_backward_weights)
-    clip 1.0 + optimiser + warm-up schedule                            lcrec_grad_norm_clip, lcrec_adamw_step (Adam/AdamW) or
-                                                                       lcrec_{sgd,adagrad,rmsprop}_step (learning rate and
-                                                                       bias corrections from a device step counter)
+    clip 1.0 + optimiser + warm-up schedule                            lcrec_grad_norm_clip, lcrec_{adamw,sgd,adagrad,rmsprop}_step
+                                                                       (one kernel, four rules; learning rate and bias
+                                                                       corrections from a device step counter)
     loss sums, NaN flag                                                device accumulators, read once per epoch
 
 and captures it with torch.cuda.CUDAGraph (a hipGraph) once per batch size: a step is then one index_select, one copy
-and one graph launch on the host.  Parameters, gradients and the optimiser's state (both Adam moments; SGD's momentum
-buffer; Adagrad's sum; RMSprop's square_avg, momentum_buffer, grad_avg -- only those the rule keeps) live in flat fp32
+and one graph launch on the host.  Parameters, gradients and the optimiser's state (Adam's exp_avg and exp_avg_sq; SGD's
+momentum buffer; Adagrad's sum; RMSprop's square_avg, momentum_buffer, grad_avg -- only those the rule keeps) live in flat fp32
 buffers; the module's nn.Parameters (and the torch optimizer's state entries, under torch's own keys, so checkpoints keep
 the reference's layout) are views into them.
 
@@ -55,9 +55,18 @@ _ALIGN = 64     # floats: every parameter starts on a 256-byte boundary of the f
 # rule; LCREC_DW_SPLITS, tuning)
 DW_SPLITS = int(os.environ.get("LCREC_DW_SPLITS", "1"))
 
-# the hyper-parameters (torch's param_group keys) each of the other rules' kernels reads
-_HYPER = {"sgd": ("momentum", "dampening", "nesterov"), "adagrad": ("lr_decay", "eps", "initial_accumulator_value"),
-          "rmsprop": ("alpha", "eps", "momentum", "centered")}
+# The rules.  The hyper-parameters (torch's param_group keys) each rule's kernel reads ...
+_HYPER = {"adam": ("betas", "eps"), "sgd": ("momentum", "dampening", "nesterov"),
+          "adagrad": ("lr_decay", "eps", "initial_accumulator_value"), "rmsprop": ("alpha", "eps", "momentum", "centered")}
+# ... torch's state keys of the flat buffers it keeps, in torch's order: only what the rule needs (plain SGD: nothing) ...
+_STATE = {"adam": lambda h: ["exp_avg", "exp_avg_sq"],
+          "sgd": lambda h: ["momentum_buffer"] if h["momentum"] != 0 else [],
+          "adagrad": lambda h: ["sum"],
+          "rmsprop": lambda h: ["square_avg"] + (["momentum_buffer"] if h["momentum"] > 0 else []) + (["grad_avg"] if h["centered"] else [])}
+# ... and torch's float32 `step` entry.  "shared": one scalar on the engine's device for all parameters, exposed with the
+# moments when the engine is built; "each": an element per parameter of a buffer on the host, as torch keeps it, unless it
+# already lives elsewhere or the optimizer is capturable, exposed when torch itself would have state; None: SGD has none.
+_STEP = {"adam": "shared", "sgd": None, "adagrad": "each", "rmsprop": "each"}
 
 
 def _rule(optimizer):
@@ -102,12 +111,7 @@ class TrainEngine:
         self.rule = _rule(optimizer)
         self.base_lr = float(group.get("initial_lr", group["lr"]))
         self.weight_decay = float(group["weight_decay"])
-        if self.rule == "adam":
-            self.betas = tuple(group["betas"])
-            self.eps = float(group["eps"])
-            self.decoupled = isinstance(optimizer, torch.optim.AdamW)
-        else:
-            self.hyper = {k: group[k] for k in _HYPER[self.rule]}
+        self.hyper = {k: group[k] for k in _HYPER[self.rule]}
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         self.device = self.params[0].device
         self._prior_steps = 0
@@ -183,27 +187,13 @@ class TrainEngine:
         dev = self.device
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        if self.rule == "adam":
-            self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
-            self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
-            self._step_f32 = torch.zeros((), dtype=torch.float32, device=dev)
-            self._exposed = True
-        else:
-            h = self.hyper
-            if self.rule == "sgd":
-                keys = ["momentum_buffer"] if h["momentum"] != 0 else []
-            elif self.rule == "adagrad":
-                keys = ["sum"]
-            else:
-                keys = ["square_avg"] + (["momentum_buffer"] if h["momentum"] > 0 else []) + (["grad_avg"] if h["centered"] else [])
-            # torch's state keys -> flat buffers: only what the rule keeps (plain SGD: nothing)
-            self.flat_state = {k: torch.zeros(total, dtype=torch.float32, device=dev) for k in keys}
-            # SGD's first step sets buf = g: whether the buffer holds a value is a device byte of its own (set by the kernel)
-            self._buf_ready = torch.zeros((), dtype=torch.uint8, device=dev) if self.rule == "sgd" and self.flat_state else None
-            self._steps_f32 = None
-            self._state_views = []
-            self._exposed = False
-            held, step_dev = False, None
+        # torch's state keys -> flat buffers
+        self.flat_state = {k: torch.zeros(total, dtype=torch.float32, device=dev) for k in _STATE[self.rule](self.hyper)}
+        # SGD's first step sets buf = g: whether the buffer holds a value is a device byte of its own (set by the kernel)
+        self._buf_ready = torch.zeros((), dtype=torch.uint8, device=dev) if self.rule == "sgd" and self.flat_state else None
+        self._state_views = []
+        self._exposed = False
+        held, step_dev = False, None
         self.grad_view = {}
         # spans of the flat buffers for the data-parallel gradient exchange: the decoder's parameters (contiguous in
         # parameter order) and whatever lies before / after them
@@ -224,48 +214,42 @@ class TrainEngine:
                 p.data = view(self.flat_p)
                 p.grad = view(self.flat_g)
                 self.grad_view[p] = p.grad
-                if self.rule != "adam":
-                    state = self.optimizer.state.get(p, {})         # (.get: plain SGD keeps no per-parameter state at all)
-                    for k, flat in self.flat_state.items():
-                        if k in state:                               # the autograd path has been here before the engine
-                            view(flat).copy_(state[k])
-                            held = True
-                        elif k == "sum":
-                            view(flat).fill_(float(self.hyper["initial_accumulator_value"]))
-                    if torch.is_tensor(state.get("step")):
-                        self._prior_steps = int(float(state["step"]))
-                        step_dev = state["step"].device
-                    self._state_views.append({k: view(flat) for k, flat in self.flat_state.items()})
-                    continue
-                state = self.optimizer.state[p]
-                if "exp_avg" in state:                                   # steps were taken before the engine took over
-                    view(self.flat_m).copy_(state["exp_avg"])
-                    view(self.flat_v).copy_(state["exp_avg_sq"])
+                state = self.optimizer.state.get(p, {})             # (.get: plain SGD keeps no per-parameter state at all)
+                for k, flat in self.flat_state.items():
+                    if k in state:                                   # the autograd path has been here before the engine
+                        view(flat).copy_(state[k])
+                        held = True
+                    elif k == "sum":
+                        view(flat).fill_(float(self.hyper["initial_accumulator_value"]))
+                if "step" in state:
                     self._prior_steps = int(float(state["step"]))
-                state["step"] = self._step_f32
-                state["exp_avg"] = view(self.flat_m)
-                state["exp_avg_sq"] = view(self.flat_v)
-        if self.rule in ("adagrad", "rmsprop"):
-            # torch keeps a float32 `step` per parameter (Adagrad's clr reads it): one element each of a buffer that
-            # sync_host_state fills -- on the host, as torch keeps it, unless it already lives elsewhere or is capturable
+                    step_dev = state["step"].device if torch.is_tensor(state["step"]) else None
+                self._state_views.append({k: view(flat) for k, flat in self.flat_state.items()})
+        # the `step` entries (Adagrad's clr reads torch's): one buffer that sync_host_state fills
+        kind = _STEP[self.rule]
+        self._steps_f32 = None
+        if kind == "shared":
+            self._steps_f32 = torch.zeros((), dtype=torch.float32, device=dev)
+        elif kind == "each":
             if step_dev is None:
                 step_dev = dev if self.optimizer.param_groups[0].get("capturable") else torch.device("cpu")
             self._steps_f32 = torch.zeros(len(self.params), dtype=torch.float32, device=step_dev)
-        if self.rule != "adam" and held:
-            if self._buf_ready is not None:
-                self._buf_ready.fill_(1)
+        if held and self._buf_ready is not None:
+            self._buf_ready.fill_(1)
+        if held or kind == "shared":
             self._expose_state()
 
     def _expose_state(self):
-        """The optimizer's state entries of the rules other than Adam become views of the flat buffers, under torch's keys and
-        in its order -- when torch itself would have them: at construction for Adagrad, after the first step otherwise."""
+        """The optimizer's state entries become views of the flat buffers, under torch's keys and in its order -- Adam's when
+        the engine is built, the others' when torch itself would have them: at construction for Adagrad, after the first
+        step otherwise."""
         self._exposed = True
         for i, (p, views) in enumerate(zip(self.params, self._state_views)):
             if not views and self._steps_f32 is None:
                 continue                                             # plain SGD: the state stays empty
             state = self.optimizer.state[p]
             if self._steps_f32 is not None:
-                state["step"] = self._steps_f32[i]
+                state["step"] = self._steps_f32[i] if self._steps_f32.dim() else self._steps_f32
             state.update(views)
 
     # ------------------------------------------------------------------ the step, as library calls
@@ -434,17 +418,12 @@ class TrainEngine:
                 ops.ema_update(lvl._ema_cluster_size, lvl._ema_w, lvl.embedding.weight.data, stats[t][0], stats[t][1],
                                lvl.ema_decay, lvl.epsilon, skip_flag=self.bad[0])
         ops.grad_norm_clip(self.flat_g, self.max_norm, out=self.clip)
-        if self.rule == "adam":
-            ops.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.step_count, self.base_lr, self.betas, self.eps,
-                           self.weight_decay, self.decoupled, clip=self.clip, schedule=self.schedule,
-                           warmup_steps=self.warmup_steps, total_steps=self.total_steps, lr_out=self.lr_used,
-                           skip_flag=self.bad[0])        # a NaN loss (sticky) leaves parameters, moments and step at the last good step
-        else:
-            self._update()
+        self._update()
 
     def _update(self):
-        """The update of SGD / Adagrad / RMSprop, with everything around it as for Adam: clipped gradient, device step counter
-        and schedule, the learning rate used, and the NaN flag that freezes parameters, state and counter."""
+        """The optimiser's update, for every rule with the same things around it: clipped gradient, device step counter and
+        schedule, the learning rate used, and the NaN flag (sticky) that leaves parameters, state and counter at the last
+        good step."""
         h, st = self.hyper, self.flat_state
         common = dict(clip=self.clip, schedule=self.schedule, warmup_steps=self.warmup_steps, total_steps=self.total_steps,
                       lr_out=self.lr_used, skip_flag=self.bad[0])
@@ -454,10 +433,13 @@ class TrainEngine:
         elif self.rule == "adagrad":
             ops.adagrad_step(self.flat_p, self.flat_g, st["sum"], self.step_count, self.base_lr, h["lr_decay"], h["eps"],
                              self.weight_decay, **common)
-        else:
+        elif self.rule == "rmsprop":
             ops.rmsprop_step(self.flat_p, self.flat_g, st["square_avg"], self.step_count, self.base_lr, h["alpha"], h["eps"],
                              self.weight_decay, h["momentum"], h["centered"], momentum_buffer=st.get("momentum_buffer"),
                              grad_avg=st.get("grad_avg"), **common)
+        else:                                                                # Adam, or AdamW: decoupled weight decay
+            ops.adamw_step(self.flat_p, self.flat_g, st["exp_avg"], st["exp_avg_sq"], self.step_count, self.base_lr, h["betas"],
+                           h["eps"], self.weight_decay, isinstance(self.optimizer, torch.optim.AdamW), **common)
 
     # ------------------------------------------------------------------ driving it
     def step_selected(self, data, index):
@@ -576,9 +558,7 @@ class TrainEngine:
     def sync_host_state(self, scheduler=None):
         """Make what the host can see agree with the device: the optimizer's per-parameter `step` entries (checkpoints; Adam,
         Adagrad, RMSprop) and the LambdaLR scheduler's counters and `lr` (logging, get_last_lr)."""
-        if self.rule == "adam":
-            self._step_f32.fill_(float(self.host_steps))
-        elif self._steps_f32 is not None:
+        if self._steps_f32 is not None:
             self._steps_f32.fill_(float(self.host_steps))
         if self._bn_pending and self._bn_counters:
             torch._foreach_add_(self._bn_counters, self._bn_pending)

@@ -895,24 +895,6 @@ def quantizer_input_grad(z, codebook0, idx_col, coef, weight, g_xq, dbias_out=No
     return out
 
 
-def adamw_step(params, grads, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True,
-               clip=None, schedule=-1, warmup_steps=0, total_steps=0, lr_out=None, skip_flag=None):
-    """One AdamW/Adam step on flat fp32 buffers, all updated in place (see lcrec_adamw_step); `step` is a device int64
-    scalar the call increments.  skip_flag: a device bool/uint8 scalar; when set nothing is updated."""
-    lib = _lib.load()
-    for name, t in (("params", params), ("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == params.numel()):
-            raise _lib.LcrecError(f"{name} must be a contiguous float32 device buffer of {params.numel()} elements")
-    if not (step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
-        raise _lib.LcrecError("step must be a device int64 scalar")
-    with _on(params.device):
-        rc = lib.lcrec_adamw_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), params.numel(), _ptr(clip),
-                                  _ptr(step), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                                  int(bool(decoupled)), int(schedule), int(warmup_steps), int(total_steps), _ptr(lr_out),
-                                  _ptr(_ticket(params.device)), _ptr(skip_flag), _stream_ptr())
-    _lib.check(rc, "lcrec_adamw_step")
-
-
 def _flat_check(params, **bufs):
     for name, t in (("params", params),) + tuple(bufs.items()):
         if t is None:
@@ -926,35 +908,46 @@ def _step_check(step):
         raise _lib.LcrecError("step must be a device int64 scalar")
 
 
+def _optim_step(entry, params, grads, state, extra, step, lr, hyper, clip, schedule, warmup_steps, total_steps, lr_out, skip_flag):
+    """What the four optimiser entry points of include/lcrec.h share: (params, grads, the rule's state buffers `state`
+    {name: flat buffer | None} and further pointers `extra`, count, clip, step, lr, the rule's hyper-parameters `hyper`,
+    schedule, warmup_steps, total_steps, lr_out, ticket, skip_flag, stream)."""
+    lib = _lib.load()
+    _flat_check(params, grads=grads, **state)
+    _step_check(step)
+    with _on(params.device):
+        rc = getattr(lib, entry)(_ptr(params), _ptr(grads), *[_ptr(t) for t in (*state.values(), *extra)], params.numel(),
+                                 _ptr(clip), _ptr(step), float(lr), *hyper, int(schedule), int(warmup_steps), int(total_steps),
+                                 _ptr(lr_out), _ptr(_ticket(params.device)), _ptr(skip_flag), _stream_ptr())
+    _lib.check(rc, entry)
+
+
+def adamw_step(params, grads, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True,
+               clip=None, schedule=-1, warmup_steps=0, total_steps=0, lr_out=None, skip_flag=None):
+    """One AdamW/Adam step on flat fp32 buffers, all updated in place (see lcrec_adamw_step); `step` is a device int64
+    scalar the call increments.  skip_flag: a device bool/uint8 scalar; when set nothing is updated."""
+    _optim_step("lcrec_adamw_step", params, grads, dict(exp_avg=exp_avg, exp_avg_sq=exp_avg_sq), (), step, lr,
+                (float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled))),
+                clip, schedule, warmup_steps, total_steps, lr_out, skip_flag)
+
+
 def sgd_step(params, grads, step, lr, momentum=0.0, dampening=0.0, nesterov=False, weight_decay=0.0, momentum_buffer=None,
              momentum_ready=None, clip=None, schedule=-1, warmup_steps=0, total_steps=0, lr_out=None, skip_flag=None):
     """One torch.optim.SGD step on flat fp32 buffers, updated in place (see lcrec_sgd_step).  With momentum != 0:
     momentum_buffer (flat fp32) and momentum_ready (a device bool/uint8 scalar, False until the buffer holds a value --
     torch's first step sets buf = g -- and set by the call)."""
-    lib = _lib.load()
-    _flat_check(params, grads=grads, momentum_buffer=momentum_buffer)
-    _step_check(step)
     if momentum_ready is not None and not (momentum_ready.is_cuda and momentum_ready.element_size() == 1 and momentum_ready.numel() == 1):
         raise _lib.LcrecError("momentum_ready must be a device bool/uint8 scalar")
-    with _on(params.device):
-        rc = lib.lcrec_sgd_step(_ptr(params), _ptr(grads), _ptr(momentum_buffer), _ptr(momentum_ready), params.numel(), _ptr(clip),
-                                _ptr(step), float(lr), float(momentum), float(dampening), int(bool(nesterov)), float(weight_decay),
-                                int(schedule), int(warmup_steps), int(total_steps), _ptr(lr_out), _ptr(_ticket(params.device)),
-                                _ptr(skip_flag), _stream_ptr())
-    _lib.check(rc, "lcrec_sgd_step")
+    _optim_step("lcrec_sgd_step", params, grads, dict(momentum_buffer=momentum_buffer), (momentum_ready,), step, lr,
+                (float(momentum), float(dampening), int(bool(nesterov)), float(weight_decay)),
+                clip, schedule, warmup_steps, total_steps, lr_out, skip_flag)
 
 
 def adagrad_step(params, grads, state_sum, step, lr, lr_decay=0.0, eps=1e-10, weight_decay=0.0, clip=None, schedule=-1,
                  warmup_steps=0, total_steps=0, lr_out=None, skip_flag=None):
     """One torch.optim.Adagrad step on flat fp32 buffers, updated in place (see lcrec_adagrad_step)."""
-    lib = _lib.load()
-    _flat_check(params, grads=grads, state_sum=state_sum)
-    _step_check(step)
-    with _on(params.device):
-        rc = lib.lcrec_adagrad_step(_ptr(params), _ptr(grads), _ptr(state_sum), params.numel(), _ptr(clip), _ptr(step), float(lr),
-                                    float(lr_decay), float(eps), float(weight_decay), int(schedule), int(warmup_steps),
-                                    int(total_steps), _ptr(lr_out), _ptr(_ticket(params.device)), _ptr(skip_flag), _stream_ptr())
-    _lib.check(rc, "lcrec_adagrad_step")
+    _optim_step("lcrec_adagrad_step", params, grads, dict(state_sum=state_sum), (), step, lr,
+                (float(lr_decay), float(eps), float(weight_decay)), clip, schedule, warmup_steps, total_steps, lr_out, skip_flag)
 
 
 def rmsprop_step(params, grads, square_avg, step, lr, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False,
@@ -962,15 +955,9 @@ def rmsprop_step(params, grads, square_avg, step, lr, alpha=0.99, eps=1e-8, weig
                  skip_flag=None):
     """One torch.optim.RMSprop step on flat fp32 buffers, updated in place (see lcrec_rmsprop_step); momentum_buffer
     exactly when momentum > 0, grad_avg exactly when centered."""
-    lib = _lib.load()
-    _flat_check(params, grads=grads, square_avg=square_avg, momentum_buffer=momentum_buffer, grad_avg=grad_avg)
-    _step_check(step)
-    with _on(params.device):
-        rc = lib.lcrec_rmsprop_step(_ptr(params), _ptr(grads), _ptr(square_avg), _ptr(momentum_buffer), _ptr(grad_avg),
-                                    params.numel(), _ptr(clip), _ptr(step), float(lr), float(alpha), float(eps), float(weight_decay),
-                                    float(momentum), int(bool(centered)), int(schedule), int(warmup_steps), int(total_steps),
-                                    _ptr(lr_out), _ptr(_ticket(params.device)), _ptr(skip_flag), _stream_ptr())
-    _lib.check(rc, "lcrec_rmsprop_step")
+    _optim_step("lcrec_rmsprop_step", params, grads, dict(square_avg=square_avg, momentum_buffer=momentum_buffer, grad_avg=grad_avg),
+                (), step, lr, (float(alpha), float(eps), float(weight_decay), float(momentum), int(bool(centered))),
+                clip, schedule, warmup_steps, total_steps, lr_out, skip_flag)
 
 
 def trace_enable(on=True):

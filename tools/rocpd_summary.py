@@ -16,7 +16,9 @@ import sqlite3
 import sys
 
 NAMES = [("bn_relu_backward_kernel", "bn_relu_backward"), ("bn_relu_forward_kernel", "bn_relu_forward"),
-         ("sk_persistent_kernel", "sinkhorn"), ("adamw_step_kernel", "adamw_step"),
+         ("sk_persistent_kernel", "sinkhorn"),
+         # the Adam instantiation of the optimiser kernel (RULE_ADAM = 3 in csrc/train_ops.hip), demangled or not
+         ("optim_step_kernel<3>", "adamw_step"), ("optim_step_kernelILi3E", "adamw_step"),
          ("linear_fwd_pp3_kernel", "linear_fwd_pp_256x128"), ("linear_fwd_pp2_kernel", "linear_fwd_pp_256x128"), ("linear_fwd_pp_kernel", "linear_fwd_pp_256x128"),
          ("linear_fwd_kernel<2, 2, 2, 2", "linear_fwd_128x128"), ("linear_fwd_kernel<2, 2, 1, 1", "linear_fwd_64x64"),
          ("linear_fwd_kernel<4, 1, 1, 2", "linear_fwd_128x64"), ("linear_fwd_kernel<4, 1, 1, 1", "linear_fwd_128x32"),

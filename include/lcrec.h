@@ -484,6 +484,30 @@ int lcrec_rmsprop_step(float *params, float *grads, float *square_avg, float *mo
                        double momentum, int centered, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
                        unsigned int *ticket, const unsigned char *skip_flag, void *stream);
 
+/* Dropout masks (nn.Dropout in front of every Linear, index/models/layers.py:17; --dropout_prob of index/main.py).
+ * The mask is a FUNCTION of (seed, step, position, element), not a stream of draws, so a captured training step needs no
+ * generator state and a test can recompute any mask on the host:
+ *   generator  Philox4x32-10 with the standard constants: multipliers 0xD2511F53 and 0xCD9E8D57, Weyl increments
+ *              0x9E3779B9 and 0xBB67AE85, 10 rounds
+ *   key        (seed low 32 bits, seed high 32 bits)
+ *   counter    (q low 32, q high 32, position, (uint32) step), q = flat element index / 4; the four output words belong
+ *              to elements 4q .. 4q+3; flat element index = (row_offset + row) * features + col
+ *   keep rule  an element is kept iff its word u >= T, T = min(2^32 - 1, floor(p * 2^32)) computed by the caller in double;
+ *              kept value = x * s with s = (float)(1.0 / (1.0 - (double)p)) -- one fp32 multiply; dropped value = +0.0f
+ * 0 <= p < 1: lcrec_dropout_apply returns LCREC_EINVAL for an s that no such p gives (not finite, below 1, NaN).
+ * seed, step: device int64 scalars, read by the kernel -- a replayed hipGraph draws a new mask every step because the
+ * optimiser entry points above advance *step, with no new kernel argument.  position: which Dropout module (>= 0).
+ * row_offset: global row of this call's row 0 (a rank's shard of a data-parallel batch; 0 otherwise).  features: a positive
+ * multiple of 4.  n rows; [n][features] row-major.
+ *
+ * lcrec_dropout_apply: out = mask * in * s; out may alias in; both 16-byte aligned.  Forward and backward are the same call
+ * (the gradient of the dropped tensor's source is g * mask * s).
+ * lcrec_dropout_mask: keep_out[n][features] (uint8, 4-byte aligned) = 1 where the element is kept, else 0. */
+int lcrec_dropout_apply(const float *in, float *out, int64_t n, int features, uint32_t T, float s, const int64_t *seed,
+                        const int64_t *step, int position, int64_t row_offset, void *stream);
+int lcrec_dropout_mask(unsigned char *keep_out, int64_t n, int features, uint32_t T, const int64_t *seed, const int64_t *step,
+                       int position, int64_t row_offset, void *stream);
+
 /* Which items share an identical index tuple.  Replaces the Python string-set / dict passes of
  * index/trainer.py:139-150 (collision rate) and index/generate_indices.py:18-42
  * (check_collision, get_indices_count, get_collision_item), keeping get_collision_item's order:

@@ -28,7 +28,7 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "collision_groups", "linear_fwd_pp_256x128", "linear_fwd_64x64", "sinkhorn_slab",
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
-                                           "optim_step"};
+                                           "optim_step", "dropout"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -461,6 +461,18 @@ LCREC_API int lcrec_rmsprop_step(float *params, float *grads, float *square_avg,
 {
     return rmsprop_step(params, grads, square_avg, momentum_buffer, grad_avg, count, clip, step, base_lr, alpha, eps, weight_decay,
                         momentum, centered, schedule, warmup_steps, total_steps, lr_out, ticket, skip_flag, (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_dropout_apply(const float *in, float *out, int64_t n, int features, uint32_t T, float s, const int64_t *seed,
+                                  const int64_t *step, int position, int64_t row_offset, void *stream)
+{
+    return dropout_apply(in, out, n, features, T, s, seed, step, position, row_offset, (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_dropout_mask(unsigned char *keep_out, int64_t n, int features, uint32_t T, const int64_t *seed, const int64_t *step,
+                                 int position, int64_t row_offset, void *stream)
+{
+    return dropout_mask(keep_out, n, features, T, seed, step, position, row_offset, (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_codebook_grad(const float *count, const float *sum, const float *codebook, int K, int e, float scale,

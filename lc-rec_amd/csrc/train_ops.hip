@@ -1109,6 +1109,59 @@ __global__ __launch_bounds__(256) void codebook_grad_kernel(const float *__restr
     grad[i] = (scale * t) * weight;
 }
 
+// ---------------------------------------------------------------- dropout (include/lcrec.h, "Dropout masks")
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants).  One call yields the four words of elements 4q .. 4q+3.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t out[4])
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+constexpr int DROP_THREADS = 256;
+constexpr int DROP_BLOCKS_PER_CU = 4;   // 16 waves per CU: loads enough in flight for a stream whose ALU work (40 multiplies) is hidden
+
+// MASK_ONLY: keep_out[4q .. 4q+3] = [word >= T]; else out = keep ? in * s : +0 (out may be in).  quads = n * features / 4,
+// q0 = row_offset * features / 4: the launch's first counter.  seed and step are read here, from device memory, so a replayed
+// graph sees the values of the step it runs in.
+template <bool MASK_ONLY>
+__global__ __launch_bounds__(DROP_THREADS) void dropout_kernel(const float *in, float *out, unsigned char *keep_out, int64_t quads,
+                                                               uint64_t q0, uint32_t T, float s, const int64_t *__restrict__ seed,
+                                                               const int64_t *__restrict__ step, uint32_t position)
+{
+    const uint64_t key = (uint64_t)*seed;
+    const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32), c3 = (uint32_t)(uint64_t)*step;
+    const int64_t stride = (int64_t)gridDim.x * DROP_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * DROP_THREADS + threadIdx.x; i < quads; i += stride) {
+        const uint64_t q = q0 + (uint64_t)i;
+        uint32_t w[4];
+        philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), position, c3, k0, k1, w);
+        if (MASK_ONLY) {
+            uchar4 m;
+            m.x = w[0] >= T; m.y = w[1] >= T; m.z = w[2] >= T; m.w = w[3] >= T;
+            reinterpret_cast<uchar4 *>(keep_out)[i] = m;
+        } else {
+            const f32x4 x = reinterpret_cast<const f32x4 *>(in)[i];
+            f32x4 y;
+            y.x = w[0] >= T ? x.x * s : 0.0f;
+            y.y = w[1] >= T ? x.y * s : 0.0f;
+            y.z = w[2] >= T ? x.z * s : 0.0f;
+            y.w = w[3] >= T ? x.w * s : 0.0f;
+            reinterpret_cast<f32x4 *>(out)[i] = y;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- host side
 
 // strip width by feature count: wide layers read 128-byte row segments; narrow ones take narrower strips so that more
@@ -1472,6 +1525,59 @@ int rmsprop_step(float *p, float *g, float *square_avg, float *buf, float *grad_
     OptimParams a = optim_params(p, g, count, clip, step, base_lr, weight_decay, schedule, warmup_steps, total_steps, lr_out, ticket, skip);
     a.sq = square_avg; a.buf = buf; a.gavg = grad_avg; a.alpha = alpha; a.eps = eps; a.momentum = momentum; a.centered = centered != 0;
     return launch_optim_step<RULE_RMSPROP>(a, "rmsprop_step", K_OPTIM_STEP, stream);
+}
+
+// grid of the dropout kernels: from the device's CU count (a batch's widest activation is 2 M elements = 2 k workgroups of
+// one access each; 4 per CU make the same passes with fewer workgroups to dispatch), never more than the work
+static int dropout_grid(int64_t quads)
+{
+    static const int cus = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = 256;
+        return v;
+    }();
+    const int64_t need = (quads + DROP_THREADS - 1) / DROP_THREADS;
+    const int64_t cap = (int64_t)cus * DROP_BLOCKS_PER_CU;
+    return (int)(need < cap ? need : cap);
+}
+
+static int dropout_check(const char *what, int64_t n, int F, const int64_t *seed, const int64_t *step, int position, int64_t row_offset)
+{
+    if (!seed || !step) return fail(LCREC_EINVAL, "%s: NULL pointer", what);
+    if (n < 0 || F < 4 || F % 4) return fail(LCREC_EINVAL, "%s: features %d (a positive multiple of 4) and n %lld (>= 0)", what, F, (long long)n);
+    if (position < 0 || row_offset < 0) return fail(LCREC_EINVAL, "%s: position and row_offset must be >= 0", what);
+    if (n > INT64_MAX / F - row_offset) return fail(LCREC_EINVAL, "%s: (row_offset + n) * features overflows", what);
+    return LCREC_OK;
+}
+
+int dropout_apply(const float *in, float *out, int64_t n, int F, uint32_t T, float s, const int64_t *seed, const int64_t *step,
+                  int position, int64_t row_offset, hipStream_t stream)
+{
+    if (int rc = dropout_check("dropout_apply", n, F, seed, step, position, row_offset)) return rc;
+    // s = 1 / (1 - p) with 0 <= p < 1: finite and >= 1 (p >= 1 gives inf or a negative value, p < 0 a value below 1, NaN neither)
+    if (!(s >= 1.0f) || s > 3.4028234e38f) return fail(LCREC_EINVAL, "dropout_apply: scale %g is not 1 / (1 - p) of a p in [0, 1)", (double)s);
+    if (n == 0) return LCREC_OK;
+    if (!in || !out) return fail(LCREC_EINVAL, "dropout_apply: NULL pointer");
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return fail(LCREC_EINVAL, "dropout_apply: in and out must be 16-byte aligned");
+    const int64_t quads = n * F / 4;
+    TraceScope trace(K_DROPOUT, stream);
+    hipLaunchKernelGGL(dropout_kernel<false>, dim3((unsigned)dropout_grid(quads)), dim3(DROP_THREADS), 0, stream, in, out,
+                       (unsigned char *)nullptr, quads, (uint64_t)row_offset * (uint64_t)(F / 4), T, s, seed, step, (uint32_t)position);
+    return check_launch("dropout_apply kernel");
+}
+
+int dropout_mask(unsigned char *keep_out, int64_t n, int F, uint32_t T, const int64_t *seed, const int64_t *step, int position,
+                 int64_t row_offset, hipStream_t stream)
+{
+    if (int rc = dropout_check("dropout_mask", n, F, seed, step, position, row_offset)) return rc;
+    if (n == 0) return LCREC_OK;
+    if (!keep_out) return fail(LCREC_EINVAL, "dropout_mask: NULL pointer");
+    if ((uintptr_t)keep_out & 3) return fail(LCREC_EINVAL, "dropout_mask: keep_out must be 4-byte aligned");
+    const int64_t quads = n * F / 4;
+    TraceScope trace(K_DROPOUT, stream);
+    hipLaunchKernelGGL(dropout_kernel<true>, dim3((unsigned)dropout_grid(quads)), dim3(DROP_THREADS), 0, stream, (const float *)nullptr,
+                       (float *)nullptr, keep_out, quads, (uint64_t)row_offset * (uint64_t)(F / 4), T, 1.0f, seed, step, (uint32_t)position);
+    return check_launch("dropout_mask kernel");
 }
 
 }  // namespace lcrec

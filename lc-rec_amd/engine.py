@@ -36,9 +36,19 @@ branches' under-filled kernels side by side to any useful degree.
 
 The EMA codebook update of index_improve/ is part of the captured step (lcrec_ema_update); the steps on which a dead-code
 reset is due run eagerly.  Data-parallel runs use the same line with the exchanges in it.  What the
-engine does not cover falls back to the autograd path in trainer.py, unchanged: dropout > 0, activations other than ReLU,
-optimisers other than Adam/AdamW/SGD/Adagrad/RMSprop (and those with maximize, differentiable, Adam's amsgrad, more than
-one param group or sparse gradients), --strict_nan_check (the reference's per-step host sync).
+engine does not cover falls back to the autograd path in trainer.py, unchanged: dropout under data parallelism (and
+p >= 1), activations other than ReLU, optimisers other than Adam/AdamW/SGD/Adagrad/RMSprop (and those with maximize,
+differentiable, Adam's amsgrad, more than one param group or sparse gradients), --strict_nan_check (the reference's
+per-step host sync).
+
+Dropout (--dropout_prob, 0 < p < 1, single process) is part of the line: the nn.Dropout in front of every Linear becomes
+one lcrec_dropout_apply on the layer's input going forward and one on the gradient its dX GEMM produces going back.  The
+mask is a function -- Philox4x32-10 of (seed, step, position, element), include/lcrec.h -- not torch's random stream: the
+seed is a device scalar fixed when the engine is built (drawn from torch's CPU generator, so torch.manual_seed governs
+it), the step is the device step counter the optimiser kernel advances, positions number the Dropout modules (encoder
+0 .. k-1, decoder k .. 2k-1).  A replayed graph therefore draws a new mask every step with no new kernel argument.  A step
+skipped for a NaN loss leaves the counter where it was, so the next step would repeat its masks: the NaN flag is sticky
+and the epoch raises, so no such step's result is ever used.  The autograd path keeps torch's nn.Dropout.
 """
 import os
 
@@ -81,14 +91,16 @@ def _rule(optimizer):
 
 class TrainEngine:
     def __init__(self, model, optimizer, schedule, warmup_steps, total_steps, max_norm=1.0, use_graph=True, use_ema=False,
-                 dist=None, dp_graph="auto", fuse_bn=None, scheduler=None):
+                 dist=None, dp_graph="auto", fuse_bn=None, scheduler=None, dropout_seed=None):
         """schedule: "linear" | "constant" (index/trainer.py:83-92) or None (fixed learning rate).
         scheduler: the LambdaLR driving `optimizer`, if any: SGD keeps no step count in its state, so the steps taken before
         the engine takes over are its last_epoch.
         use_ema: the improve fork's EMA codebook update after every step (index_improve/trainer.py:119).
         dist: an enabled dist.DistContext for item-sharded data parallel (the caller sets dist.set_batch before a step).
         dp_graph: "on" captures the data-parallel step with its RCCL collectives; "off" launches the same line eagerly;
-        "auto" = on for a one-rank group (run in the GPU suite), off for more ranks -- UNVERIFIED on more than one GPU."""
+        "auto" = on for a one-rank group (run in the GPU suite), off for more ranks -- UNVERIFIED on more than one GPU.
+        dropout_seed: the 64-bit seed of the dropout masks when the model has dropout > 0; None draws one from torch's
+        default CPU generator."""
         self.model = model
         # BatchNorm folded into the GEMMs on either side of it (lcrec_linear_bn_forward: 56 launches per step instead of 68).
         # OFF by default: measured slower on MI355X (1.28 vs 1.18 ms per step at the run.sh shape) -- a hand-over between
@@ -132,6 +144,12 @@ class TrainEngine:
         self.last_idx = None
         self._bn_counters = None                                             # BatchNorm1d.num_batches_tracked tensors ...
         self._bn_pending = 0                                                 # ... and the steps not yet added to them
+        # dropout: the masks' seed as a device scalar (p == 0: nothing drawn, nothing allocated, no launch)
+        self.dropout_seed = None
+        if model.encoder.dropout > 0 or model.decoder.dropout > 0:
+            if dropout_seed is None:
+                dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())
+            self.dropout_seed = ops._i64_scalar(int(dropout_seed), "dropout_seed", dev)
         # whoever reads the state dict (a checkpoint, a test) sees the host-side bookkeeping brought up to date first
         model.register_state_dict_pre_hook(lambda _m, _prefix, _keep: self.sync_host_state())
         optimizer.register_state_dict_pre_hook(lambda _opt: self.sync_host_state())
@@ -165,7 +183,10 @@ class TrainEngine:
             return f"e_dim {model.e_dim}"
         for mlp in (model.encoder, model.decoder):
             if mlp.dropout > 0:
-                return "dropout"
+                if not mlp.dropout < 1:
+                    return "dropout p >= 1"
+                if dist is not None and dist.enabled:
+                    return "dropout under data parallelism"
             if not mlp.fusable():
                 return "non-ReLU activation"
             for g in mlp._groups:
@@ -253,20 +274,31 @@ class TrainEngine:
             state.update(views)
 
     # ------------------------------------------------------------------ the step, as library calls
-    def _mlp_forward(self, mlp, h):
-        """One MLP going forward.  Per layer `saved` gets (layer input, Linear, BatchNorm | None, relu, t, y, mean, rstd,
+    def _mlp_forward(self, mlp, h, pos0=0):
+        """One MLP going forward; pos0 = the dropout position of its first layer.  Per layer `saved` gets (layer input, Linear, BatchNorm | None, relu, t, y, mean, rstd,
         in_fold, out_fold): with FUSED BatchNorm (single process, batch-sized launches -- lcrec_linear_bn_forward) no
         activation y is ever written: a layer's input is the previous layer's pre-BatchNorm output t plus that BatchNorm's
         folded (scale, shift) = in_fold, applied by the consumers' operand staging; out_fold is this layer's own."""
         saved = []
         mods = mlp.mlp_layers
         groups = mlp._groups
-        fused = self.fuse_bn and self.dist is None and all(
+        p = mlp.dropout if self.dropout_seed is not None else 0.0
+        # (with dropout the unfused line runs: the fused one hands t and a fold from layer to layer, and there is no y to mask)
+        fused = self.fuse_bn and self.dist is None and not p > 0 and all(
             ops.linear_bn_supported(h.shape[0], mods[g["linear"]].in_features, mods[g["linear"]].out_features) for g in groups)
         fold = None                                                          # (scale, shift, relu) of the tensor `h` stands for
-        for g in groups:
+        for l, g in enumerate(groups):
             lin = mods[g["linear"]]
             relu = "act" in g
+            if p > 0:
+                # The Dropout in front of this Linear: `saved` holds the dropped tensor, the input dW must see.  The first
+                # input (the batch -- also the reconstruction target and the graph's static input -- or the quantiser's
+                # output) is masked out of place.  Every later one is the previous layer's y, masked in place: y has one
+                # more reader, that layer's backward, which takes the ReLU mask [y > 0] from it (or recomputes it from t).
+                # With m the keep mask and s > 0, [m*y*s > 0] = [y > 0] * m, and the gradient that arrives there has been
+                # through this same position's mask already (_mlp_backward), so it is zero wherever m is: the product is
+                # the one the undropped y gives.
+                h = ops.dropout_apply(h, p, self.dropout_seed, self.step_count, pos0 + l, out=h if l > 0 else None)
             if fused:
                 bn = mods[g["bn"]] if "bn" in g else None
                 bn_args = None if bn is None else (bn.weight.data, bn.bias.data, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
@@ -303,8 +335,9 @@ class TrainEngine:
             raise ops._lib.LcrecError("engine: the last layer of an MLP has no BatchNorm (layers.py:19-30)")
         return h, saved
 
-    def _mlp_backward(self, saved, g, need_input_grad, dw, last_bias_done=False):
-        """The dX chain of one MLP: BatchNorm/ReLU backward -> dX GEMM -> next layer.  Weight gradients are leaves of the
+    def _mlp_backward(self, saved, g, need_input_grad, dw, last_bias_done=False, drop=None):
+        """The dX chain of one MLP: BatchNorm/ReLU backward -> dX GEMM (-> the dropout mask of that layer's input: drop =
+        (p, position of the first layer), or None) -> next layer.  Weight gradients are leaves of the
         dependency graph and most of them are a handful of tiles: they are queued in `dw` as (dt, layer input, gradient
         view[, input fold]) and computed by ONE grouped launch at the end of the step (lcrec_linear_backward_weights)."""
         gv = self.grad_view
@@ -336,6 +369,8 @@ class TrainEngine:
                                             True, False)[0]
                 else:
                     g = ops.linear_backward(dt, h, w, True, False)[0]
+                if drop is not None:                     # d (mask * x * s) / d x: the forward's call, on the gradient
+                    g = ops.dropout_apply(g, drop[0], self.dropout_seed, self.step_count, drop[1] + i, out=g)
             else:
                 g = None
         return g
@@ -343,13 +378,16 @@ class TrainEngine:
     def _run(self, x, eager):
         m = self.model
         levels = list(m.rq.vq_layers)
-        z, enc = self._mlp_forward(m.encoder, x)
+        k = len(m.encoder._groups)                                           # dropout positions: encoder 0 .. k-1, decoder k .. 2k-1
+        drops = [(mlp.dropout, pos0) if self.dropout_seed is not None and mlp.dropout > 0 else None
+                 for mlp, pos0 in ((m.encoder, 0), (m.decoder, k))]
+        z, enc = self._mlp_forward(m.encoder, x, 0)
         if eager and any(not q.initted for q in levels):
             m.rq._lazy_kmeans(z.reshape(-1, m.e_dim), True)                 # vq.py:67-68, first training batch only
         cbs = [q.embedding.weight.data for q in levels]
         q = quantize_values(z, cbs, float(m.rq.beta), level_plan(levels, True), False, True, want_loss=False)
         self.last_idx = q["idx"]                                             # [rows, L] of the last step (a graph's static output)
-        out, dec = self._mlp_forward(m.decoder, q["xq"])
+        out, dec = self._mlp_forward(m.decoder, q["xq"], k)
         # (BatchNorm1d.num_batches_tracked is only ever read by checkpoints: counted on the host, written by sync_host_state)
         if self._bn_counters is None:
             self._bn_counters = [s[2].num_batches_tracked for s in enc + dec if s[2] is not None]
@@ -376,7 +414,7 @@ class TrainEngine:
         ops.step_losses(sse, n, e, float(m.rq.beta), m.quant_loss_weight, recon, self.last, self.sums, self.bad[0],
                         poison_probe=probe, poison_flag=self.bad[1])
         dw = []
-        g_xq = self._mlp_backward(dec, g_out, True, dw)
+        g_xq = self._mlp_backward(dec, g_out, True, dw, drop=drops[1])
         if world is not None and self._late_span is not None:
             ops.linear_backward_weights(dw, splits=DW_SPLITS)                # the decoder's weight gradients, one launch ...
             dw = []
@@ -393,7 +431,7 @@ class TrainEngine:
         # per-code (count, sum) of every level and the codebook gradients (scale * (cnt*C - sum)) * g_loss: one launch
         stats = ops.code_stats_levels(q["idx"], q["resid_in"], [c.shape[0] for c in cbs], cbs,
                                       [self.grad_view[lvl.embedding.weight] for lvl in levels], scale, m.quant_loss_weight)
-        self._mlp_backward(enc, gz, False, dw, last_bias_done=bias_here)
+        self._mlp_backward(enc, gz, False, dw, last_bias_done=bias_here, drop=drops[0])
         ops.linear_backward_weights(dw, splits=DW_SPLITS)                    # all 14 weight gradients, one launch: 2 000 tiles, one chain each
         del dw
         if world is not None:

@@ -960,6 +960,68 @@ def rmsprop_step(params, grads, square_avg, step, lr, alpha=0.99, eps=1e-8, weig
                 clip, schedule, warmup_steps, total_steps, lr_out, skip_flag)
 
 
+def dropout_threshold(p):
+    """(T, s) of include/lcrec.h's keep rule for a drop probability 0 <= p < 1: an element is kept iff its Philox word
+    u >= T = min(2^32 - 1, floor(p * 2^32)), and a kept value is x * s, s = (float)(1 / (1 - p))."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise _lib.LcrecError(f"dropout: p must satisfy 0 <= p < 1, got {p}")
+    return min(2 ** 32 - 1, int(p * 4294967296.0)), 1.0 / (1.0 - p)
+
+
+def _i64_scalar(v, name, device):
+    """A device int64 scalar: `v` itself if it is one, else a new one holding the Python integer `v` (wrapped to 64 bits)."""
+    if isinstance(v, torch.Tensor):
+        if not (v.is_cuda and v.dtype == torch.int64 and v.numel() == 1):
+            raise _lib.LcrecError(f"{name} must be a device int64 scalar (or a Python int)")
+        return v
+    v = int(v) & (2 ** 64 - 1)
+    return torch.tensor(v - 2 ** 64 if v >= 2 ** 63 else v, dtype=torch.int64, device=device)
+
+
+def _dropout_shape(shape, name):
+    if len(shape) != 2 or shape[1] < 4 or shape[1] % 4:
+        raise _lib.LcrecError(f"{name}: expected [rows, features] with features a positive multiple of 4, got {tuple(shape)}")
+    return int(shape[0]), int(shape[1])
+
+
+def dropout_apply(x, p, seed, step, position, row_offset=0, out=None):
+    """mask * x * s for the mask of (seed, step, position) -- lcrec_dropout_apply; the backward of it is the same call on the
+    gradient.  seed, step: device int64 scalars the kernel reads when it runs (or Python ints).  out: None (a new tensor), x
+    itself (in place) or another contiguous tensor of x's shape."""
+    lib = _lib.load()
+    T, s = dropout_threshold(p)
+    x = _dev(x, "x")
+    n, F = _dropout_shape(x.shape, "dropout_apply")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == x.shape):
+        raise _lib.LcrecError("out must be a contiguous float32 device tensor of x's shape")
+    with _on(x.device):
+        # (held in names until the call is made: a temporary's block would go back to the allocator, and to the next one)
+        seed, step = _i64_scalar(seed, "seed", x.device), _i64_scalar(step, "step", x.device)
+        rc = lib.lcrec_dropout_apply(_ptr(x), _ptr(out), n, F, T, s, _ptr(seed), _ptr(step), int(position), int(row_offset),
+                                     _stream_ptr())
+    _lib.check(rc, "lcrec_dropout_apply")
+    return out
+
+
+def dropout_mask(shape, p, seed, step, position, row_offset=0, device=None):
+    """uint8 [rows, features]: 1 where dropout_apply keeps the element for (seed, step, position) -- lcrec_dropout_mask."""
+    lib = _lib.load()
+    T, _ = dropout_threshold(p)
+    n, F = _dropout_shape(tuple(shape), "dropout_mask")
+    if device is None:
+        device = seed.device if isinstance(seed, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    keep = torch.empty((n, F), dtype=torch.uint8, device=device)
+    with _on(device):
+        seed, step = _i64_scalar(seed, "seed", device), _i64_scalar(step, "step", device)       # (see dropout_apply)
+        rc = lib.lcrec_dropout_mask(_ptr(keep), n, F, T, _ptr(seed), _ptr(step), int(position), int(row_offset), _stream_ptr())
+    _lib.check(rc, "lcrec_dropout_mask")
+    return keep
+
+
 def trace_enable(on=True):
     """Bracket every kernel launch with hipEvents (include/lcrec.h, lcrec_trace_enable)."""
     _lib.check(_lib.load().lcrec_trace_enable(int(bool(on))), "lcrec_trace_enable")

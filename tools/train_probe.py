@@ -3,6 +3,7 @@
 the reference's CPU path does ~7-12 k items/s at batch 2048).
 
     python tools/train_probe.py [--in_dim 768] [--batch 2048] [--steps 30] [--bn] [--ema] [--learner AdamW|Adam|SGD|Adagrad|RMSprop]
+                                 [--dropout P]
 """
 import argparse
 import os
@@ -29,7 +30,7 @@ def trainer_probe(a):
                 "--no_kmeans_init", "--num_emb_list", "256", "256", "256", "256",          # run.sh: 4 levels, Sinkhorn on the last
                 "--sk_epsilons", "0.0", "0.0", "0.0", "0.0" if a.no_sk else "0.003"] \
             + (["--bn", "True"] if a.bn else ["--no_bn"]) + (["--strict_nan_check"] if a.strict else []) + ["--train_engine", a.engine] \
-            + ["--learner", a.learner]
+            + ["--learner", a.learner] + (["--dropout_prob", str(a.dropout)] if a.dropout > 0 else [])
         args = cli.parse_args(argv)
         ctx = None
         if a.rccl1:
@@ -67,7 +68,7 @@ def trainer_probe(a):
         if ctx is not None:
             ldist.shutdown(ctx)
         print(f"Trainer._train_epoch{' [one-rank RCCL group, %d collectives/step]' % (eng.collectives // 2 if eng is not None else -1) if a.rccl1 else ''}: "
-              f"in_dim {a.in_dim} batch {a.batch} levels 4 sinkhorn {not a.no_sk} bn {a.bn} strict_nan_check {a.strict} learner {a.learner} "
+              f"in_dim {a.in_dim} batch {a.batch} levels 4 sinkhorn {not a.no_sk} bn {a.bn} strict_nan_check {a.strict} learner {a.learner} dropout {a.dropout:g} "
               f"engine {'hipGraph (%d replays)' % eng.graph_replays if eng is not None else 'off (autograd path)'}: "
               f"{dt / steps * 1e3:.3f} ms/step, {a.batch * steps / dt:,.0f} items/s")
 
@@ -86,6 +87,7 @@ def main():
     ap.add_argument("--rccl1", action="store_true", help="with --trainer: data-parallel step on a one-rank RCCL group")
     ap.add_argument("--learner", default="AdamW", choices=["AdamW", "Adam", "SGD", "Adagrad", "RMSprop"],
                     help="the optimiser (--learner of lcrec_amd.main)")
+    ap.add_argument("--dropout", type=float, default=0.0, help="dropout probability (--dropout_prob of lcrec_amd.main)")
     ap.add_argument("--trainer", action="store_true",
                     help="time lcrec_amd.trainer.Trainer._train_epoch itself (loader, NaN check, fused AdamW, schedule)")
     a = ap.parse_args()
@@ -94,7 +96,7 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(2024)
     model = lcrec_amd.RQVAE(in_dim=a.in_dim, num_emb_list=[256] * 4, e_dim=32, layers=[2048, 1024, 512, 256, 128, 64],
-                            bn=a.bn, kmeans_init=False, sk_epsilons=[0.0, 0.0, 0.0, 0.0 if a.no_sk else 0.003],
+                            bn=a.bn, dropout_prob=a.dropout, kmeans_init=False, sk_epsilons=[0.0, 0.0, 0.0, 0.0 if a.no_sk else 0.003],
                             sk_iters=50, ema_decay=0.99 if a.ema else None).to(dev)
     x = torch.randn((a.batch, a.in_dim), device=dev)
     with torch.no_grad():   # data-scale codebooks
@@ -128,7 +130,7 @@ def main():
     dt = time.perf_counter() - t0
     tr = ops.trace_collect()
     ops.trace_enable(False)
-    print(f"in_dim {a.in_dim} batch {a.batch} bn {a.bn} ema {a.ema} learner {a.learner}: {dt / a.steps * 1e3:.3f} ms/step, "
+    print(f"in_dim {a.in_dim} batch {a.batch} bn {a.bn} ema {a.ema} learner {a.learner} dropout {a.dropout:g}: {dt / a.steps * 1e3:.3f} ms/step, "
           f"{a.batch * a.steps / dt:,.0f} items/s, loss {loss.item():.4f}")
     lib_ms = sum(v[1] for v in tr.values()) / a.steps
     print(f"  lcrec kernels: {lib_ms:.3f} ms/step ->", {k: (v[0] // a.steps, round(v[1] / a.steps, 3)) for k, v in tr.items()})

@@ -191,8 +191,9 @@ class TrainEngine:
                 return "non-ReLU activation"
             for g in mlp._groups:
                 lin = mlp.mlp_layers[g["linear"]]
-                if lin.bias is None or lin.in_features % 4 or lin.out_features % 4:
-                    return "Linear shape"
+                # (lcrec_linear_forward takes in_features in multiples of 8; the backward products and the flat buffers need 4)
+                if lin.bias is None or lin.in_features % 8 or lin.out_features % 4:
+                    return f"Linear shape ({lin.in_features} -> {lin.out_features}{'' if lin.bias is not None else ', no bias'})"
                 if "bn" in g:
                     bn = mlp.mlp_layers[g["bn"]]
                     if type(bn) is not nn.BatchNorm1d or bn.momentum is None or not bn.track_running_stats or not bn.affine:

@@ -218,6 +218,11 @@ class MLPLayers(nn.Module):
                 mods.append(act)
             self._groups.append(group)
         self.mlp_layers = nn.Sequential(*mods)
+        # lcrec_linear_forward -- what every path through this stack calls, training or not -- stages a layer's input eight
+        # floats at a time: a width it has no kernel for is known here, and forward says so before anything is launched
+        odd = [(i, w) for i, w in enumerate(layers[:-1]) if w % 8]
+        self.shape_error = (f"MLPLayers {list(layers)}: Linear {odd[0][0]} has in_features={odd[0][1]}, not a multiple of 8 "
+                            "(lcrec_linear_forward has no kernel for it)") if odd else None
         self.apply(self.init_weights)
 
     def init_weights(self, module):
@@ -255,6 +260,8 @@ class MLPLayers(nn.Module):
                    and ("act" not in g or isinstance(mods[g["act"]], nn.ReLU)) for g in self._groups)
 
     def forward(self, input_feature):
+        if self.shape_error:
+            raise ops._lib.LcrecError(self.shape_error)
         x = input_feature
         if x.dim() != 2:
             x = x.reshape(-1, x.shape[-1])

@@ -40,7 +40,20 @@ class RQVAE(nn.Module):
         self.decode_layer_dims = self.encode_layer_dims[::-1]
         self.decoder = MLPLayers(layers=self.decode_layer_dims, dropout=self.dropout_prob, bn=self.bn)
 
+    def shape_error(self):
+        """Why no kernel of the library runs this model -- the dimension at fault, by name -- or None.  forward, get_indices and
+        the Trainer ask before they launch anything, so such a model fails whole instead of half-way through a step."""
+        if self.e_dim not in (16, 32, 64):
+            return f"RQVAE: e_dim={self.e_dim} (the quantiser kernels support 16, 32, 64)"
+        return self.encoder.shape_error or self.decoder.shape_error
+
+    def _check_shape(self):
+        reason = self.shape_error()
+        if reason:
+            raise ops._lib.LcrecError(reason)
+
     def forward(self, x, use_sk=True, use_ema=True):
+        self._check_shape()
         x = self.encoder(x)
         x_q, rq_loss, indices = self.rq(x, use_sk=use_sk, use_ema=use_ema)
         out = self.decoder(x_q)
@@ -50,6 +63,7 @@ class RQVAE(nn.Module):
     def get_indices(self, xs, use_sk=False):
         """rqvae.py:68-72.  In eval mode with hard assignment this is ONE library call
         (lcrec_encode_assign): encoder GEMM chain + all quantiser levels, nothing else computed."""
+        self._check_shape()
         levels = list(self.rq.vq_layers)
         hard = (not use_sk) or all(q.sk_epsilon <= 0 for q in levels)
         if hard and not self.training and self.encoder.fusable() and xs.dim() == 2:

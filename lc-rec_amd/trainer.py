@@ -178,6 +178,9 @@ class Trainer(object):
         if not self._engine_decided:
             self._engine_decided = True
             from .engine import TrainEngine
+            broken = self.model.shape_error() if hasattr(self.model, "shape_error") else None
+            if broken:                         # neither the engine nor the autograd path has kernels for it: say so now
+                raise ops._lib.LcrecError(broken)
             reason = TrainEngine.unsupported_reason(self.model, self.optimizer, self.args, self.dist, self.use_ema)
             if reason is None and (os.environ.get("LCREC_TRAIN_ENGINE", "1") == "0"
                                    or getattr(self.args, "train_engine", "auto") == "off"):

@@ -31,11 +31,15 @@ def linear_slot(layer, bn):
     return layer * (4 if bn else 3) + 1
 
 
-def mlp(sd, prefix, x, n_layers, bn, training=False):
+def mlp(sd, prefix, x, n_layers, bn, training=False, masks=None):
     """MLPLayers.forward (layers.py:42).  `sd` maps state-dict names to tensors; in training mode
-    the BatchNorm running statistics in `sd` are updated in place, as nn.BatchNorm1d does."""
+    the BatchNorm running statistics in `sd` are updated in place, as nn.BatchNorm1d does.
+    `masks`: the Dropout in front of every Linear (layers.py:20) with GIVEN draws -- masks[prefix][l] holds, for the input
+    of layer l, keep * 1/(1-p) per element; None (the default) is p = 0, nothing is multiplied."""
     for l in range(n_layers):
         slot = linear_slot(l, bn)
+        if masks is not None:
+            x = x * masks[prefix][l].to(x.dtype)
         x = F.linear(x, sd[f"{prefix}.mlp_layers.{slot}.weight"], sd[f"{prefix}.mlp_layers.{slot}.bias"])
         if l != n_layers - 1:
             if bn:
@@ -133,11 +137,11 @@ class Spec:
         return [sd[f"rq.vq_layers.{l}.embedding.weight"] for l in range(self.levels)]
 
 
-def forward(spec, sd, x, use_sk=True, training=False, hook=None, force_idx=None):
-    """RQVAE.forward (rqvae.py:61-66): returns (out, rq_loss, indices)."""
-    z = mlp(sd, "encoder", x, spec.n_layers, spec.bn, training)
+def forward(spec, sd, x, use_sk=True, training=False, hook=None, force_idx=None, masks=None):
+    """RQVAE.forward (rqvae.py:61-66): returns (out, rq_loss, indices).  `masks`: see mlp."""
+    z = mlp(sd, "encoder", x, spec.n_layers, spec.bn, training, masks)
     q, rq_loss, idx = rq(z, spec.codebooks(sd), spec.beta, use_sk, spec.sk_epsilons, spec.sk_iters, hook, force_idx)
-    out = mlp(sd, "decoder", q, spec.n_layers, spec.bn, training)
+    out = mlp(sd, "decoder", q, spec.n_layers, spec.bn, training, masks)
     return out, rq_loss, idx
 
 

@@ -168,3 +168,75 @@ def strided_sample(a, limit=2048):
     flat = np.asarray(a).reshape(-1)
     step = max(1, -(-flat.size // limit))
     return flat[::step]
+
+
+# ---------------------------------------------------------------- the engine's support matrix, one step per configuration
+# (tests/test_gpu_support_matrix.py; judged by tests/step_check.py against oracle/torch_ref.py in fp64 -- no fixture)
+def _matrix(in_dim, layers, e_dim, codes, bn, loss, batch, sk, beta=0.25, qlw=1.0, dropout=0.0):
+    return dict(in_dim=in_dim, layers=layers, e_dim=e_dim, codes=codes, bn=bn, loss=loss, batch=batch, sk=sk, beta=beta,
+                qlw=qlw, dropout=dropout)
+
+
+SUPPORT_MATRIX = {
+    "A": _matrix(72, [40, 24], 16, [100, 7, 32], False, "l1", 37, [0.0, 0.0, 0.003]),
+    "B": _matrix(128, [72, 40], 64, [64, 48], True, "mse", 50, [0.003, 0.0], beta=0.5, qlw=0.3),
+    "C": _matrix(32, [], 32, [16, 16], False, "mse", 2, [0.0, 0.0]),
+    "D": _matrix(64, [32], 16, [32, 32, 32], True, "l1", 64, [0.003, 0.003, 0.003], qlw=2.0),
+    "E": _matrix(40, [24], 16, [7, 5], False, "mse", 1, [0.0, 0.0]),
+    "F": _matrix(136, [264, 72, 40], 32, [256, 100], True, "l1", 131, [0.0, 0.003]),
+    "G": _matrix(128, [72, 40], 64, [64, 48], True, "l1", 50, [0.003, 0.0], beta=0.5, qlw=0.3, dropout=0.3),
+    "H": _matrix(72, [40, 24], 16, [100, 7, 32], False, "mse", 37, [0.0, 0.0, 0.003], dropout=0.5),
+    # two Sinkhorn levels of more than 16 384 batch x codes entries each: the size from which the one-launch solver can
+    # give up, so that each level hands the engine a give-up probe (the second one is OR-ed into the flag on its own)
+    "I": _matrix(64, [32], 16, [32, 32], True, "mse", 600, [0.003, 0.003]),
+}
+SUPPORT_MATRIX_SK_ITERS = 50
+
+
+def near_miss(**changes):
+    """The plain model the walk along the edge of the matrix varies one thing of (test_the_edge_of_the_support_matrix)."""
+    base = _matrix(64, [32], 16, [32, 32], False, "mse", 48, [0.0, 0.003])
+    base.update(changes)
+    return base
+
+
+# the accepted side of that edge: the widths next to 36 and 100 that the kernels do take, the largest e_dim, dropout close to 1
+SUPPORT_EDGE = {
+    "a": near_miss(layers=[40]), "b": near_miss(layers=[104]), "c": near_miss(in_dim=40), "d": near_miss(in_dim=104),
+    "e": near_miss(e_dim=64), "f": near_miss(dropout=0.9),
+}
+
+
+def support_matrix_case(letter, config=None):
+    """(configuration, state dict name -> array, batch [rows, in_dim]) of one row of SUPPORT_MATRIX or SUPPORT_EDGE (or of
+    `config`, a dict of the same keys, under a letter of its own), all draws from
+    RandomState(ord(letter)) in this order: per MLP (encoder, decoder) and layer the Linear weight N(0, 2/(in+out)), its bias
+    0.05 N and, in front of a BatchNorm, gamma 1 + 0.1 N and beta 0.1 N (running statistics 0 / 1); the batch N(0, 1); per
+    level l the codebook = 0.6**l x rows of the encoder's training-mode latents of the batch (drawn with replacement, no
+    dropout) + 0.01 N."""
+    import torch
+    from oracle import torch_ref
+    c = config if config is not None else SUPPORT_MATRIX[letter] if letter in SUPPORT_MATRIX else SUPPORT_EDGE[letter]
+    r = rs(ord(letter))
+    dims = [c["in_dim"]] + list(c["layers"]) + [c["e_dim"]]
+    names = state_dict_names(len(dims) - 1, c["bn"], len(c["codes"]))
+    sd = {}
+    for part, d in (("encoder", dims), ("decoder", dims[::-1])):
+        for l, nme in enumerate(names[part]):
+            fan_in, fan_out = d[l], d[l + 1]
+            sd[nme + ".weight"] = f32(r.standard_normal((fan_out, fan_in)) * np.sqrt(2.0 / (fan_in + fan_out)))
+            sd[nme + ".bias"] = f32(0.05 * r.standard_normal(fan_out))
+            if c["bn"] and l != len(dims) - 2:
+                bn = names["bn"][part][l]
+                sd[bn + ".weight"] = f32(1.0 + 0.1 * r.standard_normal(fan_out))
+                sd[bn + ".bias"] = f32(0.1 * r.standard_normal(fan_out))
+                sd[bn + ".running_mean"], sd[bn + ".running_var"] = np.zeros(fan_out, np.float32), np.ones(fan_out, np.float32)
+                sd[bn + ".num_batches_tracked"] = np.zeros((), np.int64)
+    x = f32(r.standard_normal((c["batch"], c["in_dim"])))
+    scratch = {k: torch.from_numpy(v.copy()) for k, v in sd.items()}        # (training mode moves the running statistics)
+    with torch.no_grad():
+        z = torch_ref.mlp(scratch, "encoder", torch.from_numpy(x), len(dims) - 1, c["bn"], training=True).numpy()
+    for l, K in enumerate(c["codes"]):
+        rows = r.randint(0, c["batch"], size=K)
+        sd[names["codebooks"][l]] = f32(0.6 ** l * z[rows] + 0.01 * r.standard_normal((K, c["e_dim"])))
+    return c, sd, x

@@ -28,8 +28,7 @@
  *     reads a handful of environment variables ONCE per process, on the first call that
  *     consults them (function-local statics): they select between kernels that compute
  *     the same bits and exist for A/B measurements, not for configuration --
- *       LCREC_GEMM_PP, LCREC_GEMM_PP3, LCREC_GEMM_FAST, LCREC_GEMM_SMALL, LCREC_GEMM_TUNE,
- *       LCREC_GEMM_S16, LCREC_GEMM_S16_TILES
+ *       LCREC_GEMM_PP, LCREC_GEMM_PP3, LCREC_GEMM_FAST, LCREC_GEMM_S16, LCREC_GEMM_S16_TILES
  *                                  which tiling / kernel form lcrec_linear_forward (and the
  *                                  dX product of lcrec_linear_backward) takes
  *       LCREC_GEMM_SPLITK           cap on the K-runs of the weight gradient (changes S of

@@ -1674,114 +1674,6 @@ __global__ __launch_bounds__(256) void linear_s16_kernel(const float *__restrict
     }
 }
 
-static int launch_s16(const float *A, const float *W, const float *b, const float *sc, const float *sh, int relu, float *C, int64_t M,
-                      int N, int K, bool kmajor_w, hipStream_t stream)
-{
-    const int64_t bm_blocks = (M + S16_BM - 1) / S16_BM;
-    const int bn_blocks = (N + S16_BN - 1) / S16_BN;
-    const int64_t grid = bm_blocks * bn_blocks;
-    if (grid > 0x7fffffffLL) return fail(LCREC_EINVAL, "linear (32 x 64 tiles): grid too large");
-    TraceScope trace(K_LINEAR_32x64, stream);
-    if (kmajor_w) hipLaunchKernelGGL(linear_s16_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, A, W, b, sc, sh, C, M, N, K, relu, bn_blocks);
-    else hipLaunchKernelGGL(linear_s16_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, A, W, b, sc, sh, C, M, N, K, relu, bn_blocks);
-    return check_launch("linear_s16_kernel");
-}
-
-// Which launches take the 32 x 64 tiles: K a multiple of 32, and 64 x 64 tiles would leave the chip under-filled -- at most
-// LCREC_GEMM_S16_TILES (default below) of them.  LCREC_GEMM_S16=0 never, =1 whenever the shape allows (tuning).
-static bool use_s16_tiles(int64_t M, int N, int K)
-{
-    static const int mode = [] { const char *e = getenv("LCREC_GEMM_S16"); return e ? atoi(e) : -1; }();
-    static const int limit = [] { const char *e = getenv("LCREC_GEMM_S16_TILES"); return e ? atoi(e) : 128; }();
-    if (mode == 0 || K % BK != 0 || K < BK || N % 4 != 0 || (int64_t)K * 4 * (M + 64) >= (1ll << 31) || (int64_t)K * N * 4 >= (1ll << 31)) return false;
-    if (mode == 1) return true;
-    return ((M + 63) / 64) * ((N + 63) / 64) <= limit;
-}
-
-static int launch_pp2(dim3 grid, hipStream_t stream, const float *x, const float *W, const float *b, const float *sc,
-                      const float *sh, float *y, int64_t n, int out_dim, int in_dim, int relu, int bn_blocks, int bm_blocks,
-                      int xcd_order)
-{
-    constexpr size_t lds = (size_t)(2 * 128 + 2 * 128) * (BK + 4) * sizeof(float);     // 73 728 B
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp2_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(attr));
-    hipLaunchKernelGGL(linear_fwd_pp2_kernel, grid, dim3(512), lds, stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu,
-                       bn_blocks, bm_blocks, xcd_order);
-    return LCREC_OK;
-}
-
-static int launch_pp3(int total_virtual, hipStream_t stream, const float *x, const float *W, const float *b, const float *sc,
-                      const float *sh, float *y, int64_t n, int out_dim, int in_dim, int relu, int bn_blocks, int bm_blocks,
-                      int xcd_order)
-{
-    constexpr size_t lds = (size_t)(2 * 128 + 2 * 128 + 8 * 32) * LDK * sizeof(float);     // 110 592 B
-    static const int cus = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
-        return v > 8 ? v / 8 * 8 : 8;                // a multiple of 8 keeps a workgroup's tiles on its own XCD
-    }();
-    static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp3_kernel<false>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp3_kernel<true>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr0 != hipSuccess || attr1 != hipSuccess)
-        return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(attr0 != hipSuccess ? attr0 : attr1));
-    const int grid = total_virtual < cus ? total_virtual : cus;
-    if (sc)
-        hipLaunchKernelGGL(linear_fwd_pp3_kernel<true>, dim3((unsigned)grid), dim3(512), lds, stream, x, W, b, sc, sh, y, n, out_dim,
-                           in_dim, relu, bn_blocks, bm_blocks, total_virtual, xcd_order);
-    else
-        hipLaunchKernelGGL(linear_fwd_pp3_kernel<false>, dim3((unsigned)grid), dim3(512), lds, stream, x, W, b, sc, sh, y, n, out_dim,
-                           in_dim, relu, bn_blocks, bm_blocks, total_virtual, xcd_order);
-    return LCREC_OK;
-}
-
-static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *W, const float *b, const float *sc,
-                            const float *sh, int relu, int out_dim, float *y, int xcd_order, hipStream_t stream)
-{
-    const int64_t bm_blocks = (n + 255) / 256;
-    const int bn_blocks = (out_dim + 127) / 128;
-    const int64_t grid = xcd_order ? ((bm_blocks + 7) / 8) * 8 * bn_blocks : bm_blocks * bn_blocks;
-    if (grid > 0x7fffffffLL) return fail(LCREC_EINVAL, "linear_forward: grid too large (n=%lld)", (long long)n);
-    TraceScope trace(K_LINEAR_PP, stream);
-    // the persistent form where it applies (measured +1.2 % on C3, +0.5 .. +3.4 % per layer); LCREC_GEMM_PP3=0 turns it off
-    static const int pp3 = [] { const char *e = getenv("LCREC_GEMM_PP3"); return e ? atoi(e) : 1; }();
-    int rc;
-    if (pp3 && in_dim % 64 == 0 && in_dim >= 12 * BK && out_dim % 128 == 0 && (int64_t)out_dim * 4 * 128 < (1ll << 31))
-        rc = launch_pp3((int)grid, stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu, bn_blocks, (int)bm_blocks, xcd_order);
-    else
-        rc = launch_pp2(dim3((unsigned)grid), stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu, bn_blocks, (int)bm_blocks,
-                        xcd_order);
-    return rc ? rc : check_launch("linear_fwd_pp2_kernel");
-}
-
-template <int WAVES_M, int WAVES_N, int TM, int TN>
-static int launch_linear(const float *x, int64_t n, int in_dim, const float *W, const float *b,
-                         const float *sc, const float *sh, int relu, int out_dim, float *y,
-                         hipStream_t stream)
-{
-    constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
-    const int64_t bm_blocks = (n + BM - 1) / BM;
-    const int bn_blocks = (out_dim + BN - 1) / BN;
-    // LCREC_GEMM_TUNE=0 turns the XCD-aware tile order off (default on: same speed, 2.3x less fabric traffic by FETCH_SIZE)
-    static const int tune = [] { const char *e = getenv("LCREC_GEMM_TUNE"); return (e ? atoi(e) : 1) & 1; }();
-    const int64_t grid = (tune & 1) ? ((bm_blocks + 7) / 8) * 8 * bn_blocks : bm_blocks * bn_blocks;
-    if (grid > 0x7fffffffLL) return fail(LCREC_EINVAL, "linear_forward: grid too large (n=%lld)", (long long)n);
-    TraceScope trace(BM == 64 ? K_LINEAR_64x64 : BN == 128 ? K_LINEAR_128x128 : BN == 64 ? K_LINEAR_128x64 : K_LINEAR_128x32, stream);
-    // K % 32 == 0 (every layer of the run.sh architecture): the instantiation whose staging path has no VALU
-    static const int fast = [] { const char *e = getenv("LCREC_GEMM_FAST"); return e ? atoi(e) : 1; }();
-    if (fast && in_dim % BK == 0 && (int64_t)in_dim * 4 * (BM + 64) < (1ll << 31))
-        hipLaunchKernelGGL((linear_fwd_kernel<WAVES_M, WAVES_N, TM, TN, true>), dim3((unsigned)grid), dim3(256), 0,
-                           stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu, bn_blocks, (int)bm_blocks, tune, 1 << 30,
-                           (int64_t)0);
-    else
-        hipLaunchKernelGGL((linear_fwd_kernel<WAVES_M, WAVES_N, TM, TN, false>), dim3((unsigned)grid), dim3(256), 0,
-                           stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu, bn_blocks, (int)bm_blocks, tune, 1 << 30,
-                           (int64_t)0);
-    return check_launch("linear_fwd_kernel");
-}
-
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restrict__ partial, int splits, int64_t total4,
                                                           float *__restrict__ out)
 {
@@ -1793,27 +1685,209 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
     reinterpret_cast<f32x4 *>(out)[q] = acc;
 }
 
+// ---- Launch side: which kernel a shape gets.  Top to bottom: knobs, tile table, choosers, grid helper, launches, entry
+// points.  Every kernel gives the same bits for a given product; the one choice that changes bits is S, the K-runs of a
+// weight gradient (linear_backward_splits).  bench.py replays the forward rule (pp_fits, pp_head_rows,
+// forward_tile_shape) to attribute flops, and tests/test_gpu_kernels.py pins the trace labels at its boundaries.
+// Two knobs were retired on their measurements: LCREC_GEMM_TUNE=0 (XCD-aware tile order off; only the forward launches
+// honoured it) gave the same speed with 2.3x more fabric traffic by FETCH_SIZE -- the kernels keep their `tune` argument,
+// every launch passes XCD_ORDER; LCREC_GEMM_SMALL=1 / =2 (every batch-sized wide launch on 64 x 128 / on 128 x 64 tiles,
+// the latter <2,2,2,1>, launched by nothing else) was slower than 64 x 64 on all but the widest layer: wide_tiles_fill().
+
+// ---- knobs: A/B switches between kernels that compute the same bits (LCREC_GEMM_SPLITK excepted), read once per process
+static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+struct GemmKnobs {
+    int pp = env_int("LCREC_GEMM_PP", -1);                 // 0 / 1: never / always the ping-pong kernel where it applies (-1: by shape)
+    int pp3 = env_int("LCREC_GEMM_PP3", 1);                // 0: the per-tile instead of the persistent ping-pong kernel
+    int fast = env_int("LCREC_GEMM_FAST", 1);              // 0: guarded staging even where K % 32 == 0
+    int s16 = env_int("LCREC_GEMM_S16", -1);               // 0 / 1: never / wherever they can run: the 32 x 64 tiles (-1: by tile count)
+    int s16_tiles = env_int("LCREC_GEMM_S16_TILES", 128);  // most 64 x 64 tiles a launch may have and still take the 32 x 64 tiles
+    int splitk = env_int("LCREC_GEMM_SPLITK", 16);         // cap on S, the K-runs of a weight gradient (changes the bits of gw)
+};
+static const GemmKnobs &knobs() { static const GemmKnobs k; return k; }
+constexpr int XCD_ORDER = 1;        // the kernels' `tune` argument: row panel p -> XCD p % 8 (see linear_tile_body)
+
+// ---- the tile table: one row per shape the generic kernel (linear_tile_body) is launched with
+enum TileShape { TILE_64x64, TILE_128x128, TILE_128x64, TILE_128x32, TILE_64x128 };
+template <int WAVES_M_, int WAVES_N_, int TM_, int TN_, KernelId LABEL_>          // LABEL: what a launch is called in the trace
+struct Tile {
+    static constexpr int WAVES_M = WAVES_M_, WAVES_N = WAVES_N_, TM = TM_, TN = TN_, BM = WAVES_M_ * TM_ * 32, BN = WAVES_N_ * TN_ * 32;
+    static constexpr KernelId LABEL = LABEL_;
+};
+// calls f with the row of `shape` as a constant: the one place a runtime shape becomes template arguments
+template <class F>
+static auto with_tile(TileShape shape, F &&f)
+{
+    switch (shape) {
+    case TILE_128x128: return f(Tile<2, 2, 2, 2, K_LINEAR_128x128>{});
+    case TILE_128x64:  return f(Tile<4, 1, 1, 2, K_LINEAR_128x64>{});
+    case TILE_128x32:  return f(Tile<4, 1, 1, 1, K_LINEAR_128x32>{});
+    case TILE_64x128:  return f(Tile<2, 2, 1, 2, K_LINEAR_64x64>{});    // traced as 64x64 (tests and bench.py read it so)
+    default:           return f(Tile<2, 2, 1, 1, K_LINEAR_64x64>{});    // TILE_64x64
+    }
+}
+struct TileDims { int bm, bn; };
+static TileDims tile_dims(TileShape s) { return with_tile(s, [](auto tile) { return TileDims{decltype(tile)::BM, decltype(tile)::BN}; }); }
+
+// ---- choosers
 // a batch-sized launch (fewer than 512 tiles of 128 x 128) whose 64 x 128 tiles still give every CU one
 static bool wide_tiles_fill(int64_t M, int N) { return ((M + 63) / 64) * ((N + 127) / 128) >= 256; }
 
+// The forward rule: the tile shape of an [M][N] output -- lcrec_linear_forward where neither the ping-pong kernel nor
+// the 32 x 64 tiles apply, and both backward products.
+static TileShape forward_tile_shape(int64_t M, int N)
+{
+    if (N > 64) {
+        // batch-sized problems (a training step has 1-2 k rows): 128 x 128 tiles would leave most CUs idle, so launches
+        // with fewer than two tiles per CU use 64 x 64 tiles (4x the workgroups) -- or 64 x 128 tiles (two accumulators
+        // per wave: a K-tile's fixed costs are paid once per 32 MFMAs instead of 16) when those still fill the chip:
+        // 768 -> 2048 at batch 2048 72 -> 62 us, 4096 -> 2048 at batch 1024 148 -> 144 us
+        if (((M + 127) / 128) * ((N + 127) / 128) >= 512) return TILE_128x128;
+        return wide_tiles_fill(M, N) ? TILE_64x128 : TILE_64x64;
+    }
+    // 33 .. 64 columns: 128 x 64 tiles, or 64 x 64 while those would not give every CU one (a batch-sized launch: twice
+    // the workgroups, and the register-buffered K-tile: 128 -> 64 at batch 1024 9.0 -> ~5 us)
+    if (N > 32) return (M + 127) / 128 < 256 ? TILE_64x64 : TILE_128x64;
+    return TILE_128x32;
+}
+
+// The training forward (linear_bn_forward, which admits fewer than 512 tiles of 128 x 128 only): the forward rule, except
+// that 33 .. 64 columns ALWAYS get 64 x 64 tiles, never 128 x 64.  Only these three shapes have a training kernel.
+static TileShape train_tile_shape(int64_t n, int out_dim)
+{
+    if (out_dim > 64) return wide_tiles_fill(n, out_dim) ? TILE_64x128 : TILE_64x64;
+    return out_dim > 32 ? TILE_64x64 : TILE_128x32;
+}
+
+// Which launches take the 32 x 64 tiles (linear_s16_kernel): K a multiple of 32, and 64 x 64 tiles would leave the chip
+// under-filled -- at most knobs().s16_tiles of them.
+static bool use_s16_tiles(int64_t M, int N, int K)
+{
+    const int mode = knobs().s16;
+    if (mode == 0 || K % BK != 0 || K < BK || N % 4 != 0 || (int64_t)K * 4 * (M + 64) >= (1ll << 31) || (int64_t)K * N * 4 >= (1ll << 31)) return false;
+    if (mode == 1) return true;
+    return ((M + 63) / 64) * ((N + 63) / 64) <= knobs().s16_tiles;
+}
+
+// Wide layers: the ping-pong kernel (one 512-thread workgroup per CU) wins as soon as its 256 x 128 tiles fill the
+// 256 CUs in whole rounds: at least one round, and either >= 8 rounds or <= 20 % of the last round empty (measured with
+// tools/pp_sweep.sh: 8 192 x 768->2048 = 512 tiles: 117 vs 89 TFLOP/s; 16 896 x 1024->512 = 264 tiles: 76 vs 83).
+// Otherwise the generic kernels (several workgroups per CU, finer tail).
+static bool pp_fits(int64_t n, int out_dim)
+{
+    const int64_t tiles = ((n + 255) / 256) * ((out_dim + 127) / 128), rounds = (tiles + 255) / 256;
+    return tiles >= 256 && (rounds >= 8 || tiles * 5 >= rounds * 256 * 4);
+}
+
+// Mid-sized launches (Games: 16 859 rows = 65.9 row panels) leave the last round of 256 x 128 tiles mostly empty -- 1056
+// tiles are 4.1 rounds, 528 are 2.06 -- and a persistent workgroup's time is its LONGEST tile list.  Rows are
+// independent, so such a launch is cut at a row-panel boundary: the largest head whose tiles fill whole rounds (or >= 90 %
+// of the last one) goes to the ping-pong kernel, the tail (here 475 rows) to the other kernels in a second launch.  Same
+// chains, same bits.  Launches of >= 8 rounds are left alone (their partial round is noise).
+// Returns the head's row count, or 0 for no split.
+static int64_t pp_head_rows(int64_t n, int out_dim)
+{
+    const int64_t ntile = (out_dim + 127) / 128;
+    const int64_t tiles = ((n + 255) / 256) * ntile, rounds = (tiles + 255) / 256, last_round = tiles % 256;
+    if (rounds >= 8 || last_round == 0 || last_round * 10 >= 256 * 9) return 0;
+    // (the tail stays below one round of tiles: look back at most 256 / ntile panels)
+    for (int64_t p = n / 256; p >= 1 && p * ntile >= 256 && p >= n / 256 - 256 / ntile; --p) {
+        const int64_t last = p * ntile % 256;
+        if (last == 0 || last * 10 >= 256 * 9) return p * 256 < n ? p * 256 : 0;     // (0: the launch is whole rounds already)
+    }
+    return 0;
+}
+
+// ---- the grid of an [M][N] output in bm x bn tiles.  xcd_padded: the row-panel count rounded up to the 8 XCDs, which the
+// XCD-aware tile numbering needs (it has holes, see linear_tile_body).  Fails when the grid does not fit a launch.
+struct TileGrid { int64_t bm_blocks; int bn_blocks; unsigned grid; };
+static int tile_grid(TileGrid &g, const char *who, int64_t M, int N, int bm, int bn, bool xcd_padded)
+{
+    g.bm_blocks = (M + bm - 1) / bm;
+    g.bn_blocks = (N + bn - 1) / bn;
+    const int64_t grid = (xcd_padded ? (g.bm_blocks + 7) / 8 * 8 : g.bm_blocks) * g.bn_blocks;
+    if (grid > 0x7fffffffLL) return fail(LCREC_EINVAL, "%s: grid too large (%lld x %d)", who, (long long)M, N);
+    g.grid = (unsigned)grid;
+    return LCREC_OK;
+}
+
+// ---- launches
+static int launch_s16(const float *A, const float *W, const float *b, const float *sc, const float *sh, int relu, float *C, int64_t M,
+                      int N, int K, bool kmajor_w, hipStream_t stream)
+{
+    TileGrid g;
+    if (int rc = tile_grid(g, "linear (32 x 64 tiles)", M, N, S16_BM, S16_BN, false)) return rc;
+    TraceScope trace(K_LINEAR_32x64, stream);
+    const auto kernel = kmajor_w ? linear_s16_kernel<true> : linear_s16_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, stream, A, W, b, sc, sh, C, M, N, K, relu, g.bn_blocks);
+    return check_launch("linear_s16_kernel");
+}
+
+static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *W, const float *b, const float *sc,
+                            const float *sh, int relu, int out_dim, float *y, hipStream_t stream)
+{
+    constexpr size_t lds2 = (size_t)(2 * 128 + 2 * 128) * (BK + 4) * sizeof(float);            // 73 728 B
+    constexpr size_t lds3 = (size_t)(2 * 128 + 2 * 128 + 8 * 32) * LDK * sizeof(float);        // 110 592 B
+    TileGrid g;
+    if (int rc = tile_grid(g, "linear_forward", n, out_dim, 256, 128, XCD_ORDER)) return rc;
+    TraceScope trace(K_LINEAR_PP, stream);
+    // the persistent form where it applies (measured +1.2 % on C3, +0.5 .. +3.4 % per layer)
+    if (knobs().pp3 && in_dim % 64 == 0 && in_dim >= 12 * BK && out_dim % 128 == 0 && (int64_t)out_dim * 4 * 128 < (1ll << 31)) {
+        static const int cus = [] {
+            int dev = 0, v = 0;
+            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
+            return v > 8 ? v / 8 * 8 : 8;                // a multiple of 8 keeps a workgroup's tiles on its own XCD
+        }();
+        static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp3_kernel<false>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
+        static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp3_kernel<true>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
+        if (attr0 != hipSuccess || attr1 != hipSuccess)
+            return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds3, hipGetErrorString(attr0 != hipSuccess ? attr0 : attr1));
+        const int total = (int)g.grid;                   // tiles: each workgroup walks total / grid of them
+        const dim3 grid((unsigned)(total < cus ? total : cus));
+        hipLaunchKernelGGL(sc ? linear_fwd_pp3_kernel<true> : linear_fwd_pp3_kernel<false>, grid, dim3(512), lds3, stream, x, W, b, sc, sh, y,
+                           n, out_dim, in_dim, relu, g.bn_blocks, (int)g.bm_blocks, total, XCD_ORDER);
+    } else {
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp2_kernel),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+        if (attr != hipSuccess) return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds2, hipGetErrorString(attr));
+        hipLaunchKernelGGL(linear_fwd_pp2_kernel, dim3(g.grid), dim3(512), lds2, stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu,
+                           g.bn_blocks, (int)g.bm_blocks, XCD_ORDER);
+    }
+    return check_launch("linear_fwd_pp2_kernel");
+}
+
+template <class T>
+static int launch_linear(T, const float *x, int64_t n, int in_dim, const float *W, const float *b, const float *sc, const float *sh,
+                         int relu, int out_dim, float *y, hipStream_t stream)
+{
+    TileGrid g;
+    if (int rc = tile_grid(g, "linear_forward", n, out_dim, T::BM, T::BN, XCD_ORDER)) return rc;
+    TraceScope trace(T::LABEL, stream);
+    // K % 32 == 0 (every layer of the run.sh architecture): the instantiation whose staging path has no VALU
+    const bool fast = knobs().fast && in_dim % BK == 0 && (int64_t)in_dim * 4 * (T::BM + 64) < (1ll << 31);
+    const auto kernel = fast ? linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true> : linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, false>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu, g.bn_blocks,
+                       (int)g.bm_blocks, XCD_ORDER, 1 << 30, (int64_t)0);
+    return check_launch("linear_fwd_kernel");
+}
+
 // C[M][N] = A * B with A given [M][K] (TA false) or [K][M] (TA true) and B given [K][N] (always k-major here):
-// the two backward products of a Linear layer.  Same tiles and the same dispatch by (M, N) as the forward launches;
-// `splits` > 1 cuts K into that many runs of K-tiles whose partial products go to `partial` [splits][M][N].
-template <int WAVES_M, int WAVES_N, int TM, int TN, bool TA>
-static int launch_kmajor(const float *A, const float *B, int64_t M, int N, int K, float *C, int splits, float *partial,
+// the two backward products of a Linear layer.  `splits` > 1 cuts K into that many runs of K-tiles whose partial
+// products go to `partial` [splits][M][N].
+template <bool TA, class T>
+static int launch_kmajor(T, const float *A, const float *B, int64_t M, int N, int K, float *C, int splits, float *partial,
                          hipStream_t stream)
 {
-    constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
-    const int64_t bm_blocks = (M + BM - 1) / BM;
-    const int bn_blocks = (N + BN - 1) / BN;
-    const int64_t grid = ((bm_blocks + 7) / 8) * 8 * bn_blocks;
-    if (grid > 0x7fffffffLL) return fail(LCREC_EINVAL, "linear_backward: grid too large");
+    TileGrid g;
+    if (int rc = tile_grid(g, "linear_backward", M, N, T::BM, T::BN, XCD_ORDER)) return rc;
     const int nk = (K + BK - 1) / BK;
     const int per = splits > 1 ? (nk + splits - 1) / splits : 1 << 30;
-    TraceScope trace(BM == 64 ? K_LINEAR_64x64 : BN == 128 ? K_LINEAR_128x128 : BN == 64 ? K_LINEAR_128x64 : K_LINEAR_128x32, stream);
-    hipLaunchKernelGGL((linear_fwd_kernel<WAVES_M, WAVES_N, TM, TN, true, TA, true>), dim3((unsigned)grid, (unsigned)(splits > 1 ? splits : 1)),
+    TraceScope trace(T::LABEL, stream);
+    hipLaunchKernelGGL((linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, TA, true>), dim3(g.grid, (unsigned)(splits > 1 ? splits : 1)),
                        dim3(256), 0, stream, A, B, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
-                       splits > 1 ? partial : C, M, N, K, 0, bn_blocks, (int)bm_blocks, 1, per, splits > 1 ? M * (int64_t)N : (int64_t)0);
+                       splits > 1 ? partial : C, M, N, K, 0, g.bn_blocks, (int)g.bm_blocks, XCD_ORDER, per, splits > 1 ? M * (int64_t)N : (int64_t)0);
     if (splits > 1) {
         const int64_t total4 = M * (int64_t)N / 4;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, partial, splits, total4, C);
@@ -1821,28 +1895,48 @@ static int launch_kmajor(const float *A, const float *B, int64_t M, int N, int K
     return check_launch("linear_fwd_kernel (k-major operands)");
 }
 
-// which tile shape a (M, N) output gets: 0 = 64x64, 1 = 128x128, 2 = 128x64, 3 = 128x32, 4 = 64x128 (the forward rule)
-static int kmajor_shape(int64_t M, int N)
+template <class T>
+static int launch_train_fwd(T, const float *x, int64_t n, int in_dim, const float *W, const float *b, int out_dim, float *t,
+                            bool pro, bool stats, const TileExtras &ex, hipStream_t stream)
 {
-    if (N > 64) return ((M + 127) / 128) * ((N + 127) / 128) >= 512 ? 1 : (wide_tiles_fill(M, N) ? 4 : 0);
-    return N > 32 ? ((M + 127) / 128 < 256 ? 0 : 2) : 3;
+    TileGrid g;
+    if (int rc = tile_grid(g, "linear_bn_forward", n, out_dim, T::BM, T::BN, XCD_ORDER)) return rc;
+    TraceScope trace(T::LABEL, stream);
+    const auto kernel = pro && stats ? linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 1, true>
+                        : pro        ? linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 1, false>
+                                     : linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 0, true>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, stream, x, W, b, t, n, out_dim, in_dim, g.bn_blocks, (int)g.bm_blocks, XCD_ORDER, ex);
+    return check_launch("linear_train_fwd_kernel");
 }
 
-template <bool TA>
-static int gemm_kmajor(const float *A, const float *B, int64_t M, int N, int K, float *C, int splits, float *partial,
-                       hipStream_t stream)
+// ---- entry points
+int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const float *b,
+                   const float *bn_scale, const float *bn_shift, int relu, int out_dim, float *y,
+                   hipStream_t stream)
 {
-    if constexpr (!TA) {
-        if (splits <= 1 && use_s16_tiles(M, N, K))          // dX of an under-filled launch: the 32 x 64 tiles
-            return launch_s16(A, B, nullptr, nullptr, nullptr, 0, C, M, N, K, true, stream);
+    if (n == 0) return LCREC_OK;                       // empty batch: nothing to read or write
+    if (!x || !W || !y) return fail(LCREC_EINVAL, "linear_forward: NULL pointer");
+    if (n < 0 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_forward: bad shape");
+    if ((bn_scale == nullptr) != (bn_shift == nullptr))
+        return fail(LCREC_EINVAL, "linear_forward: bn_scale and bn_shift must both be given or both NULL");
+    if (in_dim % 8 != 0)
+        return fail(LCREC_EUNSUPPORTED, "linear_forward: in_dim=%d is not a multiple of 8", in_dim);
+    if (((uintptr_t)x | (uintptr_t)W) & 15)
+        return fail(LCREC_EINVAL, "linear_forward: x and W must be 16-byte aligned");
+    const int pp = knobs().pp;
+    const bool pp_ok = out_dim > 64 && in_dim % BK == 0 && (int64_t)in_dim * 4 * 192 < (1ll << 31);     // else the other kernels
+    if (const int64_t head = pp_ok && pp == -1 ? pp_head_rows(n, out_dim) : 0) {
+        int rc = launch_linear_pp(x, head, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
+        if (rc) return rc;
+        return linear_forward(x + head * in_dim, n - head, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y + head * out_dim, stream);
     }
-    switch (kmajor_shape(M, N)) {
-    case 0: return launch_kmajor<2, 2, 1, 1, TA>(A, B, M, N, K, C, splits, partial, stream);
-    case 1: return launch_kmajor<2, 2, 2, 2, TA>(A, B, M, N, K, C, splits, partial, stream);
-    case 2: return launch_kmajor<4, 1, 1, 2, TA>(A, B, M, N, K, C, splits, partial, stream);
-    case 4: return launch_kmajor<2, 2, 1, 2, TA>(A, B, M, N, K, C, splits, partial, stream);
-    default: return launch_kmajor<4, 1, 1, 1, TA>(A, B, M, N, K, C, splits, partial, stream);
-    }
+    if (pp_ok && (pp == 1 || (pp == -1 && pp_fits(n, out_dim))))
+        return launch_linear_pp(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
+    // launches that 64 x 64 tiles cannot fill the chip with: 32 x 64 tiles on the 16 x 16 x 4 MFMA (linear_s16_kernel)
+    if (use_s16_tiles(n, out_dim, in_dim))
+        return launch_s16(x, W, b, bn_scale, bn_shift, relu, y, n, out_dim, in_dim, false, stream);
+    return with_tile(forward_tile_shape(n, out_dim),
+                     [&](auto tile) { return launch_linear(tile, x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream); });
 }
 
 // dW = dY^T X contracts over the batch: a [out][in] output of a narrow layer is a handful of tiles, each a serial
@@ -1852,14 +1946,17 @@ static int gemm_kmajor(const float *A, const float *B, int64_t M, int N, int K, 
 // ordered sum of S fma chains, S = lcrec_linear_backward_splits(n, in_dim, out_dim).
 int linear_backward_splits(int64_t n, int in_dim, int out_dim)
 {
-    static const int cap = [] { const char *e = getenv("LCREC_GEMM_SPLITK"); return e ? atoi(e) : 16; }();
-    const int shape = kmajor_shape(out_dim, in_dim);
-    const int bm = shape == 0 ? 64 : 128, bn = shape == 0 ? 64 : shape == 1 ? 128 : shape == 2 ? 64 : 32;
-    const int64_t tiles = ((out_dim + bm - 1) / bm) * (int64_t)((in_dim + bn - 1) / bn);
+    const TileShape shape = forward_tile_shape(out_dim, in_dim);
+    TileDims t = tile_dims(shape);
+    // The one exception to the table: a 64 x 128 launch is counted as 128 x 32 tiles, as it was before that shape existed.
+    // S is part of lcrec_linear_backward's arithmetic contract: counting the real tiles would change S for some layers,
+    // and a changed S changes the bits of gw.
+    if (shape == TILE_64x128) t = TileDims{128, 32};
+    const int64_t tiles = ((out_dim + t.bm - 1) / t.bm) * (int64_t)((in_dim + t.bn - 1) / t.bn);
     const int64_t nk = (n + BK - 1) / BK;
     int64_t s = 512 / (tiles > 0 ? tiles : 1);
     if (s > nk / 4) s = nk / 4;
-    if (s > cap) s = cap;
+    if (s > knobs().splitk) s = knobs().splitk;
     if (s < 2) return 1;
     const int64_t per = (nk + s - 1) / s;          // K-tiles per run; the count returned has no empty run
     return (int)((nk + per - 1) / per);
@@ -1887,7 +1984,9 @@ int linear_backward(const float *gy, const float *x, const float *W, int64_t n, 
     if (gx) {
         // dX [n][in] = dY [n][out] * W [out][in]: A row-major (K = out), B = W as it is stored
         if (out_dim % BK != 0) return fail(LCREC_EUNSUPPORTED, "linear_backward: out_dim=%d is not a multiple of 32", out_dim);
-        int rc = gemm_kmajor<false>(gy, W, n, in_dim, out_dim, gx, 1, nullptr, stream);
+        int rc = use_s16_tiles(n, in_dim, out_dim)             // an under-filled launch: the 32 x 64 tiles
+                     ? launch_s16(gy, W, nullptr, nullptr, nullptr, 0, gx, n, in_dim, out_dim, true, stream)
+                     : with_tile(forward_tile_shape(n, in_dim), [&](auto tile) { return launch_kmajor<false>(tile, gy, W, n, in_dim, out_dim, gx, 1, nullptr, stream); });
         if (rc) return rc;
     }
     if (gw) {
@@ -1896,7 +1995,9 @@ int linear_backward(const float *gy, const float *x, const float *W, int64_t n, 
         const size_t need = linear_backward_workspace(n, in_dim, out_dim);
         if (splits > 1 && (!workspace || workspace_bytes < need))
             return fail(LCREC_EWORKSPACE, "linear_backward: workspace %zu B < required %zu B", workspace_bytes, need);
-        int rc = gemm_kmajor<true>(gy, x, out_dim, in_dim, (int)n, gw, splits, reinterpret_cast<float *>(workspace), stream);
+        int rc = with_tile(forward_tile_shape(out_dim, in_dim), [&](auto tile) {
+            return launch_kmajor<true>(tile, gy, x, out_dim, in_dim, (int)n, gw, splits, reinterpret_cast<float *>(workspace), stream);
+        });
         if (rc) return rc;
     }
     return LCREC_OK;
@@ -1931,9 +2032,9 @@ int linear_backward_weights(const lcrec_dw_problem *pr, int count, void *workspa
     if (count == 0) return LCREC_OK;
     if (!pr || count < 0 || count > DW_GROUP_MAX)
         return fail(LCREC_EINVAL, "linear_backward_weights: %d problems (1..%d supported)", count, DW_GROUP_MAX);
-    if (workspace_bytes < linear_backward_weights_workspace(pr, count) || (!workspace && linear_backward_weights_workspace(pr, count)))
-        return fail(LCREC_EWORKSPACE, "linear_backward_weights: workspace %zu B < required %zu B", workspace_bytes,
-                    linear_backward_weights_workspace(pr, count));
+    const size_t need = linear_backward_weights_workspace(pr, count);
+    if (workspace_bytes < need || (!workspace && need))
+        return fail(LCREC_EWORKSPACE, "linear_backward_weights: workspace %zu B < required %zu B", workspace_bytes, need);
     DwGroup g = {};
     DwReduce r = {};
     char *ws = reinterpret_cast<char *>(workspace);
@@ -1952,9 +2053,8 @@ int linear_backward_weights(const lcrec_dw_problem *pr, int count, void *workspa
             return fail(LCREC_EUNSUPPORTED, "linear_backward_weights: problem %d exceeds the 2 GiB a buffer descriptor spans", i);
         const int splits = dw_problem_splits(q);
         const int nk = (int)((q.n + BK - 1) / BK);
-        const int64_t bm_blocks = (q.out_dim + 63) / 64;
-        const int bn_blocks = (q.in_dim + 63) / 64;
-        const int64_t tiles = ((bm_blocks + 7) / 8) * 8 * bn_blocks;      // XCD-aware numbering has holes (see linear_tile_body)
+        TileGrid tg;                                                      // 64 x 64 tiles for every problem
+        if (int rc = tile_grid(tg, "linear_backward_weights", q.out_dim, q.in_dim, 64, 64, XCD_ORDER)) return rc;
         g.A[i] = q.gy; g.B[i] = q.x;
         if ((q.x_scale == nullptr) != (q.x_shift == nullptr)) return fail(LCREC_EINVAL, "linear_backward_weights: problem %d: x_scale and x_shift go together", i);
         if (((uintptr_t)q.x_scale | (uintptr_t)q.x_shift) & 15) return fail(LCREC_EINVAL, "linear_backward_weights: x_scale / x_shift must be 16-byte aligned");
@@ -1962,10 +2062,10 @@ int linear_backward_weights(const lcrec_dw_problem *pr, int count, void *workspa
         g.lo[i] = (q.x_scale && q.x_relu) ? 0.0f : -__builtin_inff();
         any_pro = any_pro || q.x_scale != nullptr;
         g.M[i] = q.out_dim; g.N[i] = q.in_dim; g.K[i] = (int)q.n;
-        g.bn_blocks[i] = bn_blocks; g.bm_blocks[i] = (int)bm_blocks; g.tiles[i] = (int)tiles;
+        g.bn_blocks[i] = tg.bn_blocks; g.bm_blocks[i] = (int)tg.bm_blocks; g.tiles[i] = (int)tg.grid;
         g.kt_per_split[i] = splits > 1 ? (nk + splits - 1) / splits : 1 << 30;
         g.wg_start[i] = wg;
-        wg += (unsigned)(tiles * (splits > 1 ? splits : 1));
+        wg += tg.grid * (unsigned)(splits > 1 ? splits : 1);
         if (splits > 1) {
             float *partial = reinterpret_cast<float *>(ws);
             ws += align_up(dw_problem_workspace(q), 256);
@@ -1983,43 +2083,17 @@ int linear_backward_weights(const lcrec_dw_problem *pr, int count, void *workspa
     g.wg_start[count] = wg;
     r.wg_start[r.count] = rwg;
     TraceScope trace(K_LINEAR_64x64, stream);
-    if (any_pro) hipLaunchKernelGGL(linear_dw_grouped_kernel<true>, dim3(wg), dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL(linear_dw_grouped_kernel<false>, dim3(wg), dim3(256), 0, stream, g);
+    hipLaunchKernelGGL(any_pro ? linear_dw_grouped_kernel<true> : linear_dw_grouped_kernel<false>, dim3(wg), dim3(256), 0, stream, g);
     if (r.count) hipLaunchKernelGGL(splitk_reduce_grouped_kernel, dim3(rwg), dim3(256), 0, stream, r);
     return check_launch("linear_dw_grouped_kernel");
 }
 
 // ---- lcrec_linear_bn_forward: the training step's Linear with its input's BatchNorm + ReLU folded into the operand staging
 // and its output's batch statistics taken in the epilogue (TileExtras)
-static int train_tile_shape(int64_t n, int out_dim)
-{
-    if (out_dim > 64) return wide_tiles_fill(n, out_dim) ? 4 : 0;       // 64 x 128 : 64 x 64
-    return out_dim > 32 ? 0 : 3;                                        // 64 x 64 : 128 x 32
-}
-
 size_t linear_bn_forward_workspace(int64_t n, int out_dim)
 {
-    const int bm = train_tile_shape(n, out_dim) == 3 ? 128 : 64;
+    const int bm = tile_dims(train_tile_shape(n, out_dim)).bm;
     return (size_t)((n + bm - 1) / bm) * 3 * (size_t)out_dim * sizeof(float);
-}
-
-template <int WAVES_M, int WAVES_N, int TM, int TN>
-static int launch_train_fwd(const float *x, int64_t n, int in_dim, const float *W, const float *b, int out_dim, float *t,
-                            bool pro, bool stats, const TileExtras &ex, hipStream_t stream)
-{
-    constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
-    const int64_t bm_blocks = (n + BM - 1) / BM;
-    const int bn_blocks = (out_dim + BN - 1) / BN;
-    const int64_t grid = ((bm_blocks + 7) / 8) * 8 * bn_blocks;
-    TraceScope trace(BM == 64 ? K_LINEAR_64x64 : K_LINEAR_128x32, stream);
-#define LCREC_TRAIN_LAUNCH(P, S)                                                                                                  \
-    hipLaunchKernelGGL((linear_train_fwd_kernel<WAVES_M, WAVES_N, TM, TN, P, S>), dim3((unsigned)grid), dim3(256), 0, stream, x, W, b, t, \
-                       n, out_dim, in_dim, bn_blocks, (int)bm_blocks, 1, ex)
-    if (pro && stats) LCREC_TRAIN_LAUNCH(1, true);
-    else if (pro) LCREC_TRAIN_LAUNCH(1, false);
-    else LCREC_TRAIN_LAUNCH(0, true);
-#undef LCREC_TRAIN_LAUNCH
-    return check_launch("linear_train_fwd_kernel");
 }
 
 int linear_bn_forward(const float *x, int64_t n, int in_dim, const float *in_scale, const float *in_shift, int in_relu,
@@ -2051,82 +2125,12 @@ int linear_bn_forward(const float *x, int64_t n, int in_dim, const float *in_sca
     ex.gamma = gamma; ex.beta = beta; ex.eps = eps; ex.momentum = momentum;
     ex.running_mean = running_mean; ex.running_var = running_var;
     ex.mean_out = mean_out; ex.rstd_out = rstd_out; ex.scale_out = scale_out; ex.shift_out = shift_out;
-    switch (train_tile_shape(n, out_dim)) {
-    case 4: return launch_train_fwd<2, 2, 1, 2>(x, n, in_dim, W, b, out_dim, t_out, pro, stats, ex, stream);
-    case 3: return launch_train_fwd<4, 1, 1, 1>(x, n, in_dim, W, b, out_dim, t_out, pro, stats, ex, stream);
-    default: return launch_train_fwd<2, 2, 1, 1>(x, n, in_dim, W, b, out_dim, t_out, pro, stats, ex, stream);
-    }
-}
-
-int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const float *b,
-                   const float *bn_scale, const float *bn_shift, int relu, int out_dim, float *y,
-                   hipStream_t stream)
-{
-    if (n == 0) return LCREC_OK;                       // empty batch: nothing to read or write
-    if (!x || !W || !y) return fail(LCREC_EINVAL, "linear_forward: NULL pointer");
-    if (n < 0 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_forward: bad shape");
-    if ((bn_scale == nullptr) != (bn_shift == nullptr))
-        return fail(LCREC_EINVAL, "linear_forward: bn_scale and bn_shift must both be given or both NULL");
-    if (in_dim % 8 != 0)
-        return fail(LCREC_EUNSUPPORTED, "linear_forward: in_dim=%d is not a multiple of 8", in_dim);
-    if (((uintptr_t)x | (uintptr_t)W) & 15)
-        return fail(LCREC_EINVAL, "linear_forward: x and W must be 16-byte aligned");
-    // Wide layers: the ping-pong kernel (one 512-thread workgroup per CU) wins as soon as its 256 x 128 tiles fill
-    // the 256 CUs in whole rounds: at least one round, and either >= 8 rounds or <= 20 % of the last round empty
-    // (measured with tools/pp_sweep.sh: 8 192 x 768->2048 = 512 tiles: 117 vs 89 TFLOP/s; 16 896 x 1024->512 = 264
-    // tiles: 76 vs 83).  Otherwise the 128 x 128 / 64 x 64 kernels (several workgroups per CU, finer tail).
-    // LCREC_GEMM_PP=0/1 forces one or the other (tuning only).
-    static const int pp = [] { const char *e = getenv("LCREC_GEMM_PP"); return e ? atoi(e) : -1; }();
-    static const int pp_tune = [] { const char *e = getenv("LCREC_GEMM_TUNE"); return (e ? atoi(e) : 1) & 1; }();
-    const int64_t pp_tiles = ((n + 255) / 256) * ((out_dim + 127) / 128);
-    const int64_t pp_rounds = (pp_tiles + 255) / 256;
-    const bool pp_fits = pp_tiles >= 256 && (pp_rounds >= 8 || pp_tiles * 5 >= pp_rounds * 256 * 4);
-    const bool pp_ok = in_dim % BK == 0 && (int64_t)in_dim * 4 * 192 < (1ll << 31);     // else the generic kernels
-    // Mid-sized launches (Games: 16 859 rows = 65.9 row panels) leave the last round of 256 x 128 tiles mostly empty --
-    // 1056 tiles are 4.1 rounds, 528 are 2.06 -- and a persistent workgroup's time is its LONGEST tile list.  Rows are
-    // independent, so such a launch is cut at a row-panel boundary: the largest head whose tiles fill whole rounds (or
-    // >= 90 % of the last one) goes to the ping-pong kernel, the tail (here 475 rows) to the generic kernels in a second
-    // launch.  Same chains, same bits.  Launches of >= 8 rounds are left alone (their partial round is noise).
-    const int64_t pp_last = pp_tiles % 256;
-    if (out_dim > 64 && pp_ok && pp == -1 && pp_rounds < 8 && pp_last != 0 && pp_last * 10 < 256 * 9) {
-        const int64_t ntile = (out_dim + 127) / 128;
-        // (the tail stays below one round of tiles: look back at most 256 / ntile panels)
-        for (int64_t p = n / 256; p >= 1 && p * ntile >= 256 && p >= n / 256 - 256 / ntile; --p) {
-            const int64_t t = p * ntile, last = t % 256;
-            if (last == 0 || last * 10 >= 256 * 9) {
-                const int64_t head = p * 256;
-                if (head >= n) break;                     // the whole launch is already whole rounds
-                int rc = launch_linear_pp(x, head, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, pp_tune, stream);
-                if (rc) return rc;
-                return linear_forward(x + head * in_dim, n - head, in_dim, W, b, bn_scale, bn_shift, relu, out_dim,
-                                      y + head * out_dim, stream);
-            }
-        }
-    }
-    const bool use_pp = out_dim > 64 && pp_ok && (pp == 1 || (pp == -1 && pp_fits));
-    if (use_pp) return launch_linear_pp(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, pp_tune, stream);
-    // launches that 64 x 64 tiles cannot fill the chip with: 32 x 64 tiles on the 16 x 16 x 4 MFMA (linear_s16_kernel)
-    if (use_s16_tiles(n, out_dim, in_dim))
-        return launch_s16(x, W, b, bn_scale, bn_shift, relu, y, n, out_dim, in_dim, false, stream);
-    if (out_dim > 64) {
-        // batch-sized problems (a training step has 1-2 k rows): 128 x 128 tiles would leave most CUs idle,
-        // so launches with fewer than two tiles per CU use 64 x 64 tiles (4x the workgroups)
-        const int64_t tiles128 = ((n + 127) / 128) * ((out_dim + 127) / 128);
-        static const int small_tile = [] { const char *e = getenv("LCREC_GEMM_SMALL"); return e ? atoi(e) : 0; }();   // tuning only
-        if (tiles128 < 512 && small_tile == 1) return launch_linear<2, 2, 1, 2>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-        if (tiles128 < 512 && small_tile == 2) return launch_linear<2, 2, 2, 1>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-        // ... and 64 x 128 tiles (two accumulators per wave: a K-tile's fixed costs are paid once per 32 MFMAs instead of 16)
-        // when those still fill the chip: 768 -> 2048 at batch 2048 72 -> 62 us, 4096 -> 2048 at batch 1024 148 -> 144 us
-        if (tiles128 < 512 && small_tile == 0 && wide_tiles_fill(n, out_dim))
-            return launch_linear<2, 2, 1, 2>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-        if (tiles128 < 512) return launch_linear<2, 2, 1, 1>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-        return launch_linear<2, 2, 2, 2>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-    }
-    // 33 .. 64 columns: 128 x 64 tiles, or 64 x 64 while those would not give every CU one (a batch-sized launch: twice the
-    // workgroups, and the register-buffered K-tile: 128 -> 64 at batch 1024 9.0 -> ~5 us)
-    if (out_dim > 32 && (n + 127) / 128 < 256) return launch_linear<2, 2, 1, 1>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-    if (out_dim > 32) return launch_linear<4, 1, 1, 2>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-    return launch_linear<4, 1, 1, 1>(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
+    return with_tile(train_tile_shape(n, out_dim), [&](auto tile) -> int {
+        if constexpr (decltype(tile)::BM == 128 && decltype(tile)::BN > 32)       // never chosen: no training kernel is built for these
+            return fail(LCREC_EUNSUPPORTED, "linear_bn_forward: no kernel for %d x %d tiles", decltype(tile)::BM, decltype(tile)::BN);
+        else
+            return launch_train_fwd(tile, x, n, in_dim, W, b, out_dim, t_out, pro, stats, ex, stream);
+    });
 }
 
 }  // namespace lcrec

@@ -50,6 +50,7 @@ it), the step is the device step counter the optimiser kernel advances, position
 skipped for a NaN loss leaves the counter where it was, so the next step would repeat its masks: the NaN flag is sticky
 and the epoch raises, so no such step's result is ever used.  The autograd path keeps torch's nn.Dropout.
 """
+import gc
 import os
 
 import torch
@@ -363,13 +364,7 @@ class TrainEngine:
                 dt, _ = ops.relu_bias_backward(g, y, relu, dbias_out=gv[lin.bias], inplace=True)
             dw.append((dt, h, gv[lin.weight]) if in_fold is None else (dt, h, gv[lin.weight], in_fold))
             if i > 0 or need_input_grad:
-                w = lin.weight.data
-                pad = (-w.shape[0]) % 32                # layers._LinearAct.backward: K slice of the k-major dX kernel
-                if pad:
-                    g = ops.linear_backward(torch.nn.functional.pad(dt, (0, pad)), h, torch.nn.functional.pad(w, (0, 0, 0, pad)),
-                                            True, False)[0]
-                else:
-                    g = ops.linear_backward(dt, h, w, True, False)[0]
+                g = ops.linear_backward(dt, h, lin.weight.data, True, False)[0]
                 if drop is not None:                     # d (mask * x * s) / d x: the forward's call, on the gradient
                     g = ops.dropout_apply(g, drop[0], self.dropout_seed, self.step_count, drop[1] + i, out=g)
             else:
@@ -526,6 +521,10 @@ class TrainEngine:
                 self._run(batch.contiguous(), eager=True)
             self._seen[rows] = done + 1
             return
+        # An engine that is no longer used is cyclic garbage (the state_dict hooks above hold it), and so are its graphs.
+        # Destroying a graph synchronises the device, which is an error inside a capture, raised in a destructor: it ends the
+        # process.  torch.cuda.graph no longer collects before it captures, so the collector may not find them in there.
+        gc.collect()
         static = batch.clone()
         graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(self.device)

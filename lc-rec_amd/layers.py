@@ -14,7 +14,6 @@ runs is different:
 """
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 from torch.nn.init import xavier_normal_
 
 from . import dist as ldist
@@ -92,37 +91,29 @@ def _own_batchnorm(bn, x):
     return covered and x.shape[0] >= 2 and torch.is_grad_enabled()
 
 
+def _linear_act_backward(gy, x, weight, y, need_gx, need_gw, need_gb):
+    """(gx, gw, gb) of y = [relu](x W^T + b) for a contiguous gy; y is the saved output when there was a ReLU, else None.
+    Both products read gy, x and W as they are stored (k-major operand staging in the kernel), for any batch size."""
+    if y is not None:
+        gy = torch.ops.aten.threshold_backward(gy, y, 0.0)
+    gb = gy.sum(0) if need_gb else None
+    gx, gw = ops.linear_backward(gy, x, weight, need_gx, need_gw)
+    return gx, gw, gb
+
+
 class _LinearAct(torch.autograd.Function):
     """y = [relu](x W^T + b) with the HIP GEMM in all three products."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
         y = ops.linear_forward(x, weight, bias, relu=relu)
-        ctx.relu = relu
         ctx.save_for_backward(x, weight, y if relu else None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, weight, y = ctx.saved_tensors
-        gy = gy.contiguous()
-        if ctx.relu:
-            gy = torch.ops.aten.threshold_backward(gy, y, 0.0)
-        gx = gw = gb = None
-        out_dim, in_dim = weight.shape
-        if ctx.needs_input_grad[2]:
-            gb = gy.sum(0)
-        # both products read gy, x and W as they are stored (k-major operand staging in the kernel), for any
-        # batch size.  A narrow layer whose width is not a multiple of the K slice (e_dim 16, say) is padded
-        # with zero columns / rows first: fma(0, w, acc) adds nothing, and the copies are a few KB.
-        pad = (-out_dim) % 32
-        if pad:
-            gy = F.pad(gy, (0, pad))
-            weight = F.pad(weight, (0, 0, 0, pad))
-        gx, gw = ops.linear_backward(gy, x, weight, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        if pad and gw is not None:
-            gw = gw[:out_dim]
-        return gx, gw, gb, None
+        return (*_linear_act_backward(gy.contiguous(), x, weight, y, *ctx.needs_input_grad[:3]), None)
 
 
 class _MlpChain(torch.autograd.Function):
@@ -139,33 +130,19 @@ class _MlpChain(torch.autograd.Function):
             y = ops.linear_forward(h, w, b, relu=relu)
             saved += [h, w, y if relu else None]
             h = y
-        ctx.relus = relus
         ctx.save_for_backward(*saved)
         return h
 
     @staticmethod
     def backward(ctx, gy):
         saved = ctx.saved_tensors
-        L = len(ctx.relus)
-        grads = [None] * (2 * L)
+        need = ctx.needs_input_grad
+        grads = [None] * (len(saved) // 3 * 2)
         g = gy.contiguous()
-        for l in range(L - 1, -1, -1):
-            x, weight, y = saved[3 * l], saved[3 * l + 1], saved[3 * l + 2]
-            if ctx.relus[l]:
-                g = torch.ops.aten.threshold_backward(g, y, 0.0)
-            if ctx.needs_input_grad[2 + 2 * l + 1]:
-                grads[2 * l + 1] = g.sum(0)
-            out_dim = weight.shape[0]
-            pad = (-out_dim) % 32                      # see _LinearAct.backward
-            if pad:
-                g = F.pad(g, (0, pad))
-                weight = F.pad(weight, (0, 0, 0, pad))
-            need_gx = l > 0 or ctx.needs_input_grad[0]
-            gx, gw = ops.linear_backward(g, x, weight, need_gx, ctx.needs_input_grad[2 + 2 * l])
-            if gw is not None:
-                grads[2 * l] = gw[:out_dim] if pad else gw
-            g = gx
-        return (g if ctx.needs_input_grad[0] else None, None, *grads)
+        for l in range(len(saved) // 3 - 1, -1, -1):
+            x, weight, y = saved[3 * l:3 * l + 3]
+            g, grads[2 * l], grads[2 * l + 1] = _linear_act_backward(g, x, weight, y, l > 0 or need[0], need[2 + 2 * l], need[3 + 2 * l])
+        return (g, None, *grads)
 
 
 def fold_batchnorm(bn):

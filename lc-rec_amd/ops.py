@@ -235,13 +235,23 @@ def linear_backward(gy, x, weight, need_gx=True, need_gw=True, gw_out=None):
     lcrec_linear_backward): gx = gy W, gw = gy^T x, every operand read as stored.  Raises
     LcrecError(LCREC_EUNSUPPORTED) for shapes the k-major kernels do not cover.
     gw_out: optional contiguous [out_dim, in_dim] tensor the weight gradient is written into (a view of a flat
-    gradient buffer)."""
+    gradient buffer).
+    The dX kernel slices K = out_dim in steps of 32: for a layer whose width is not a multiple of that (e_dim 16, say),
+    gy gets zero columns and weight zero rows up to the next multiple first -- fma(0, w, acc) adds nothing, the copies are
+    a few KB -- and gw is the first out_dim rows of the padded product (the same bits: dW contracts over the batch)."""
     lib = _lib.load()
     gy, x, weight = _dev(gy, "gy"), _dev(x, "x"), _dev(weight, "weight")
     n, out_dim = gy.shape
     in_dim = x.shape[1]
     if x.shape[0] != n or tuple(weight.shape) != (out_dim, in_dim):
         raise _lib.LcrecError(f"linear_backward: shapes gy {tuple(gy.shape)}, x {tuple(x.shape)}, W {tuple(weight.shape)}")
+    pad = (-out_dim) % 32 if need_gx else 0
+    if pad:
+        gx, gw = linear_backward(torch.nn.functional.pad(gy, (0, pad)), x, torch.nn.functional.pad(weight, (0, 0, 0, pad)), True, need_gw)
+        if gw is not None and gw_out is not None:
+            gw_out.copy_(gw[:out_dim])
+            return gx, gw_out
+        return gx, None if gw is None else gw[:out_dim]
     gx = torch.empty((n, in_dim), dtype=torch.float32, device=gy.device) if need_gx else None
     gw = None
     if need_gw:

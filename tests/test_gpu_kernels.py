@@ -83,6 +83,99 @@ def test_linear_backward_bit_exact(hip, oracle, n, k, out):
     assert only_gw[0] is None and torch.equal(only_gw[1], gw)
 
 
+def _launches(trace):
+    return {name: launches for name, (launches, _) in trace.items()}
+
+
+@pytest.mark.parametrize("n,k,out,labels", [
+    # (expected by hand from the dispatch rule of csrc/gemm_f32.hip; K = 72 / 40 keeps a launch off the ping-pong kernel and the
+    # 32 x 64 tiles, which both need K % 32 == 0, so that the table of the generic kernel decides)
+    (64, 64, 32, {"linear_fwd_32x64": 1}),             # one 64 x 64 tile <= 128: the 32 x 64 tiles
+    (64, 72, 32, {"linear_fwd_128x32": 1}),            # up to 32 columns
+    (64, 72, 64, {"linear_fwd_64x64": 1}),             # 33 .. 64 columns, fewer than 256 row panels of 128
+    (32768, 40, 64, {"linear_fwd_128x64": 1}),         # ... 256 row panels
+    (1024, 72, 128, {"linear_fwd_64x64": 1}),          # wide, 8 tiles of 128 x 128 (< 512), 16 of 64 x 128 (< 256): 64 x 64
+    (8192, 72, 1024, {"linear_fwd_128x128": 1}),       # 64 x 8 = 512 tiles of 128 x 128
+    (4096, 64, 2048, {"linear_fwd_pp_256x128": 1}),    # 16 x 16 = 256 tiles of 256 x 128: exactly one round
+    # 66 x 4 = 264 tiles = one round + 8: cut after 64 row panels (16 384 rows, one whole round); the 475-row tail is 8 x 8 tiles of 64 x 64
+    (16859, 64, 512, {"linear_fwd_pp_256x128": 1, "linear_fwd_32x64": 1}),
+])
+def test_linear_forward_dispatch_boundaries(hip, oracle, n, k, out, labels):
+    """Which kernel lcrec_linear_forward launches on either side of every threshold of its dispatch rule, read from the
+    launch trace -- and that kernel's values against the oracle, bit for bit."""
+    rs = _rs(n + k + out)
+    x = rs.standard_normal((n, k)).astype(np.float32)
+    W = (rs.standard_normal((out, k)) / np.sqrt(k)).astype(np.float32)
+    b = (0.1 * rs.standard_normal(out)).astype(np.float32)
+    want = oracle.linear(x, W, b, None, None, relu=True, threads=8)
+    t = lambda a: torch.from_numpy(a).to(torch.device("cuda:0"))
+    hip.ops.trace_enable(True)
+    got = hip.ops.linear_forward(t(x), t(W), t(b), relu=True).cpu().numpy()
+    trace = hip.ops.trace_collect()
+    hip.ops.trace_enable(False)
+    assert _launches(trace) == labels, trace
+    assert np.array_equal(got, want), f"max abs diff {np.abs(got - want).max()}"
+
+
+@pytest.mark.parametrize("n,k,out,splits,labels", [
+    # dX [64][64] over K = 32 is one 64 x 64 tile: the 32 x 64 tiles; dW [32][64]: 64 x 64 tiles, 2 K-tiles: one run
+    (64, 64, 32, 1, {"linear_fwd_32x64": 1, "linear_fwd_64x64": 1}),
+    # out = 40 is padded to 64 for dX [4096][200]: 64 x 4 = 256 tiles of 64 x 64 (> 128), 32 x 2 of 128 x 128, 64 x 2 of 64 x 128
+    # (< 256): 64 x 64; dW [64][200]: 4 tiles of 64 x 64, 128 K-tiles: min(512 / 4, 128 / 4, 16) = 16 runs
+    (4096, 200, 40, 16, {"linear_fwd_64x64": 2}),
+    # dX [2048][64] over K = 32: 32 tiles: the 32 x 64 tiles; dW [32][64]: one tile, 64 K-tiles: min(512, 16, 16) = 16 runs
+    (2048, 64, 32, 16, {"linear_fwd_32x64": 1, "linear_fwd_64x64": 1}),
+])
+def test_linear_backward_dispatch(hip, oracle, n, k, out, splits, labels):
+    """The launches of lcrec_linear_backward from the trace (a dX on the 32 x 64 tiles, a layer whose width ops.linear_backward
+    pads to the K slice of the dX kernel, a weight gradient summed from S > 1 runs) and their values against the oracle."""
+    rs = _rs(n * 3 + k + out)
+    x = rs.standard_normal((n, k)).astype(np.float32)
+    W = (rs.standard_normal((out, k)) / np.sqrt(k)).astype(np.float32)
+    gy = rs.standard_normal((n, out)).astype(np.float32)
+    gy[rs.random_sample(gy.shape) < 0.4] = 0.0                    # as after a ReLU mask
+    assert hip.ops.linear_backward_splits(n, k, out) == splits
+    want_gx, want_gw = oracle.linear_backward(gy, x, W, splits=splits, threads=8)
+    t = lambda a: torch.from_numpy(a).to(torch.device("cuda:0"))
+    gy_d, x_d, W_d = t(gy), t(x), t(W)
+    hip.ops.trace_enable(True)
+    gx, gw = hip.ops.linear_backward(gy_d, x_d, W_d)
+    trace = hip.ops.trace_collect()
+    hip.ops.trace_enable(False)
+    assert _launches(trace) == labels, trace
+    assert np.array_equal(gx.cpu().numpy(), want_gx), f"gx max abs diff {np.abs(gx.cpu().numpy() - want_gx).max()}"
+    assert np.array_equal(gw.cpu().numpy(), want_gw), f"gw max abs diff {np.abs(gw.cpu().numpy() - want_gw).max()}"
+
+
+def test_linear_backward_pads_narrow_layers_itself(hip):
+    """ops.linear_backward zero-pads a layer whose width is not a multiple of 32 for the dX product only.  The weight gradient
+    has the same bits with and without the padding (it contracts over the batch; tiles, tile shape and S do not change up to
+    the next multiple of 32), and both equal what the call sites computed when they padded the operands themselves."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(40)
+    pad = torch.nn.functional.pad
+    n, split = 2048, []
+    for out in (40, 72):
+        for k in (72, 200):
+            gy = torch.randn((n, out), generator=g, device=dev)
+            gy[torch.rand((n, out), generator=g, device=dev) < 0.4] = 0.0
+            x = torch.randn((n, k), generator=g, device=dev)
+            W = torch.randn((out, k), generator=g, device=dev)
+            split.append(hip.ops.linear_backward_splits(n, k, out))
+            _, gw_only = hip.ops.linear_backward(gy, x, W, need_gx=False)
+            gx, gw = hip.ops.linear_backward(gy, x, W, need_gx=True)
+            p = (-out) % 32
+            gx_hand, gw_hand = hip.ops.linear_backward(pad(gy, (0, p)), x, pad(W, (0, 0, 0, p)))
+            assert tuple(gw.shape) == (out, k) and tuple(gw_hand.shape) == (out + p, k)
+            assert torch.equal(gw_only, gw) and torch.equal(gw, gw_hand[:out]) and torch.equal(gx, gx_hand), (out, k)
+            assert not gw_hand[out:].any()
+            for need_gx in (False, True):                          # gw_out: the result lands in the caller's tensor
+                into = torch.full((out, k), float("nan"), device=dev)
+                res = hip.ops.linear_backward(gy, x, W, need_gx=need_gx, gw_out=into)
+                assert res[1] is into and torch.equal(into, gw) and (res[0] is None or torch.equal(res[0], gx))
+    assert max(split) > 1, split
+
+
 @pytest.mark.parametrize("n,e,Ks", [(1024, 32, [256] * 4), (475, 16, [32, 256, 7]), (2048, 32, [1024] * 8), (9000, 32, [64, 64])])
 def test_code_stats_levels_equal_per_level_calls(hip, oracle, n, e, Ks):
     """lcrec_code_stats_levels: (count, sum) of every level and the fused codebook gradient in one launch -- the same bits as

@@ -507,6 +507,18 @@ int lcrec_dropout_apply(const float *in, float *out, int64_t n, int features, ui
 int lcrec_dropout_mask(unsigned char *keep_out, int64_t n, int features, uint32_t T, const int64_t *seed, const int64_t *step,
                        int position, int64_t row_offset, void *stream);
 
+/* Embedding files that are not fp32 (the reference takes any float dtype: index/datasets.py:12-18, np.load then
+ * torch.FloatTensor): the file's bytes are copied to HBM as they are and converted there, instead of on host threads.
+ * dst[i] = (float)src[i] for i < count: fp16 -> fp32 exact, fp64 -> fp32 round-to-nearest-even
+ * (overflow -> +-inf, fp32 subnormal results kept, not flushed; NaN stays NaN) -- numpy's astype(float32), bit for bit.
+ * Device pointers; src aligned to its element size, dst to 4 bytes -- nothing more is required; src and dst do not overlap.
+ * When src and dst reach 16-byte alignment after the same number of leading elements the launch moves 16 bytes per access,
+ * otherwise one element per access.
+ * count >= 0 (0: no launch).  Enqueued on `stream`, no synchronisation, no allocation, capturable. */
+#define LCREC_DTYPE_F16 1
+#define LCREC_DTYPE_F64 2
+int lcrec_cast_rows(const void *src, int src_dtype, int64_t count, float *dst, void *hip_stream);
+
 /* Which items share an identical index tuple.  Replaces the Python string-set / dict passes of
  * index/trainer.py:139-150 (collision rate) and index/generate_indices.py:18-42
  * (check_collision, get_indices_count, get_collision_item), keeping get_collision_item's order:

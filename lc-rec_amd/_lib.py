@@ -102,6 +102,7 @@ _SIGNATURES = {
     "lcrec_dropout_apply": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, _vp, _vp, ctypes.c_int,
                                            ctypes.c_int64, _vp]),
     "lcrec_dropout_mask": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.c_int, ctypes.c_int64, _vp]),
+    "lcrec_cast_rows": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
     "lcrec_collision_groups_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "lcrec_collision_groups": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp,
                                               _vp, _vp, _vp, ctypes.c_size_t, _vp]),

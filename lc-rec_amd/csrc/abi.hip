@@ -28,7 +28,7 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "collision_groups", "linear_fwd_pp_256x128", "linear_fwd_64x64", "sinkhorn_slab",
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
-                                           "optim_step", "dropout"};
+                                           "optim_step", "dropout", "cast_rows"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -473,6 +473,11 @@ LCREC_API int lcrec_dropout_mask(unsigned char *keep_out, int64_t n, int feature
                                  int position, int64_t row_offset, void *stream)
 {
     return dropout_mask(keep_out, n, features, T, seed, step, position, row_offset, (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_cast_rows(const void *src, int src_dtype, int64_t count, float *dst, void *stream)
+{
+    return cast_rows(src, src_dtype, count, dst, (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_codebook_grad(const float *count, const float *sum, const float *codebook, int K, int e, float scale,

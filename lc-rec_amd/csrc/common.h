@@ -31,7 +31,7 @@ inline int check_launch(const char *what)
 enum KernelId { K_LINEAR_128x128 = 0, K_LINEAR_128x64, K_LINEAR_128x32, K_RQ_ASSIGN, K_RQ_SSE_FINALIZE,
                 K_VQ_DISTANCE, K_SINKHORN, K_SINKHORN_SMALL, K_APPLY_LEVEL, K_CODE_STATS, K_EMA_UPDATE, K_COLLISION,
                 K_LINEAR_PP, K_LINEAR_64x64, K_SINKHORN_SLAB, K_SINKHORN_TINY, K_BN_FWD, K_BN_BWD, K_RELU_BIAS_BWD, K_LOSS,
-                K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_COUNT };
+                K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_COUNT };
 extern const char *const kKernelNames[K_COUNT];
 bool trace_on();
 void trace_begin(int kernel, hipStream_t stream);
@@ -269,6 +269,7 @@ int dropout_apply(const float *in, float *out, int64_t n, int F, uint32_t T, flo
                   int position, int64_t row_offset, hipStream_t stream);
 int dropout_mask(unsigned char *keep_out, int64_t n, int F, uint32_t T, const int64_t *seed, const int64_t *step, int position,
                  int64_t row_offset, hipStream_t stream);
+int cast_rows(const void *src, int src_dtype, int64_t count, float *dst, hipStream_t stream);
 
 // host-side text (index_json.hip)
 int64_t index_json_bound(int64_t n, int L);

@@ -1162,6 +1162,54 @@ __global__ __launch_bounds__(DROP_THREADS) void dropout_kernel(const float *in, 
     }
 }
 
+// ---------------------------------------------------------------- fp16 / fp64 -> fp32 (include/lcrec.h, lcrec_cast_rows)
+// An embedding file that is not fp32 is copied to HBM as it is and widened / narrowed here: dst[i] = (float)src[i], the
+// hardware's own conversions (v_cvt_f32_f16 is exact, v_cvt_f32_f64 rounds to nearest even; fp32 subnormal results are
+// kept -- the library is built without denormal flushing).  HBM-bound: 2 + 4 or 8 + 4 bytes per element, no LDS.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+constexpr int CAST_THREADS = 256;
+
+template <typename SRC> struct CastVec;
+template <> struct CastVec<_Float16> { static constexpr int N = 8; };   // one 16-byte load, two 16-byte stores
+template <> struct CastVec<double> { static constexpr int N = 4; };     // two 16-byte loads, one 16-byte store
+
+__device__ __forceinline__ void cast_vec(const _Float16 *src, float *dst)
+{
+    const f16x8 h = *reinterpret_cast<const f16x8 *>(src);
+    f32x4 lo, hi;
+    lo.x = (float)h[0]; lo.y = (float)h[1]; lo.z = (float)h[2]; lo.w = (float)h[3];
+    hi.x = (float)h[4]; hi.y = (float)h[5]; hi.z = (float)h[6]; hi.w = (float)h[7];
+    reinterpret_cast<f32x4 *>(dst)[0] = lo;
+    reinterpret_cast<f32x4 *>(dst)[1] = hi;
+}
+__device__ __forceinline__ void cast_vec(const double *src, float *dst)
+{
+    const f64x2 a = reinterpret_cast<const f64x2 *>(src)[0], b = reinterpret_cast<const f64x2 *>(src)[1];
+    f32x4 y;
+    y.x = (float)a.x; y.y = (float)a.y; y.z = (float)b.x; y.w = (float)b.y;
+    *reinterpret_cast<f32x4 *>(dst) = y;
+}
+
+// Elements [head, head + nvec * N) go N at a time through 16-byte accesses: the launcher chose `head` so that src + head and
+// dst + head are both 16-byte aligned.  The head and the tail behind the vectors (at most N - 1 elements each) go one element
+// per thread in the same launch.  nvec == 0 and head == 0 is the scalar path: every element is an "end".
+template <typename SRC>
+__global__ __launch_bounds__(CAST_THREADS) void cast_rows_kernel(const SRC *__restrict__ src, float *__restrict__ dst, int64_t count,
+                                                                 int head, int64_t nvec)
+{
+    constexpr int N = CastVec<SRC>::N;
+    const int64_t stride = (int64_t)gridDim.x * CAST_THREADS;
+    const int64_t first = (int64_t)blockIdx.x * CAST_THREADS + threadIdx.x;
+    for (int64_t i = first; i < nvec; i += stride) cast_vec(src + head + i * N, dst + head + i * N);
+    const int64_t body = nvec * N, ends = count - body;
+    for (int64_t i = first; i < ends; i += stride) {
+        const int64_t j = i < head ? i : i + body;
+        dst[j] = (float)src[j];
+    }
+}
+
 // ---------------------------------------------------------------- host side
 
 // strip width by feature count: wide layers read 128-byte row segments; narrow ones take narrower strips so that more
@@ -1527,7 +1575,7 @@ int rmsprop_step(float *p, float *g, float *square_avg, float *buf, float *grad_
     return launch_optim_step<RULE_RMSPROP>(a, "rmsprop_step", K_OPTIM_STEP, stream);
 }
 
-// grid of the dropout kernels: from the device's CU count (a batch's widest activation is 2 M elements = 2 k workgroups of
+// grid of the dropout and cast kernels (one item = one thread's access per trip): from the device's CU count (a batch's widest activation is 2 M elements = 2 k workgroups of
 // one access each; 4 per CU make the same passes with fewer workgroups to dispatch), never more than the work
 static int dropout_grid(int64_t quads)
 {
@@ -1578,6 +1626,39 @@ int dropout_mask(unsigned char *keep_out, int64_t n, int F, uint32_t T, const in
     hipLaunchKernelGGL(dropout_kernel<true>, dim3((unsigned)dropout_grid(quads)), dim3(DROP_THREADS), 0, stream, (const float *)nullptr,
                        (float *)nullptr, keep_out, quads, (uint64_t)row_offset * (uint64_t)(F / 4), T, 1.0f, seed, step, (uint32_t)position);
     return check_launch("dropout_mask kernel");
+}
+
+// The 16-byte path needs src + h and dst + h aligned together for one head h < count.  dst + h is aligned for h = h0, h0 + 4, ...
+// (h0 <= 3) and src + h every 8 halves / 2 doubles, so h0 and h0 + 4 are the only candidates worth a look (fp64: h0 alone).
+template <typename SRC>
+static int launch_cast(const SRC *src, int64_t count, float *dst, hipStream_t stream)
+{
+    constexpr int N = CastVec<SRC>::N;
+    int head = (int)(((16 - ((uintptr_t)dst & 15)) & 15) / 4);
+    if (((uintptr_t)(src + head) & 15) && N == 8) head += 4;
+    const bool fast = !((uintptr_t)(src + head) & 15) && head + N <= count;
+    if (!fast) head = 0;
+    const int64_t nvec = fast ? (count - head) / N : 0;
+    const int64_t ends = count - nvec * N;
+    TraceScope trace(K_CAST, stream);
+    hipLaunchKernelGGL(cast_rows_kernel<SRC>, dim3((unsigned)dropout_grid(nvec > ends ? nvec : ends)), dim3(CAST_THREADS), 0, stream, src,
+                       dst, count, head, nvec);
+    return check_launch("cast_rows kernel");
+}
+
+int cast_rows(const void *src, int src_dtype, int64_t count, float *dst, hipStream_t stream)
+{
+    if (src_dtype != LCREC_DTYPE_F16 && src_dtype != LCREC_DTYPE_F64)
+        return fail(LCREC_EINVAL, "cast_rows: src_dtype %d is neither LCREC_DTYPE_F16 (1) nor LCREC_DTYPE_F64 (2)", src_dtype);
+    if (count < 0) return fail(LCREC_EINVAL, "cast_rows: count %lld must be >= 0", (long long)count);
+    if (count == 0) return LCREC_OK;
+    if (!src) return fail(LCREC_EINVAL, "cast_rows: src is NULL");
+    if (!dst) return fail(LCREC_EINVAL, "cast_rows: dst is NULL");
+    const uintptr_t src_mask = src_dtype == LCREC_DTYPE_F16 ? 1 : 7;
+    if ((uintptr_t)src & src_mask) return fail(LCREC_EINVAL, "cast_rows: src must be aligned to its element size (%d bytes)", (int)src_mask + 1);
+    if ((uintptr_t)dst & 3) return fail(LCREC_EINVAL, "cast_rows: dst must be 4-byte aligned");
+    if (src_dtype == LCREC_DTYPE_F16) return launch_cast(static_cast<const _Float16 *>(src), count, dst, stream);
+    return launch_cast(static_cast<const double *>(src), count, dst, stream);
 }
 
 }  // namespace lcrec

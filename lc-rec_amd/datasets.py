@@ -10,6 +10,8 @@ import numpy as np
 import torch
 import torch.utils.data as data
 
+_CAST_TORCH = {2: torch.float16, 8: torch.float64}       # element size -> staging dtype of to_device's "device" cast
+
 
 class EmbDataset(data.Dataset):
 
@@ -25,7 +27,22 @@ class EmbDataset(data.Dataset):
     def __len__(self):
         return len(self.embeddings)
 
-    def to_device(self, device, chunk_rows=None, rows=None, workers=None, stages=None):
+    def _device_cast_refusal(self, device):
+        """None when the file can be converted in HBM (lcrec_cast_rows), else what stands in the way."""
+        e = self.embeddings
+        if device.type != "cuda":
+            return f"the target {device} is not a HIP device"
+        if e.dtype.kind != "f" or e.dtype.itemsize not in _CAST_TORCH or not e.dtype.isnative:
+            return f"the file's dtype {e.dtype.str} is not native-endian float16 or float64"
+        if e.ndim != 2 or not e.flags.c_contiguous:
+            return f"the file's array (shape {e.shape}) is not a C-contiguous [N, d] matrix"
+        return None
+
+    def casts_on_device(self, device):
+        """Whether to_device(device) -- cast="auto" -- converts this file in HBM rather than in the host threads."""
+        return self._device_cast_refusal(torch.device(device)) is None
+
+    def to_device(self, device, chunk_rows=None, rows=None, workers=None, stages=None, cast="auto"):
         """The matrix (or the item range rows=(lo, hi), one rank's shard) as one fp32 tensor in HBM
         (Games: 16 859 x 4096 = 276 MB; a 288 GB MI355X holds 17 M such rows).  Cast and copied in row
         chunks so a large or memory-mapped file never needs a second full host copy.
@@ -33,8 +50,22 @@ class EmbDataset(data.Dataset):
         On a GPU the chunks (~32 MB) go through a ring of pinned staging buffers: `workers` host threads
         cast/copy chunks into them side by side (numpy releases the GIL for the copy; one thread moves
         ~10 GB/s out of the page cache, the link takes five times that), the calling thread queues the H2D
-        copies in order on a side stream.  Measured: tools/ingest_probe.py, DESIGN.md section 5."""
+        copies in order on a side stream.  Measured: tools/ingest_probe.py, DESIGN.md section 5.
+
+        cast: where a float16 / float64 file becomes fp32.  "host": in the worker threads (numpy), so the link carries
+        fp32.  "device": the staging buffers hold the file's own dtype (the workers' copy is a memcpy), each chunk lands
+        in a raw device buffer and ops.cast_rows converts it into its rows of the result on the side stream -- the same
+        bits; ValueError for a file that is not native-endian C-contiguous float16 / float64, or a target that is not a
+        HIP device.  "auto": "device" where it applies, else "host".  `cast` is checked before the kept copy of the whole
+        matrix is looked up: an explicit "device" that does not apply raises even when a copy is already resident, and a
+        resident copy is returned whichever path made it."""
         device = torch.device(device)
+        if cast not in ("auto", "host", "device"):
+            raise ValueError(f"cast must be 'auto', 'host' or 'device', got {cast!r}")
+        refusal = None if cast == "host" else self._device_cast_refusal(device)
+        if cast == "device" and refusal is not None:
+            raise ValueError(f"EmbDataset.to_device(cast='device'): {refusal}")
+        on_device = cast != "host" and refusal is None
         whole = rows is None
         if whole and self._device_copy is not None and self._device_copy.device == device:
             return self._device_copy
@@ -42,7 +73,11 @@ class EmbDataset(data.Dataset):
         n = last - first
         out = torch.empty((n, self.dim), dtype=torch.float32, device=device)
         if chunk_rows is None:
-            chunk_rows = max(1, (32 << 20) // (4 * max(self.dim, 1)))
+            # ~32 MB of what the staging buffers hold; on the device path a multiple of 4 rows, so that every chunk's rows of
+            # `out` start 16-byte aligned like its raw buffer does, whatever the width (the 16-byte form of lcrec_cast_rows)
+            chunk_rows = max(1, (32 << 20) // ((self.embeddings.dtype.itemsize if on_device else 4) * max(self.dim, 1)))
+            if on_device and chunk_rows > 4:
+                chunk_rows -= chunk_rows % 4
         if device.type != "cuda":
             for lo in range(0, n, chunk_rows):
                 hi = min(n, lo + chunk_rows)
@@ -55,9 +90,17 @@ class EmbDataset(data.Dataset):
             chunks = [(lo, min(n, lo + step)) for lo in range(0, n, step)]
             workers = max(1, min(workers or min(8, os.cpu_count() or 1), len(chunks)))
             ring = max(2, min(stages or 2 * workers, len(chunks)))
-            stage = [torch.empty((step, self.dim), dtype=torch.float32, pin_memory=True) for _ in range(ring)]
+            staged = _CAST_TORCH[self.embeddings.dtype.itemsize] if on_device else torch.float32
+            stage = [torch.empty((step, self.dim), dtype=staged, pin_memory=True) for _ in range(ring)]
             done = [torch.cuda.Event() for _ in range(ring)]
             copier = torch.cuda.Stream(device)
+            raw = None
+            if on_device:
+                from . import ops
+                # one raw device buffer per pinned slot, in the file's dtype; freed when this call returns (by then the side
+                # stream has drained).  The side stream first lets the current one finish with whatever held this memory before.
+                raw = [torch.empty((step, self.dim), dtype=staged, device=device) for _ in range(ring)]
+                copier.wait_stream(torch.cuda.current_stream(device))
             src = self.embeddings
 
             def fill(i, wait):
@@ -72,7 +115,11 @@ class EmbDataset(data.Dataset):
                     for i, (lo, hi) in enumerate(chunks):
                         fills.pop(i).result()
                         with torch.cuda.stream(copier):
-                            out[lo:hi].copy_(stage[i % ring][:hi - lo], non_blocking=True)
+                            if raw is None:
+                                out[lo:hi].copy_(stage[i % ring][:hi - lo], non_blocking=True)
+                            else:                        # (the event below then also covers the raw buffer's reuse)
+                                raw[i % ring][:hi - lo].copy_(stage[i % ring][:hi - lo], non_blocking=True)
+                                ops.cast_rows(raw[i % ring][:hi - lo], out=out[lo:hi])
                             done[i % ring].record(copier)
                         if i + ring < len(chunks):       # its buffer's event is recorded now: safe to hand to a worker
                             fills[i + ring] = pool.submit(fill, i + ring, True)

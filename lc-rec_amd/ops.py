@@ -1032,6 +1032,32 @@ def dropout_mask(shape, p, seed, step, position, row_offset=0, device=None):
     return keep
 
 
+_CAST_DTYPES = {torch.float16: 1, torch.float64: 2}       # LCREC_DTYPE_F16 / LCREC_DTYPE_F64 of include/lcrec.h
+
+
+def cast_rows(src, out=None):
+    """float32 copy of a contiguous float16 / float64 device tensor -- lcrec_cast_rows: what numpy's astype(float32) gives,
+    bit for bit, made in HBM.  out: None (a new tensor of src's shape) or a contiguous float32 tensor on src's device with as
+    many elements, of any shape (a row range `matrix[lo:hi]` of a larger one is fine); src and out must not overlap."""
+    lib = _lib.load()
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise _lib.LcrecError("src must be a tensor on a HIP device (lcrec_amd has no CPU path)")
+    code = _CAST_DTYPES.get(src.dtype)
+    if code is None:
+        raise _lib.LcrecError(f"src must be float16 or float64, got {src.dtype}")
+    if not src.is_contiguous():
+        raise _lib.LcrecError("src must be contiguous")
+    if out is None:
+        out = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    elif not (isinstance(out, torch.Tensor) and out.device == src.device and out.is_contiguous() and out.dtype == torch.float32
+              and out.numel() == src.numel()):
+        raise _lib.LcrecError("out must be a contiguous float32 tensor on src's device with src's number of elements")
+    with _on(src.device):
+        rc = lib.lcrec_cast_rows(_ptr(src), code, src.numel(), _ptr(out), _stream_ptr())
+    _lib.check(rc, "lcrec_cast_rows")
+    return out
+
+
 def trace_enable(on=True):
     """Bracket every kernel launch with hipEvents (include/lcrec.h, lcrec_trace_enable)."""
     _lib.check(_lib.load().lcrec_trace_enable(int(bool(on))), "lcrec_trace_enable")

@@ -1174,6 +1174,8 @@ __global__ __launch_bounds__(512) void linear_fwd_pp2_kernel(
 // Measured on MI355X (131 072 rows, TFLOP/s, this / linear_fwd_pp2_kernel): 768->2048 143 / 140, 2048->1024 151 / 150,
 // 1024->512 146 / 144, 512->256 138 / 134; C3 end to end 16.49 M vs 16.30 M items/s.
 // Same arithmetic as every other kernel here: one fma chain per output over k ascending, epilogue after it.
+// K = 384 is 12 K-tiles: HEAD and TAIL take them all and the STEADY loop is empty; it runs (K / 32 - 12) / 2 times per tile.
+// tests/gemm_pp_cases.py lists the smallest shape that reaches each path (one tile per workgroup, hand-over, ragged panels, ...).
 // ------------------------------------------------------------------------------------------
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
@@ -1685,6 +1687,24 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
     reinterpret_cast<f32x4 *>(out)[q] = acc;
 }
 
+// One launch of lcrec_debug_linear_forward_plan (below; a debug export, so the struct lives here and not in include/lcrec.h).
+}  // namespace lcrec
+extern "C" struct lcrec_debug_forward_launch {
+    int64_t row0, rows;        // the rows of the call this launch covers
+    const char *label;         // its name in the launch trace
+    int form;                  // 0: not a ping-pong launch, 2: per-tile (linear_fwd_pp2_kernel), 3: persistent (linear_fwd_pp3_kernel)
+    int tile_rows, tile_cols;  // the workgroup tile
+    int k_tiles;               // K-tiles of 32 per output tile
+    int tiles, virtual_tiles;  // real tiles, and the numbering's extent (row panels padded to the 8 XCDs: the rest are holes)
+    int workgroups;            // grid size
+    int last_panel_rows;       // valid rows of the last row panel (tile_rows: not ragged)
+    // persistent form only (else 0): STEADY iterations per tile; shortest and longest tile list; workgroups with no tile
+    // and with exactly one; tiles of a ragged last row panel that are NOT the last of their list (their partial row count
+    // goes through the hand-over to the next tile's K loop instead of through finish())
+    int steady_iterations, list_min, list_max, empty_workgroups, single_tile_workgroups, ragged_handed_over;
+};
+namespace lcrec {
+
 // ---- Launch side: which kernel a shape gets.  Top to bottom: knobs, tile table, choosers, grid helper, launches, entry
 // points.  Every kernel gives the same bits for a given product; the one choice that changes bits is S, the K-runs of a
 // weight gradient (linear_backward_splits).  bench.py replays the forward rule (pp_fits, pp_head_rows,
@@ -1823,6 +1843,29 @@ static int launch_s16(const float *A, const float *W, const float *b, const floa
     return check_launch("linear_s16_kernel");
 }
 
+// ---- the ping-pong launch as a pure decision: which form, how many workgroups.  launch_linear_pp() launches what these
+// say and lcrec_debug_linear_forward_plan() reports it; neither restates the other.
+enum PpForm { PP_PER_TILE = 2, PP_PERSISTENT = 3 };      // linear_fwd_pp2_kernel / linear_fwd_pp3_kernel
+// K-tiles of a tile that linear_fwd_pp3_kernel spends outside its STEADY loop: HEAD (0..9) and TAIL (the last two).  At the
+// smallest admitted K (12 K-tiles = 384) the STEADY loop is therefore empty; it runs (K / 32 - 12) / 2 times per tile.
+constexpr int PP3_HEAD_KTILES = 10, PP3_TAIL_KTILES = 2;
+// the persistent form where it applies (measured +1.2 % on C3, +0.5 .. +3.4 % per layer)
+static PpForm pp_form(int in_dim, int out_dim)
+{
+    return knobs().pp3 && in_dim % 64 == 0 && in_dim >= (PP3_HEAD_KTILES + PP3_TAIL_KTILES) * BK && out_dim % 128 == 0 &&
+                   (int64_t)out_dim * 4 * 128 < (1ll << 31)
+               ? PP_PERSISTENT : PP_PER_TILE;
+}
+// the persistent form's workgroup count: one per CU, the CU count rounded down to a multiple of 8 (that keeps a
+// workgroup's tiles on its own XCD), and never more than there are (virtual) tiles -- each workgroup walks total / grid of them
+static int pp3_usable_cus(int device_cus) { return device_cus > 8 ? device_cus / 8 * 8 : 8; }
+static unsigned pp_workgroups(PpForm form, unsigned virtual_tiles, int cus)
+{
+    if (form == PP_PER_TILE) return virtual_tiles;
+    const unsigned usable = (unsigned)pp3_usable_cus(cus);
+    return virtual_tiles < usable ? virtual_tiles : usable;
+}
+
 static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *W, const float *b, const float *sc,
                             const float *sh, int relu, int out_dim, float *y, hipStream_t stream)
 {
@@ -1831,12 +1874,11 @@ static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *
     TileGrid g;
     if (int rc = tile_grid(g, "linear_forward", n, out_dim, 256, 128, XCD_ORDER)) return rc;
     TraceScope trace(K_LINEAR_PP, stream);
-    // the persistent form where it applies (measured +1.2 % on C3, +0.5 .. +3.4 % per layer)
-    if (knobs().pp3 && in_dim % 64 == 0 && in_dim >= 12 * BK && out_dim % 128 == 0 && (int64_t)out_dim * 4 * 128 < (1ll << 31)) {
+    if (pp_form(in_dim, out_dim) == PP_PERSISTENT) {
         static const int cus = [] {
             int dev = 0, v = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
-            return v > 8 ? v / 8 * 8 : 8;                // a multiple of 8 keeps a workgroup's tiles on its own XCD
+            return v;
         }();
         static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp3_kernel<false>),
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
@@ -1844,16 +1886,16 @@ static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
         if (attr0 != hipSuccess || attr1 != hipSuccess)
             return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds3, hipGetErrorString(attr0 != hipSuccess ? attr0 : attr1));
-        const int total = (int)g.grid;                   // tiles: each workgroup walks total / grid of them
-        const dim3 grid((unsigned)(total < cus ? total : cus));
+        const int total = (int)g.grid;                   // virtual tiles (the XCD-aware numbering has holes)
+        const dim3 grid(pp_workgroups(PP_PERSISTENT, g.grid, cus));
         hipLaunchKernelGGL(sc ? linear_fwd_pp3_kernel<true> : linear_fwd_pp3_kernel<false>, grid, dim3(512), lds3, stream, x, W, b, sc, sh, y,
                            n, out_dim, in_dim, relu, g.bn_blocks, (int)g.bm_blocks, total, XCD_ORDER);
     } else {
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp2_kernel),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
         if (attr != hipSuccess) return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds2, hipGetErrorString(attr));
-        hipLaunchKernelGGL(linear_fwd_pp2_kernel, dim3(g.grid), dim3(512), lds2, stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu,
-                           g.bn_blocks, (int)g.bm_blocks, XCD_ORDER);
+        hipLaunchKernelGGL(linear_fwd_pp2_kernel, dim3(pp_workgroups(PP_PER_TILE, g.grid, 0)), dim3(512), lds2, stream, x, W, b, sc, sh, y, n,
+                           out_dim, in_dim, relu, g.bn_blocks, (int)g.bm_blocks, XCD_ORDER);
     }
     return check_launch("linear_fwd_pp2_kernel");
 }
@@ -1910,6 +1952,37 @@ static int launch_train_fwd(T, const float *x, int64_t n, int in_dim, const floa
 }
 
 // ---- entry points
+// What lcrec_linear_forward launches for a shape, as a pure step (no HIP call): row ranges in order, each with the
+// kernel family that takes it.  linear_forward() launches exactly these; lcrec_debug_linear_forward_plan() reports them.
+enum FwdKind { FWD_PP, FWD_S16, FWD_TILE };
+struct FwdStep { int64_t row0, rows; FwdKind kind; TileShape shape; };      // shape: FWD_TILE only
+constexpr int FWD_MAX_STEPS = 4;       // (a ping-pong head and its tail are two; a tail is below one round and is never cut again)
+static int forward_steps(int64_t n, int in_dim, int out_dim, FwdStep *steps)
+{
+    const int pp = knobs().pp;
+    const bool pp_ok = out_dim > 64 && in_dim % BK == 0 && (int64_t)in_dim * 4 * 192 < (1ll << 31);     // else the other kernels
+    int count = 0;
+    int64_t row0 = 0;
+    while (n > 0) {
+        const int64_t head = pp_ok && pp == -1 && count + 1 < FWD_MAX_STEPS ? pp_head_rows(n, out_dim) : 0;
+        if (head) {
+            steps[count++] = FwdStep{row0, head, FWD_PP, TILE_64x64};
+            row0 += head;
+            n -= head;
+            continue;
+        }
+        if (pp_ok && (pp == 1 || (pp == -1 && pp_fits(n, out_dim))))
+            steps[count++] = FwdStep{row0, n, FWD_PP, TILE_64x64};
+        // launches that 64 x 64 tiles cannot fill the chip with: 32 x 64 tiles on the 16 x 16 x 4 MFMA (linear_s16_kernel)
+        else if (use_s16_tiles(n, out_dim, in_dim))
+            steps[count++] = FwdStep{row0, n, FWD_S16, TILE_64x64};
+        else
+            steps[count++] = FwdStep{row0, n, FWD_TILE, forward_tile_shape(n, out_dim)};
+        break;
+    }
+    return count;
+}
+
 int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const float *b,
                    const float *bn_scale, const float *bn_shift, int relu, int out_dim, float *y,
                    hipStream_t stream)
@@ -1923,20 +1996,82 @@ int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const 
         return fail(LCREC_EUNSUPPORTED, "linear_forward: in_dim=%d is not a multiple of 8", in_dim);
     if (((uintptr_t)x | (uintptr_t)W) & 15)
         return fail(LCREC_EINVAL, "linear_forward: x and W must be 16-byte aligned");
-    const int pp = knobs().pp;
-    const bool pp_ok = out_dim > 64 && in_dim % BK == 0 && (int64_t)in_dim * 4 * 192 < (1ll << 31);     // else the other kernels
-    if (const int64_t head = pp_ok && pp == -1 ? pp_head_rows(n, out_dim) : 0) {
-        int rc = launch_linear_pp(x, head, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
+    FwdStep steps[FWD_MAX_STEPS];
+    const int count = forward_steps(n, in_dim, out_dim, steps);
+    for (int i = 0; i < count; ++i) {
+        const FwdStep &s = steps[i];
+        const float *xs = x + s.row0 * in_dim;
+        float *ys = y + s.row0 * out_dim;
+        int rc;
+        if (s.kind == FWD_PP)
+            rc = launch_linear_pp(xs, s.rows, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, ys, stream);
+        else if (s.kind == FWD_S16)
+            rc = launch_s16(xs, W, b, bn_scale, bn_shift, relu, ys, s.rows, out_dim, in_dim, false, stream);
+        else
+            rc = with_tile(s.shape, [&](auto tile) { return launch_linear(tile, xs, s.rows, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, ys, stream); });
         if (rc) return rc;
-        return linear_forward(x + head * in_dim, n - head, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y + head * out_dim, stream);
     }
-    if (pp_ok && (pp == 1 || (pp == -1 && pp_fits(n, out_dim))))
-        return launch_linear_pp(x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream);
-    // launches that 64 x 64 tiles cannot fill the chip with: 32 x 64 tiles on the 16 x 16 x 4 MFMA (linear_s16_kernel)
-    if (use_s16_tiles(n, out_dim, in_dim))
-        return launch_s16(x, W, b, bn_scale, bn_shift, relu, y, n, out_dim, in_dim, false, stream);
-    return with_tile(forward_tile_shape(n, out_dim),
-                     [&](auto tile) { return launch_linear(tile, x, n, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, y, stream); });
+    return LCREC_OK;
+}
+
+// The launches of linear_forward(n, in_dim, out_dim) on a device of `cus` compute units, for tests and tools: nothing is
+// launched and no HIP call is made.  Rows, label and form come from forward_steps(), pp_form() and pp_workgroups(), the
+// functions the launch path runs.  The tile lists of a persistent launch are walked here as linear_fwd_pp3_kernel's
+// tile_of() / next_tile() walk them (device code: restated, with the same arguments the launch passes).
+static int linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcrec_debug_forward_launch *out, int capacity)
+{
+    if (n == 0) return 0;
+    // (plain codes: a question about a launch does not touch the thread's last-error text)
+    if (!out || capacity < FWD_MAX_STEPS || cus < 1) return LCREC_EINVAL;
+    if (n < 0 || in_dim <= 0 || out_dim <= 0) return LCREC_EINVAL;       // shapes linear_forward refuses
+    if (in_dim % 8 != 0) return LCREC_EUNSUPPORTED;
+    FwdStep steps[FWD_MAX_STEPS];
+    const int count = forward_steps(n, in_dim, out_dim, steps);
+    for (int i = 0; i < count; ++i) {
+        const FwdStep &s = steps[i];
+        lcrec_debug_forward_launch &o = out[i];
+        memset(&o, 0, sizeof o);
+        o.row0 = s.row0;
+        o.rows = s.rows;
+        const TileDims d = s.kind == FWD_PP ? TileDims{256, 128} : s.kind == FWD_S16 ? TileDims{S16_BM, S16_BN} : tile_dims(s.shape);
+        const KernelId label = s.kind == FWD_PP    ? K_LINEAR_PP
+                               : s.kind == FWD_S16 ? K_LINEAR_32x64
+                                                   : with_tile(s.shape, [](auto tile) { return decltype(tile)::LABEL; });
+        o.label = kKernelNames[label];
+        o.tile_rows = d.bm;
+        o.tile_cols = d.bn;
+        o.k_tiles = (in_dim + BK - 1) / BK;
+        TileGrid g;
+        if (int rc = tile_grid(g, "linear_forward_plan", s.rows, out_dim, d.bm, d.bn, s.kind != FWD_S16)) return rc;
+        o.tiles = (int)(g.bm_blocks * g.bn_blocks);
+        o.virtual_tiles = (int)g.grid;
+        o.workgroups = (int)g.grid;
+        o.last_panel_rows = (int)(s.rows - (g.bm_blocks - 1) * d.bm);
+        if (s.kind != FWD_PP) continue;
+        o.form = pp_form(in_dim, out_dim);
+        o.workgroups = (int)pp_workgroups((PpForm)o.form, g.grid, cus);
+        if (o.form != PP_PERSISTENT) continue;
+        o.steady_iterations = (o.k_tiles - PP3_HEAD_KTILES - PP3_TAIL_KTILES) / 2;
+        o.list_min = o.tiles;
+        for (int wg = 0; wg < o.workgroups; ++wg) {
+            int len = 0, ragged = 0;             // ragged: ragged-panel tiles in this list; last_ragged: is its last tile one
+            bool last_ragged = false;
+            for (int64_t t = wg; t < g.grid; t += o.workgroups) {
+                const int xcd = (int)(t & 7);
+                const int64_t j = t >> 3, panels = (g.bm_blocks - xcd + 7) >> 3;
+                if (j >= panels * g.bn_blocks) continue;                       // a hole
+                last_ragged = o.last_panel_rows < d.bm && j / g.bn_blocks * 8 + xcd == g.bm_blocks - 1;
+                ragged += last_ragged;
+                ++len;
+            }
+            if (len < o.list_min) o.list_min = len;
+            if (len > o.list_max) o.list_max = len;
+            o.empty_workgroups += len == 0;
+            o.single_tile_workgroups += len == 1;
+            o.ragged_handed_over += ragged - (last_ragged ? 1 : 0);
+        }
+    }
+    return count;
 }
 
 // dW = dY^T X contracts over the batch: a [out][in] output of a narrow layer is a handful of tiles, each a serial
@@ -2134,6 +2269,15 @@ int linear_bn_forward(const float *x, int64_t n, int in_dim, const float *in_sca
 }
 
 }  // namespace lcrec
+
+// Debug export (not in include/lcrec.h): the launches lcrec_linear_forward would make for [n][in_dim] -> [n][out_dim] on a
+// device of `cus` compute units, in order.  Host code only: it runs without a GPU.  Returns the number of launches written
+// to out[0 .. capacity) (capacity >= 4), or a negative LCREC_E* code.  tests/gemm_pp_cases.py holds the matching ctypes struct.
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus,
+                                                                                        lcrec_debug_forward_launch *out, int capacity)
+{
+    return lcrec::linear_forward_plan(n, in_dim, out_dim, cus, out, capacity);
+}
 
 #ifdef LCREC_GEMM_STAMP
 extern "C" __attribute__((visibility("default"))) int lcrec_debug_gemm_stamps(unsigned long long *out)

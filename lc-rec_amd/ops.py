@@ -172,8 +172,10 @@ def _audit_buffers(audit, tie_tau, n, L, dev):
     return margin, neartie, float(tie_tau or 0.0)
 
 
-def linear_forward(x, weight, bias=None, bn_scale=None, bn_shift=None, relu=False):
-    """y = [relu]([bn](x @ weight.T + bias)) -- one group of MLPLayers.forward (layers.py:18-30,42)."""
+def linear_forward(x, weight, bias=None, bn_scale=None, bn_shift=None, relu=False, out=None):
+    """y = [relu]([bn](x @ weight.T + bias)) -- one group of MLPLayers.forward (layers.py:18-30,42).
+    out: optional contiguous float32 [n, out_dim] device tensor the result is written into (a row range of a larger
+    buffer, say); it is returned."""
     lib = _lib.load()
     x = _dev(x, "x")
     weight = _dev(weight, "weight")
@@ -184,7 +186,9 @@ def linear_forward(x, weight, bias=None, bn_scale=None, bn_shift=None, relu=Fals
     out_dim = weight.shape[0]
     if weight.shape[1] != k:
         raise _lib.LcrecError(f"weight is {tuple(weight.shape)}, x is {tuple(x.shape)}")
-    y = torch.empty((n, out_dim), dtype=torch.float32, device=x.device)
+    y = out if out is not None else torch.empty((n, out_dim), dtype=torch.float32, device=x.device)
+    if y.shape != (n, out_dim) or y.dtype != torch.float32 or y.device != x.device or not y.is_contiguous():
+        raise _lib.LcrecError("out must be a contiguous float32 [n, out_dim] tensor on x's device")
     with _on(x.device):
         rc = lib.lcrec_linear_forward(_ptr(x), n, k, _ptr(weight), _ptr(bias), _ptr(bn_scale), _ptr(bn_shift),
                                       int(bool(relu)), out_dim, _ptr(y), _stream_ptr())

@@ -564,6 +564,38 @@ int lcrec_trace_enable(int on);
 /* Returns the number of entries written (<= capacity), or a negative LCREC_E* code. */
 int lcrec_trace_collect(lcrec_trace_entry *out, int capacity);
 
+/* Debug entries (diagnostic, for the tests: not a path of training or index generation).
+ *
+ * The batch-sized Sinkhorn solve of lcrec_sinkhorn_assign (a lone group too large for one workgroup) picks one of three
+ * solvers by shape; lcrec_debug_sinkhorn_plan reports that choice and its geometry, lcrec_debug_sinkhorn_batch runs it.
+ *   form   0 = what lcrec_sinkhorn_assign chooses; 1 = scaling form, eight sets of workgroups that each exchange inside one
+ *          XCD; 2 = scaling form, one set, agent-scope exchange; 3 = persistent in-place form; 4 = one launch per iteration.
+ *          A forced form that cannot take the shape is LCREC_EUNSUPPORTED, never another form. */
+typedef struct {
+    int form;                 /* 1 .. 4 as above (never 0) */
+    int cpl, rw;              /* columns per lane and rows per wave: the kernel's template arguments (form 4: ceil(K/64), 4) */
+    int workgroups;           /* per set */
+    int sets;                 /* 1, or 8 for form 1 */
+    int rows_per_workgroup;
+    int padded_columns;       /* 64 * cpl - K */
+    int ragged_wave;          /* the last wave that has rows has fewer than rw */
+    int ragged_workgroup;     /* the last workgroup has fewer than rows_per_workgroup */
+    int batch_route;          /* whether lcrec_sinkhorn_assign gives a lone group of B rows to this solver at all */
+    int64_t workspace_bytes;  /* what lcrec_debug_sinkhorn_batch needs for this shape */
+} lcrec_sinkhorn_plan;
+/* Host only: nothing is launched, no device is needed. */
+int lcrec_debug_sinkhorn_plan(int64_t B, int K, int iters, int form, lcrec_sinkhorn_plan *out);
+/* One group of n rows through the batch-sized solver, arguments as for lcrec_sinkhorn_assign, with the same kernels.
+ *   runner_out  device int64[n] or NULL: per row the column of the second-largest entry (first one on ties)
+ *   ratio_out   device double[n] or NULL (given together with runner_out): second-largest / largest entry of the row
+ *   form_ran    host int or NULL: the form whose kernels were launched (0: none)
+ * With form = 0 a solver whose launch the runtime refuses (occupancy, LDS attribute) is replaced as in production and
+ * form_ran says by which; with a forced form the refusal is LCREC_EUNSUPPORTED. */
+int lcrec_debug_sinkhorn_batch(const float *resid, int64_t n, int e, const float *codebook, int K, double epsilon, int iters,
+                               int64_t *idx_out, int64_t idx_stride, void *workspace, size_t workspace_bytes,
+                               unsigned int *ticket, void *stream, int form, int64_t *runner_out, double *ratio_out,
+                               int *form_ran);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,10 @@ _SIGNATURES = {
     "lcrec_index_json_format": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int64]),
     "lcrec_trace_enable": (ctypes.c_int, [ctypes.c_int]),
     "lcrec_trace_collect": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lcrec_debug_sinkhorn_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "lcrec_debug_sinkhorn_batch": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                  _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp, _vp,
+                                                  ctypes.POINTER(ctypes.c_int)]),
 }
 
 
@@ -118,6 +122,14 @@ class DwProblem(ctypes.Structure):
     _fields_ = [("gy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("gw", ctypes.c_void_p), ("n", ctypes.c_int64),
                 ("in_dim", ctypes.c_int), ("out_dim", ctypes.c_int), ("x_scale", ctypes.c_void_p), ("x_shift", ctypes.c_void_p),
                 ("x_relu", ctypes.c_int), ("splits", ctypes.c_int)]
+
+
+class SinkhornPlan(ctypes.Structure):
+    """lcrec_sinkhorn_plan of include/lcrec.h"""
+    _fields_ = [("form", ctypes.c_int), ("cpl", ctypes.c_int), ("rw", ctypes.c_int), ("workgroups", ctypes.c_int),
+                ("sets", ctypes.c_int), ("rows_per_workgroup", ctypes.c_int), ("padded_columns", ctypes.c_int),
+                ("ragged_wave", ctypes.c_int), ("ragged_workgroup", ctypes.c_int), ("batch_route", ctypes.c_int),
+                ("workspace_bytes", ctypes.c_int64)]
 
 
 class TraceEntry(ctypes.Structure):

@@ -199,6 +199,42 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// The debug epilogue of the three batch-sized solvers: each lane brings its best entry among the columns that are not the
+// row's winner; the wave's first maximum of those is the runner-up, written with second / best (best: the winner's value,
+// the same in every lane after the argmax butterfly).
+__device__ __forceinline__ void sk_runner_up(double sec, int sj, double best, int lane, int64_t *runner, double *ratio)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double s2 = __shfl_xor(sec, o, 64);
+        const int j2 = __shfl_xor(sj, o, 64);
+        if (s2 > sec || (s2 == sec && j2 < sj)) { sec = s2; sj = j2; }
+    }
+    if (lane == 0) { *runner = sj; *ratio = sec / best; }
+}
+
+// Where the one-launch solvers find the debug outputs: not in their kernel arguments (they sit at the SGPR limit, and an
+// argument is live through the iteration loop) but in the control words of the workspace, read after the last iteration.  Word
+// SK_CTRL_DEBUG is zeroed with the other control words by every solve's set-up (sk_ctrl_init_kernel / the distance launch's last
+// workgroup); lcrec_debug_sinkhorn_batch sets it and the two pointers behind it by a launch of its own (sk_debug_arm_kernel).
+constexpr int SK_CTRL_FLAG = 5, SK_CTRL_DEBUG = 6, SK_CTRL_DEBUG_PTRS = 32;     // words of the control block (`minmax`)
+struct SkDebugOut { int64_t *runner; double *ratio; };
+__device__ __forceinline__ SkDebugOut sk_debug_out(const unsigned *flag)      // flag = control word SK_CTRL_FLAG
+{
+    SkDebugOut o = {nullptr, nullptr};
+    if (__hip_atomic_load(flag + (SK_CTRL_DEBUG - SK_CTRL_FLAG), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
+        o.runner = *reinterpret_cast<int64_t *const *>(flag + (SK_CTRL_DEBUG_PTRS - SK_CTRL_FLAG));
+        o.ratio = *reinterpret_cast<double *const *>(flag + (SK_CTRL_DEBUG_PTRS + 2 - SK_CTRL_FLAG));
+    }
+    return o;
+}
+__global__ void sk_debug_arm_kernel(unsigned *ctrl, int64_t *runner, double *ratio)
+{
+    *reinterpret_cast<int64_t **>(ctrl + SK_CTRL_DEBUG_PTRS) = runner;
+    *reinterpret_cast<double **>(ctrl + SK_CTRL_DEBUG_PTRS + 2) = ratio;
+    ctrl[SK_CTRL_DEBUG] = 1u;
+}
+
 __global__ __launch_bounds__(SK_THREADS) void sk_init_kernel(SkBig p)
 {
     __shared__ double wsum[SK_THREADS / 64];
@@ -296,7 +332,9 @@ __global__ __launch_bounds__(SK_THREADS) void sk_iter_kernel(SkBig p, int mode, 
     }
 }
 
-__global__ __launch_bounds__(SK_THREADS) void sk_final_kernel(SkBig p, int src, int64_t *idx_out, int64_t idx_stride)
+// runner_out / ratio_out (lcrec_debug_sinkhorn_batch; NULL in production): the row's second-best column and second / best.
+__global__ __launch_bounds__(SK_THREADS) void sk_final_kernel(SkBig p, int src, int64_t *idx_out, int64_t idx_stride,
+                                                               int64_t *runner_out, double *ratio_out)
 {
     extern __shared__ __attribute__((aligned(16))) double sk_sm[];
     double *colsum = sk_sm;
@@ -328,6 +366,17 @@ __global__ __launch_bounds__(SK_THREADS) void sk_final_kernel(SkBig p, int src, 
             if (b2 > best || (b2 == best && j2 < bj)) { best = b2; bj = j2; }
         }
         if (lane == 0) idx_out[row * idx_stride] = bj;
+        if (runner_out) {                                        // wave-uniform
+            double sec = -1.0;
+            int sj = 0;
+            for (int j = lane; j < p.K; j += 64) {
+                double v = p.Q[row * p.K + j] / colsum[j];
+                v = divK(v);
+                v = v * Bd;
+                if (j != bj && v > sec) { sec = v; sj = j; }
+            }
+            sk_runner_up(sec, sj, best, lane, runner_out + row, ratio_out + row);
+        }
     }
 }
 
@@ -990,6 +1039,7 @@ __global__ __launch_bounds__(SKP_THREADS) void sk_persistent_kernel(SkPersist p)
         SK_STAMP(6);
         if (abort_sh) break;                                     // uniform: read after the barrier every thread passed
     }
+    const SkDebugOut dbg = sk_debug_out(p.flag);                 // NULL pointers in production
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
         double best = -1.0;
@@ -1014,6 +1064,21 @@ __global__ __launch_bounds__(SKP_THREADS) void sk_persistent_kernel(SkPersist p)
         if (lane == 0 && row0 + r < p.B) {
             const unsigned bad = __hip_atomic_load(p.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             p.idx_out[(row0 + r) * p.idx_stride] = bad ? -1 : bj;
+        }
+        if (dbg.runner && row0 + r < p.B) {                    // wave-uniform
+            double sec = -1.0;
+            int sj = 0;
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                const int j = lane + 64 * c;
+                if (j < K) {
+                    double v = q[r][c] / colsum[j];
+                    v = divK(v);
+                    v = v * Bd;
+                    if (j != bj && v > sec) { sec = v; sj = j; }
+                }
+            }
+            sk_runner_up(sec, sj, best, lane, dbg.runner + row0 + r, dbg.ratio + row0 + r);
         }
     }
 }
@@ -1293,6 +1358,7 @@ __global__ __launch_bounds__(SKP_THREADS) void sk_scaling_kernel(SkScale p)
         if (abort_sh) break;                                     // uniform: read after a barrier every thread passed
     }
     if (abort_sh == 2) return;                                   // another XCD's set finished the solve: it writes the assignments
+    const SkDebugOut dbg = sk_debug_out(p.flag);                 // NULL pointers in production
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
         double best = -1.0;
@@ -1314,6 +1380,19 @@ __global__ __launch_bounds__(SKP_THREADS) void sk_scaling_kernel(SkScale p)
         if (lane == 0 && row0 + r < p.B) {
             const unsigned bad = __hip_atomic_load(p.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             p.idx_out[(row0 + r) * p.idx_stride] = bad ? -1 : bj;
+        }
+        if (dbg.runner && row0 + r < p.B) {                    // wave-uniform
+            double sec = -1.0;
+            int sj = 0;
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                const int j = lane + 64 * c;
+                if (j < K) {
+                    const double v = e[r][c] * b[c];
+                    if (j != bj && v > sec) { sec = v; sj = j; }
+                }
+            }
+            sk_runner_up(sec, sj, best, lane, dbg.runner + row0 + r, dbg.ratio + row0 + r);
         }
     }
     // (a workgroup that got here has seen every member of its set publish the last iteration: the set is complete and all of it
@@ -1399,10 +1478,124 @@ __global__ __launch_bounds__(256) void sk_ctrl_init_kernel(unsigned *ctrl, doubl
         reinterpret_cast<unsigned long long *>(slots)[i] = SKP_EMPTY;
 }
 
-static int sinkhorn_big(const float *r, int64_t B, int e, const float *cb, int K, double eps, int iters,
-                        int64_t *idx_out, int64_t idx_stride, char *ws, unsigned *ticket, hipStream_t stream)
+// ---- which solver a batch-sized problem takes, as a pure function of (B, K, iters) and the tuning knobs: sinkhorn_big() below
+// executes this plan, lcrec_debug_sinkhorn_plan() reports it; neither restates the other.  What the plan cannot know is whether
+// the runtime grants the launch (skp_fits, hipFuncSetAttribute): sinkhorn_big() then goes on to the next form of the chain
+// scaling -> persistent -> multi-launch.
+enum { SKF_AUTO = 0, SKF_SCALING_LOCAL = 1, SKF_SCALING_AGENT = 2, SKF_PERSISTENT = 3, SKF_MULTI = 4 };
+
+struct SkKnobs {
+    bool allow_scaling;      // LCREC_SINKHORN_SCALING=0: the in-place forms only
+    bool allow_local;        // LCREC_SK_LOCAL=0: the scaling form with one set of workgroups, agent scope
+    bool allow_persistent;   // LCREC_SINKHORN_PERSISTENT=0: the multi-launch solver instead of the persistent kernel
+    int nblk_target;         // LCREC_SK_BLOCKS: workgroups the scaling form aims for (16)
+    int rw_env;              // LCREC_SK_RW: rows per wave of the persistent kernel at 193 <= K <= 256 (2; 1 and 4 for tuning)
+};
+
+static const SkKnobs &sk_knobs()
 {
+    static const SkKnobs k = [] {
+        SkKnobs v;
+        const char *e = getenv("LCREC_SINKHORN_SCALING");
+        v.allow_scaling = !e || atoi(e) != 0;
+        e = getenv("LCREC_SK_LOCAL");
+        v.allow_local = !e || atoi(e) != 0;
+        e = getenv("LCREC_SINKHORN_PERSISTENT");
+        v.allow_persistent = !e || atoi(e) != 0;
+        e = getenv("LCREC_SK_BLOCKS");
+        v.nblk_target = e ? atoi(e) : 16;
+        e = getenv("LCREC_SK_RW");
+        v.rw_env = e ? atoi(e) : 2;
+        return v;
+    }();
+    return k;
+}
+
+static void sk_plan_fill(lcrec_sinkhorn_plan *o, int form, int cpl, int rw, int64_t B, int K, int sets)
+{
+    const int rows = 8 * rw;
+    o->form = form; o->cpl = cpl; o->rw = rw;
+    o->workgroups = (int)((B + rows - 1) / rows);
+    o->sets = sets;
+    o->rows_per_workgroup = rows;
+    o->padded_columns = 64 * cpl - K;
+    o->ragged_wave = B % rw != 0;
+    o->ragged_workgroup = B % rows != 0;
+}
+
+// Whether `form` (not SKF_AUTO) can take the shape, and its geometry if so.
+static bool sk_plan_form(int64_t B, int K, int iters, const SkKnobs &kn, int form, lcrec_sinkhorn_plan *o)
+{
+    if (B < 1 || K < 1 || K > 64 * SK_MAXC || iters < 1) return false;
+    if (form == SKF_SCALING_LOCAL || form == SKF_SCALING_AGENT) {
+        // rows per workgroup 16 / 32 / 64 / 128 (RW = 2 .. 16 rows per wave, at most 64 doubles of E per lane), the smallest that
+        // needs no more than nblk_target workgroups -- fewer partials to add, and the arithmetic no longer wants more CUs
+        const int cpl_s = K / 64, cpl_t = cpl_s <= 1 ? 1 : cpl_s <= 2 ? 2 : cpl_s <= 4 ? 4 : cpl_s <= 8 ? 8 : 16;
+        const int rw_cap = cpl_t == 1 ? 8 : cpl_t <= 4 ? 16 : (cpl_t <= 8 ? 8 : 4);       // (<1, 16> spills: not instantiated)
+        int rw = 2;
+        while (rw < rw_cap && (B + 8 * rw - 1) / (8 * rw) > kn.nblk_target) rw *= 2;
+        const int64_t nblk_s = (B + 8 * rw - 1) / (8 * rw);
+        // (the exchange buffers live in the Q region, [B][K] doubles, which this form does not use otherwise)
+        if (!(K % 64 == 0 && nblk_s <= 64 && 3 * nblk_s <= B)) return false;
+        // XCD-local exchange: eight sets of buffers when they fit the region
+        if (form == SKF_SCALING_LOCAL && !((int64_t)8 * 3 * nblk_s <= B && 8 * nblk_s <= 256)) return false;
+        sk_plan_fill(o, form, cpl_t, rw, B, K, form == SKF_SCALING_LOCAL ? 8 : 1);
+        return true;
+    }
+    const int cpl = (K + 63) / 64;
+    if (form == SKF_PERSISTENT) {
+        // K = 256 (the reference's codebook size): two rows per wave instead of four when that still fits 128 workgroups
+        // (B <= 2048) -- twice the CUs on the divisions, 22.2 k -> 18.9 k cycles per iteration.  LCREC_SK_RW=4 disables.
+        const bool rw1 = kn.rw_env == 1 && cpl == 4 && (B + 7) / 8 <= SKP_MAX_BLOCKS;     // LCREC_SK_RW=1 (tuning): 8 rows per workgroup
+        const bool rw2 = !rw1 && kn.rw_env <= 2 && cpl == 4 && (B + 15) / 16 <= SKP_MAX_BLOCKS;
+        const int rows_p = rw1 ? 8 : rw2 ? 16 : cpl <= 4 ? 32 : (cpl <= 8 ? 16 : 8);
+        const int64_t nblk_p = (B + rows_p - 1) / rows_p, nblk = (B + SK_ROWS - 1) / SK_ROWS;
+        // the Q region ([B][K] doubles) holds the exchange buffers: 3*nblk_p*K partials + 3*K sums + nblk_p totals
+        if (!(nblk_p <= SKP_MAX_BLOCKS && nblk_p <= nblk * 4 && (3 * (int64_t)K + 1) * nblk_p + 3 * (int64_t)K <= B * (int64_t)K))
+            return false;
+        sk_plan_fill(o, form, cpl <= 1 ? 1 : cpl <= 2 ? 2 : cpl <= 4 ? 4 : cpl <= 8 ? 8 : 16, rows_p / 8, B, K, 1);
+        return true;
+    }
+    if (form != SKF_MULTI) return false;
+    sk_plan_fill(o, form, cpl, SK_ROWS / (SK_THREADS / 64), B, K, 1);
+    return true;
+}
+
+// The plan of `form`; SKF_AUTO: the first form of the chain that takes the shape.
+static int sk_batch_plan(int64_t B, int K, int iters, const SkKnobs &kn, int form, lcrec_sinkhorn_plan *o)
+{
+    if (B < 1 || K < 1 || iters < 1) return fail(LCREC_EINVAL, "sinkhorn: B=%lld, K=%d, iters=%d: all must be >= 1", (long long)B, K, iters);
     if (K > 64 * SK_MAXC) return fail(LCREC_EUNSUPPORTED, "sinkhorn: K=%d > %d", K, 64 * SK_MAXC);
+    if (form < SKF_AUTO || form > SKF_MULTI) return fail(LCREC_EINVAL, "sinkhorn: form %d (0 .. 4)", form);
+    memset(o, 0, sizeof *o);
+    bool ok;
+    if (form == SKF_AUTO)
+        ok = (kn.allow_scaling && ((kn.allow_local && sk_plan_form(B, K, iters, kn, SKF_SCALING_LOCAL, o)) ||
+                                   sk_plan_form(B, K, iters, kn, SKF_SCALING_AGENT, o))) ||
+             (kn.allow_persistent && sk_plan_form(B, K, iters, kn, SKF_PERSISTENT, o)) ||
+             sk_plan_form(B, K, iters, kn, SKF_MULTI, o);
+    else
+        ok = sk_plan_form(B, K, iters, kn, form, o);
+    if (!ok) return fail(LCREC_EUNSUPPORTED, "sinkhorn: form %d cannot take B=%lld, K=%d", form, (long long)B, K);
+    const int64_t one[2] = {0, B};
+    const SkPlan route = sk_plan(K, one, 1);
+    o->batch_route = route.biggest == B;
+    o->workspace_bytes = (int64_t)sk_big_bytes(B, K);
+    return LCREC_OK;
+}
+
+// what lcrec_debug_sinkhorn_batch adds to a solve (NULL in production)
+struct SkDebug { int form; int64_t *runner_out; double *ratio_out; int ran; };
+
+static int sinkhorn_big(const float *r, int64_t B, int e, const float *cb, int K, double eps, int iters,
+                        int64_t *idx_out, int64_t idx_stride, char *ws, unsigned *ticket, hipStream_t stream, SkDebug *dbg = nullptr)
+{
+    const SkKnobs &kn = sk_knobs();
+    const int want = dbg ? dbg->form : SKF_AUTO;
+    int64_t *const runner_out = dbg ? dbg->runner_out : nullptr;
+    double *const ratio_out = dbg ? dbg->ratio_out : nullptr;
+    lcrec_sinkhorn_plan pl;
+    if (int rc0 = sk_batch_plan(B, K, iters, kn, want, &pl)) return rc0;
     SkBig p;
     const int64_t nblk = (B + SK_ROWS - 1) / SK_ROWS;
     float *d = reinterpret_cast<float *>(ws);
@@ -1415,26 +1608,12 @@ static int sinkhorn_big(const float *r, int64_t B, int e, const float *cb, int K
     ws += align_up((size_t)nblk * sizeof(double), 256);
     unsigned *minmax = reinterpret_cast<unsigned *>(ws);
     p.d = d; p.minmax = minmax; p.B = B; p.K = K; p.nblk = (int)nblk; p.eps = eps;
-    // one launch, scaling form (sk_scaling_kernel): rows per workgroup 16 / 32 / 64 / 128 (RW = 2 .. 16 rows per wave, at most
-    // 64 doubles of E per lane), the smallest that needs no more than 16 workgroups -- fewer partials to add, and the arithmetic
-    // no longer wants more CUs.  LCREC_SINKHORN_SCALING=0: the in-place form below.
-    static const bool allow_scaling = [] { const char *e = getenv("LCREC_SINKHORN_SCALING"); return !e || atoi(e) != 0; }();
-    static const int nblk_target = [] { const char *e = getenv("LCREC_SK_BLOCKS"); return e ? atoi(e) : 16; }();
-    const int cpl_s = K / 64, cpl_t = cpl_s <= 1 ? 1 : cpl_s <= 2 ? 2 : cpl_s <= 4 ? 4 : cpl_s <= 8 ? 8 : 16;
-    const int rw_cap = cpl_t == 1 ? 8 : cpl_t <= 4 ? 16 : (cpl_t <= 8 ? 8 : 4);       // (<1, 16> spills: not instantiated)
-    int rw = 2;
-    while (rw < rw_cap && (B + 8 * rw - 1) / (8 * rw) > nblk_target) rw *= 2;
-    const int64_t nblk_s = (B + 8 * rw - 1) / (8 * rw);
-    // (the exchange buffers live in the Q region, [B][K] doubles, which this path does not use otherwise)
-    const bool scaling = allow_scaling && iters >= 1 && K % 64 == 0 && K <= 1024 && nblk_s <= 64 && 3 * nblk_s <= B;
+    const bool scaling = pl.form == SKF_SCALING_LOCAL || pl.form == SKF_SCALING_AGENT;
     // control words (and the scaling form's slot sentinels) by a kernel, not by memset nodes: inside a captured hipGraph
     // (engine.py) the two memsets were seen to take effect late -- replays found the previous solve's flag / a counter reset
     // under a running barrier
     // With a ticket the distance launch does all of that itself (its last workgroup writes the control words).
-    // XCD-local exchange (sk_scaling_kernel): eight sets of buffers when they fit the region.  LCREC_SK_LOCAL=0: one set, agent scope.
-    static const bool allow_local = [] { const char *e = getenv("LCREC_SK_LOCAL"); return !e || atoi(e) != 0; }();
-    const int replicas = scaling && allow_local && (int64_t)8 * 3 * nblk_s <= B && 8 * nblk_s <= 256 ? 8 : 1;
-    const int64_t slot_count = scaling ? (int64_t)replicas * 3 * nblk_s * K : (int64_t)0;
+    const int64_t slot_count = scaling ? (int64_t)pl.sets * 3 * pl.workgroups * K : (int64_t)0;
     const int64_t dist_blocks = ((B + DIST_ITEMS - 1) / DIST_ITEMS) * ((K + 255) / 256);
     int rc;
     if (ticket && dist_blocks <= DIST_TICKET_MAX_BLOCKS) {
@@ -1445,50 +1624,54 @@ static int sinkhorn_big(const float *r, int64_t B, int e, const float *cb, int K
         rc = vq_distances(r, B, e, cb, K, d, minmax, stream);
     }
     if (rc) return rc;
-    if (iters == 0) return fail(LCREC_EUNSUPPORTED, "sinkhorn: iters must be >= 1");
+    if (runner_out && pl.form != SKF_MULTI) {                    // (debug entry only; the multi-launch epilogue takes them as arguments)
+        hipLaunchKernelGGL(sk_debug_arm_kernel, dim3(1), dim3(1), 0, stream, minmax, runner_out, ratio_out);
+        if (int rc0 = check_launch("sk_debug_arm_kernel")) return rc0;
+    }
     TraceScope trace(K_SINKHORN, stream);
 
     if (scaling) {
         SkScale q;
         q.d = d; q.part = p.Q; q.minmax = minmax; q.flag = minmax + 5;
-        q.B = B; q.K = K; q.nblk = (int)nblk_s; q.iters = iters; q.eps = eps;
+        q.B = B; q.K = K; q.nblk = pl.workgroups; q.iters = iters; q.eps = eps;
         q.idx_out = idx_out; q.idx_stride = idx_stride;
-        q.replicas = replicas; q.done = minmax + 8; q.ranks = minmax + 16;
+        q.replicas = pl.sets; q.done = minmax + 8; q.ranks = minmax + 16;
         bool launched;
-        if (cpl_t == 1) launched = launch_sks_rw<1>(q, rw, stream);
-        else if (cpl_t == 2) launched = launch_sks_rw<2>(q, rw, stream);
-        else if (cpl_t == 4) launched = launch_sks_rw<4>(q, rw, stream);
-        else if (cpl_t == 8) launched = launch_sks_rw<8>(q, rw, stream);
-        else launched = launch_sks_rw<16>(q, rw, stream);
-        if (launched) return check_launch("sk_scaling_kernel");
+        if (pl.cpl == 1) launched = launch_sks_rw<1>(q, pl.rw, stream);
+        else if (pl.cpl == 2) launched = launch_sks_rw<2>(q, pl.rw, stream);
+        else if (pl.cpl == 4) launched = launch_sks_rw<4>(q, pl.rw, stream);
+        else if (pl.cpl == 8) launched = launch_sks_rw<8>(q, pl.rw, stream);
+        else launched = launch_sks_rw<16>(q, pl.rw, stream);
+        if (launched) {
+            if (dbg) dbg->ran = pl.form;
+            return check_launch("sk_scaling_kernel");
+        }
+        if (want != SKF_AUTO) return fail(LCREC_EUNSUPPORTED, "sinkhorn: the runtime refused the launch of forced form %d", want);
+        if (!(kn.allow_persistent && sk_plan_form(B, K, iters, kn, SKF_PERSISTENT, &pl))) sk_plan_form(B, K, iters, kn, SKF_MULTI, &pl);
     }
     // one-launch register-resident path when every workgroup can be resident (see sk_persistent_kernel)
-    const int cpl = (K + 63) / 64;
-    // K = 256 (the reference's codebook size): two rows per wave instead of four when that still fits 128 workgroups
-    // (B <= 2048) -- twice the CUs on the divisions, 22.2 k -> 18.9 k cycles per iteration.  LCREC_SK_RW=4 disables.
-    static const int rw_env = [] { const char *e = getenv("LCREC_SK_RW"); return e ? atoi(e) : 2; }();
-    const bool rw1 = rw_env == 1 && cpl == 4 && (B + 7) / 8 <= SKP_MAX_BLOCKS;           // LCREC_SK_RW=1 (tuning): 8 rows per workgroup
-    const bool rw2 = !rw1 && rw_env <= 2 && cpl == 4 && (B + 15) / 16 <= SKP_MAX_BLOCKS;
-    const int rows_p = rw1 ? 8 : rw2 ? 16 : cpl <= 4 ? 32 : (cpl <= 8 ? 16 : 8);
-    const int64_t nblk_p = (B + rows_p - 1) / rows_p;
-    static const bool allow_persistent = [] { const char *e = getenv("LCREC_SINKHORN_PERSISTENT"); return !e || atoi(e) != 0; }();
-    if (allow_persistent && nblk_p <= SKP_MAX_BLOCKS && nblk_p <= nblk * 4 && (3 * (int64_t)K + 1) * nblk_p + 3 * (int64_t)K <= B * (int64_t)K) {
+    if (pl.form == SKF_PERSISTENT) {
         SkPersist q;
+        const int64_t nblk_p = pl.workgroups;
         // the Q region ([B][K] doubles) is unused on this path and holds the exchange buffers:
-        // 3*nblk_p*K partials + 3*K sums + nblk_p totals (checked above)
+        // 3*nblk_p*K partials + 3*K sums + nblk_p totals (checked by the plan)
         q.d = d; q.col_part = p.Q; q.tot_part = p.Q + (size_t)3 * nblk_p * K + (size_t)3 * K; q.minmax = minmax;
         q.counter = minmax + 4; q.flag = minmax + 5;
         q.B = B; q.K = K; q.nblk = (int)nblk_p; q.iters = iters; q.eps = eps;
         q.idx_out = idx_out; q.idx_stride = idx_stride;
         bool launched;
-        if (cpl <= 1) launched = launch_skp<1, 4>(q, stream);
-        else if (cpl <= 2) launched = launch_skp<2, 4>(q, stream);
-        else if (rw1) launched = launch_skp<4, 1>(q, stream);
-        else if (rw2) launched = launch_skp<4, 2>(q, stream);
-        else if (cpl <= 4) launched = launch_skp<4, 4>(q, stream);
-        else if (cpl <= 8) launched = launch_skp<8, 2>(q, stream);
+        if (pl.cpl == 1) launched = launch_skp<1, 4>(q, stream);
+        else if (pl.cpl == 2) launched = launch_skp<2, 4>(q, stream);
+        else if (pl.cpl == 4 && pl.rw == 1) launched = launch_skp<4, 1>(q, stream);
+        else if (pl.cpl == 4 && pl.rw == 2) launched = launch_skp<4, 2>(q, stream);
+        else if (pl.cpl == 4) launched = launch_skp<4, 4>(q, stream);
+        else if (pl.cpl == 8) launched = launch_skp<8, 2>(q, stream);
         else launched = launch_skp<16, 1>(q, stream);
-        if (launched) return check_launch("sk_persistent_kernel");
+        if (launched) {
+            if (dbg) dbg->ran = pl.form;
+            return check_launch("sk_persistent_kernel");
+        }
+        if (want != SKF_AUTO) return fail(LCREC_EUNSUPPORTED, "sinkhorn: the runtime refused the launch of forced form %d (occupancy)", want);
     }
     hipLaunchKernelGGL(sk_init_kernel, dim3((unsigned)nblk), dim3(SK_THREADS), 0, stream, p);
     const size_t lds_iter = (size_t)(1 + SK_THREADS / 64) * K * sizeof(double);
@@ -1497,9 +1680,9 @@ static int sinkhorn_big(const float *r, int64_t B, int e, const float *cb, int K
         hipLaunchKernelGGL(sk_iter_kernel, dim3((unsigned)nblk), dim3(SK_THREADS), lds_iter, stream, p, t == 0 ? 0 : 1, src);
         src ^= 1;
     }
-    if (iters == 0) return fail(LCREC_EUNSUPPORTED, "sinkhorn: iters must be >= 1");
     hipLaunchKernelGGL(sk_final_kernel, dim3((unsigned)nblk), dim3(SK_THREADS), (size_t)K * sizeof(double), stream, p, src,
-                       idx_out, idx_stride);
+                       idx_out, idx_stride, runner_out, ratio_out);
+    if (dbg) dbg->ran = SKF_MULTI;
     return check_launch("sinkhorn kernels");
 }
 
@@ -1873,7 +2056,48 @@ int ema_update(float *ema_count, float *ema_sum, float *codebook, const float *c
     return check_launch("ema_update_kernel");
 }
 
+int debug_sinkhorn_plan(int64_t B, int K, int iters, int form, lcrec_sinkhorn_plan *out)
+{
+    if (!out) return fail(LCREC_EINVAL, "debug_sinkhorn_plan: NULL pointer");
+    return sk_batch_plan(B, K, iters, sk_knobs(), form, out);
+}
+
+int debug_sinkhorn_batch(const float *r, int64_t n, int e, const float *cb, int K, double eps, int iters, int64_t *idx_out,
+                         int64_t idx_stride, void *workspace, size_t workspace_bytes, unsigned *ticket, hipStream_t stream,
+                         int form, int64_t *runner_out, double *ratio_out, int *form_ran)
+{
+    if (form_ran) *form_ran = 0;
+    if (!r || !cb || !idx_out) return fail(LCREC_EINVAL, "debug_sinkhorn_batch: NULL pointer");
+    if ((runner_out == nullptr) != (ratio_out == nullptr))
+        return fail(LCREC_EINVAL, "debug_sinkhorn_batch: runner_out and ratio_out are given together");
+    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "debug_sinkhorn_batch: e_dim=%d (supported: 16, 32, 64)", e);
+    if (n < 1 || K < 1 || iters < 1 || !(eps > 0) || idx_stride < 1) return fail(LCREC_EINVAL, "debug_sinkhorn_batch: bad n/K/iters/eps/stride");
+    lcrec_sinkhorn_plan pl;
+    if (int rc = sk_batch_plan(n, K, iters, sk_knobs(), form, &pl)) return rc;
+    if (!workspace || workspace_bytes < (size_t)pl.workspace_bytes)
+        return fail(LCREC_EWORKSPACE, "debug_sinkhorn_batch: workspace %zu B < required %lld B", workspace_bytes, (long long)pl.workspace_bytes);
+    SkDebug dbg = {form, runner_out, ratio_out, 0};
+    const int rc = sinkhorn_big(r, n, e, cb, K, eps, iters, idx_out, idx_stride, reinterpret_cast<char *>(workspace), ticket, stream, &dbg);
+    if (form_ran) *form_ran = dbg.ran;
+    return rc;
+}
+
 }  // namespace lcrec
+
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_sinkhorn_plan(int64_t B, int K, int iters, int form, lcrec_sinkhorn_plan *out)
+{
+    return lcrec::debug_sinkhorn_plan(B, K, iters, form, out);
+}
+
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_sinkhorn_batch(const float *resid, int64_t n, int e, const float *codebook, int K,
+                                                                                double epsilon, int iters, int64_t *idx_out, int64_t idx_stride,
+                                                                                void *workspace, size_t workspace_bytes, unsigned int *ticket,
+                                                                                void *stream, int form, int64_t *runner_out, double *ratio_out,
+                                                                                int *form_ran)
+{
+    return lcrec::debug_sinkhorn_batch(resid, n, e, codebook, K, epsilon, iters, idx_out, idx_stride, workspace, workspace_bytes, ticket,
+                                       (hipStream_t)stream, form, runner_out, ratio_out, form_ran);
+}
 
 #ifdef LCREC_GEMM_STAMP
 extern "C" __attribute__((visibility("default"))) int lcrec_debug_sk_stamps(unsigned long long *out, int reset)

@@ -472,6 +472,50 @@ def sinkhorn_assign(resid, codebook, epsilon, iters, group_offsets=None, out=Non
     return out
 
 
+SK_FORMS = {0: "production's choice", 1: "scaling, XCD-local sets", 2: "scaling, agent scope", 3: "persistent", 4: "multi-launch"}
+
+
+def sinkhorn_plan(B, K, iters, form=0):
+    """The solver lcrec_sinkhorn_assign's batch-sized path takes for a lone [B, K] problem, or the forced `form` (SK_FORMS),
+    as a dict of the fields of lcrec_sinkhorn_plan (include/lcrec.h).  Host only: no GPU is needed.  LcrecError when the
+    form cannot take the shape."""
+    plan = _lib.SinkhornPlan()
+    rc = _lib.load().lcrec_debug_sinkhorn_plan(int(B), int(K), int(iters), int(form), ctypes.addressof(plan))
+    _lib.check(rc, "lcrec_debug_sinkhorn_plan")
+    return {name: int(getattr(plan, name)) for name, _ in _lib.SinkhornPlan._fields_}
+
+
+def sinkhorn_debug(resid, codebook, epsilon, iters, form=0, out=None, runner_out=None, ratio_out=None):
+    """lcrec_debug_sinkhorn_batch: all rows as one problem through the batch-sized solver `form` (SK_FORMS), with
+    production's kernels.  Returns (idx int64 [n], runner-up column int64 [n], second / best double [n], form that ran).
+    `out` may be a column view of [n, L]; outputs that are passed in keep whatever the solver does not write."""
+    lib = _lib.load()
+    resid = _dev(resid, "resid")
+    codebook = _dev(codebook, "codebook")
+    n, e = resid.shape
+    K = codebook.shape[0]
+    dev = resid.device
+    if out is None:
+        out = torch.zeros(n, dtype=torch.int64, device=dev)
+    out, stride = _idx_col(out, n)
+    if runner_out is None:
+        runner_out = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    if ratio_out is None:
+        ratio_out = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    for t, dt in ((runner_out, torch.int64), (ratio_out, torch.float64)):
+        if not t.is_cuda or t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
+            raise _lib.LcrecError("runner_out / ratio_out must be contiguous device vectors of length n (int64 / float64)")
+    nbytes = sinkhorn_plan(n, K, iters, form)["workspace_bytes"]
+    ran = ctypes.c_int(0)
+    with _on(dev):
+        ws = _workspace(nbytes, dev)
+        rc = lib.lcrec_debug_sinkhorn_batch(_ptr(resid), n, e, _ptr(codebook), K, float(epsilon), int(iters), _ptr(out), stride,
+                                            _ptr(ws), ws.numel(), _ptr(_ticket(dev)), _stream_ptr(), int(form),
+                                            _ptr(runner_out), _ptr(ratio_out), ctypes.byref(ran))
+    _lib.check(rc, "lcrec_debug_sinkhorn_batch")
+    return out, runner_out, ratio_out, ran.value
+
+
 _deferred = None
 _deferred_raw = False
 _POISON_MSG = ("lcrec_sinkhorn_assign: grid barrier timed out (device oversubscribed?); "

@@ -362,11 +362,27 @@ def _ref_sinkhorn_idx(z, cb, eps, iters):
     return torch.argmax(Q, -1).numpy(), margin
 
 
+# (solver, columns per lane, rows per wave) each shape below takes, solver as `form` of lcrec_debug_sinkhorn_plan: 1 scaling form
+# in eight XCD-local sets, 2 scaling form in one set, 3 persistent kernel, 4 multi-launch
+_SK_BATCH_FORMS = {(2048, 256): (1, 4, 16), (1000, 256): (1, 4, 8), (256, 256): (2, 4, 2), (300, 100): (3, 2, 4), (4096, 1024): (4, 16, 4),
+                   (1000, 1024): (1, 16, 4), (130, 256): (2, 4, 2), (500, 64): (1, 1, 4), (700, 128): (1, 2, 8), (1500, 512): (1, 8, 8),
+                   (3000, 256): (1, 4, 16), (600, 512): (1, 8, 8), (333, 192): (1, 4, 4)}
+
+
+def _sk_batch_form(hip, B, K):
+    p = hip.ops.sinkhorn_plan(B, K, 50)
+    assert p["batch_route"] == 1
+    return p["form"], p["cpl"], p["rw"]
+
+
 @pytest.mark.parametrize("B,K,e", [(2048, 256, 32), (1000, 256, 32), (256, 256, 32), (300, 100, 16), (4096, 1024, 32), (1000, 1024, 32),
                                    (130, 256, 64),
-                                   # every (columns per lane, rows per wave) form of the scaling-form solver: K = 64 .. 1024
+                                   # more (columns per lane, rows per wave) forms of the scaling-form solver, K = 64 .. 512: with the
+                                   # rows above, 8 of its 16 instantiations, one of the persistent kernel's 7 and the multi-launch
+                                   # solver (_SK_BATCH_FORMS).  tests/sinkhorn_cases.py has a row for every one, values included.
                                    (500, 64, 32), (700, 128, 16), (1500, 512, 32), (3000, 256, 32), (600, 512, 32), (333, 192, 32)])
 def test_sinkhorn_training_batch(hip, B, K, e):
+    assert _sk_batch_form(hip, B, K) == _SK_BATCH_FORMS[B, K]
     rs = _rs(B + K)
     z = rs.standard_normal((B, e)).astype(np.float32)
     cb = (0.8 * rs.standard_normal((K, e))).astype(np.float32)

@@ -536,6 +536,38 @@ int lcrec_collision_groups(const int64_t *idx, int64_t n, int L, const int *K, i
                            int64_t *group_offsets_out, int64_t *counters_out, void *workspace,
                            size_t workspace_bytes, void *stream);
 
+/* Nearest-free-code finishing pass: an opt-in step BEYOND the reference.  index/generate_indices.py:107-136 stops after its 20
+ * conflict rounds and writes out whatever still collides; this entry follows on from there and gives every item that still shares
+ * its tuple a free code of the LAST level.  Only last-level codes change, and only those of the items that move.
+ *
+ * The rule.  d(i,k) = (xx_i + cc_k) - 2*dot(i,k) with xx, cc and dot each one fp32 fma chain over the dimension ascending from 0:
+ * the distance of lcrec_rq_assign, bit for bit.  Wherever two distances are compared a NaN counts as +inf.
+ *   1. A bucket is the set of items that share idx[:, :L-1] (L = 1: one bucket of all items).  Only buckets in which some last
+ *      code is held by two or more items are touched.
+ *   2. Keepers: for each last code k held by >= 2 items of a bucket, the holder with the smallest d(i,k) keeps it; a tie goes to
+ *      the lowest item id.  The other holders are movers.
+ *   3. Occupied codes: every code held by any item of the bucket, items that collide with nobody included.
+ *   4. Movers, in ascending item id: each takes the free code with the smallest d(i,k), the first minimum in code order; that code
+ *      is occupied before the next mover looks.  When no code is free, this mover and all later ones of the bucket keep their code
+ *      and count as unresolved.
+ * So a moved item collides with nobody, the number of colliding items afterwards is exactly `unresolved`, and unresolved is 0
+ * whenever no touched bucket has more items than K[L-1].  The result is a function of the inputs alone.
+ *
+ *   idx             device [n][L] int64, in/out (column L-1 of the movers is rewritten); n < 2^32
+ *   K               host [L]; only K[L-1] is used
+ *   resid_last      device [n][e] float: the residual entering the last level; e in {16, 32, 64}
+ *   codebook_last   device [K[L-1]][e] float; a level lcrec_rq_assign takes (160 KB of LDS)
+ *   bucket_members, bucket_offsets   device int64, the layout lcrec_collision_groups emits: bucket b =
+ *                   members[off[b] .. off[b+1]), item ids ascending inside a bucket.  Buckets that turn out untouched cost a
+ *                   histogram and nothing else, so the groups of idx[:, :L-1] can be passed as they come.  A member whose id is
+ *                   outside [0, n) or whose last code is outside [0, K[L-1]) takes no part.
+ *   counters_out    device int64[2]: {moved, unresolved}, zeroed by the call
+ * n_buckets == 0: no launch, the counters are zeroed.  resid_last and codebook_last 16-byte aligned, the int64 arrays 8-byte.
+ * Argument errors are reported before anything is enqueued.  No workspace, no allocation, no synchronisation, capturable. */
+int lcrec_finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e,
+                              const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets,
+                              int64_t n_buckets, int64_t *counters_out, void *stream);
+
 /* Text of the `.index.json` entries for a run of items (host-side; no device work).  Replaces the
  * per-item Python of index/generate_indices.py:83-92 (token strings "<a_{i}>", "<b_{j}>", ...) and the
  * json.dump of :138-145, whose default separators (", " and ": ") every consumer relies on

@@ -28,7 +28,7 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "collision_groups", "linear_fwd_pp_256x128", "linear_fwd_64x64", "sinkhorn_slab",
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
-                                           "optim_step", "dropout", "cast_rows"};
+                                           "optim_step", "dropout", "cast_rows", "finish_nearest_free"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -376,6 +376,14 @@ LCREC_API int lcrec_collision_groups(const int64_t *idx, int64_t n, int L, const
 {
     return collision_groups(idx, n, L, K, members_out, group_offsets_out, counters_out, workspace, workspace_bytes,
                             (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e,
+                                        const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets,
+                                        int64_t n_buckets, int64_t *counters_out, void *stream)
+{
+    return finish_nearest_free(idx, n, L, K, resid_last, e, codebook_last, bucket_members, bucket_offsets, n_buckets, counters_out,
+                               (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_bn_relu_forward(const float *t, int64_t n, int features, const float *gamma, const float *beta, float eps,

@@ -31,7 +31,7 @@ inline int check_launch(const char *what)
 enum KernelId { K_LINEAR_128x128 = 0, K_LINEAR_128x64, K_LINEAR_128x32, K_RQ_ASSIGN, K_RQ_SSE_FINALIZE,
                 K_VQ_DISTANCE, K_SINKHORN, K_SINKHORN_SMALL, K_APPLY_LEVEL, K_CODE_STATS, K_EMA_UPDATE, K_COLLISION,
                 K_LINEAR_PP, K_LINEAR_64x64, K_SINKHORN_SLAB, K_SINKHORN_TINY, K_BN_FWD, K_BN_BWD, K_RELU_BIAS_BWD, K_LOSS,
-                K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_COUNT };
+                K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_FINISH, K_COUNT };
 extern const char *const kKernelNames[K_COUNT];
 bool trace_on();
 void trace_begin(int kernel, hipStream_t stream);
@@ -219,6 +219,10 @@ int code_stats_levels(const int64_t *idx, const float *const *resid, int64_t n, 
 size_t collision_workspace(int64_t n, int L);
 int collision_groups(const int64_t *idx, int64_t n, int L, const int *K, int64_t *members_out, int64_t *offsets_out,
                      int64_t *counters_out, void *workspace, size_t workspace_bytes, hipStream_t stream);
+bool rq_level_fits(int K, int e, int L);   // whether rq_assign takes a level of K codes (its 256-thread form's LDS need)
+int finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e, const float *codebook_last,
+                        const int64_t *bucket_members, const int64_t *bucket_offsets, int64_t n_buckets, int64_t *counters_out,
+                        hipStream_t stream);
 int ema_update(float *ema_count, float *ema_sum, float *codebook, const float *count, const float *sum, int K, int e,
                float decay, float alpha, float keep, float eps, const unsigned char *skip, hipStream_t stream);
 

@@ -1,0 +1,297 @@
+// Nearest-free-code finishing pass over the tuples the conflict rounds leave colliding (opt-in, --finish nearest_free).
+//
+// The reference stops after its 20 Sinkhorn rounds (index/generate_indices.py:107-128) and writes whatever still collides
+// (:131-136 only print the rate).  This pass follows on from there and goes BEYOND the reference: every item that still shares
+// its tuple with another is given a free code of the LAST level, chosen by the quantiser's own distance.  Nothing above the last
+// level moves, and no item that collides with nobody moves.
+//
+// The rule (include/lcrec.h, lcrec_finish_nearest_free, is the contract; tests/finish_ref.py restates it in numpy):
+//   d(i,k) = (xx_i + cc_k) - 2*dot(i,k), xx / cc / dot each one fp32 fma chain over the dimension ascending -- rq_assign.hip's
+//   bits, oracle/lcrec_oracle.c's lcrec_oracle_distances.  Wherever distances are compared a NaN counts as +inf, so it never
+//   beats anything (rq_assign's `d < best` from best = +inf).
+//   bucket   = the items sharing idx[:, :L-1]; the caller lists the buckets as (members, offsets), ids ascending in a bucket
+//   keepers  : for every last code held by >= 2 items of the bucket the holder with the smallest d keeps it (tie: lowest id);
+//              the other holders are movers
+//   movers   : in ascending id each takes the free code with the smallest d (tie: lowest code), which is occupied from then on;
+//              when no code is free this mover and all later ones of the bucket stay where they are: `unresolved`
+//
+// Shape: one 256-thread workgroup per bucket.
+//   1. histogram of the bucket's last codes in LDS; a bucket without a doubly held code ends here, before anything is staged;
+//   2. the codebook goes to LDS once (row stride E + 1 floats: 32 consecutive rows on 32 banks for ds_read_b32), then cc;
+//   3. keepers, parallel over members: one chain d(i, own code) each, ds_min_u64 per code on {ordered distance bits, position in
+//      the bucket} -- positions ascend with the item id, so the lowest id wins a tie in the same operation;
+//   4. movers, sequential: thread t evaluates the full chain of the free codes t, t+256, ...; a wave64 shuffle reduction and one
+//      LDS step across the four waves pick (distance, lowest code); the code's owner thread marks it occupied.
+// The mover loop stops evaluating when the free count reaches zero -- the rest is counted -- so no bucket takes more than K
+// sequential steps whatever its size.  Nothing crosses workgroups: no flag, no spin; the only global atomics are the two counters.
+#include "common.h"
+
+namespace lcrec {
+
+constexpr int FIN_THREADS = 256;
+constexpr int FIN_WAVES = FIN_THREADS / 64;
+
+struct FinishParams {
+    int64_t *idx;            // [n][L]
+    int64_t n;
+    int L, K;                // K of the last level
+    const float *resid;      // [n][E]
+    const float *cb;         // [K][E]
+    const int64_t *members, *offsets;
+    unsigned long long *counters;   // {moved, unresolved}
+};
+
+// unsigned order of the result == float order of d; NaN -> +inf, -0 -> +0
+__device__ __forceinline__ uint32_t ordered_bits(float d)
+{
+    if (!(d == d)) d = __builtin_inff();
+    if (d == 0.f) d = 0.f;
+    const uint32_t u = __float_as_uint(d);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+template <int E>
+__device__ __forceinline__ void load_row(const float *__restrict__ src, float (&x)[E])
+{
+    const f32x4 *s = reinterpret_cast<const f32x4 *>(src);
+#pragma unroll
+    for (int q = 0; q < E / 4; ++q) {
+        const f32x4 v = s[q];
+        x[4 * q] = v[0]; x[4 * q + 1] = v[1]; x[4 * q + 2] = v[2]; x[4 * q + 3] = v[3];
+    }
+}
+
+template <int E>
+__device__ __forceinline__ float distance(const float (&x)[E], float xx, const float *crow, float cc)
+{
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < E; ++k) dot = __builtin_fmaf(x[k], crow[k], dot);
+    const float t = xx + cc;
+    return t - 2.0f * dot;
+}
+
+template <int E>
+__global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(FinishParams p)
+{
+    constexpr int S = E + 1;   // LDS row stride (floats)
+    extern __shared__ __attribute__((aligned(16))) unsigned char fin_smem[];
+    const int K = p.K;
+    unsigned long long *key = reinterpret_cast<unsigned long long *>(fin_smem);   // [K] {ordered distance, position}: the keeper
+    float *cbs = reinterpret_cast<float *>(key + K);                              // [K][S]
+    float *ccs = cbs + (size_t)K * S;                                             // [K]
+    int *cnt = reinterpret_cast<int *>(ccs + K);                                  // [K] holders, then 1 for a code a mover took
+    __shared__ unsigned long long wmask[FIN_WAVES];
+    __shared__ float red_d[2][FIN_WAVES];
+    __shared__ int red_k[2][FIN_WAVES];
+    __shared__ int sum_sh[FIN_WAVES];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t lo = p.offsets[blockIdx.x], hi = p.offsets[blockIdx.x + 1];
+    const int64_t m = hi > lo ? hi - lo : 0;
+    const int64_t *mem = p.members + lo;
+    const int L = p.L;
+
+    // a member takes part when its id and its code are in range; any other is left alone (nothing is read or written for it)
+    auto code_of = [&](int64_t pos, int64_t &id) -> int {
+        id = mem[pos];
+        if (id < 0 || id >= p.n) return -1;
+        const int64_t c = p.idx[id * L + (L - 1)];
+        return (c < 0 || c >= K) ? -1 : (int)c;
+    };
+
+    // ---- 1. holders per code
+    for (int k = tid; k < K; k += FIN_THREADS) { cnt[k] = 0; key[k] = ~0ull; }
+    __syncthreads();
+    for (int64_t pos = tid; pos < m; pos += FIN_THREADS) {
+        int64_t id;
+        const int c = code_of(pos, id);
+        if (c >= 0) atomicAdd(&cnt[c], 1);
+    }
+    __syncthreads();
+    int twice = 0, used = 0;
+    for (int k = tid; k < K; k += FIN_THREADS) {
+        twice |= cnt[k] >= 2;
+        used += cnt[k] > 0;
+    }
+    if (!__syncthreads_or(twice)) return;                                         // untouched bucket (the whole workgroup leaves)
+
+    // ---- 2. codebook and cc
+    for (int q = tid; q < K * (E / 4); q += FIN_THREADS) {
+        const int row = q / (E / 4), g = q % (E / 4);
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(p.cb + (size_t)row * E + 4 * g);
+        float *dst = cbs + row * S + 4 * g;
+        dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) used += __shfl_xor(used, o, 64);
+    if (lane == 0) sum_sh[wave] = used;
+    __syncthreads();
+    int free_codes = K;
+#pragma unroll
+    for (int w = 0; w < FIN_WAVES; ++w) free_codes -= sum_sh[w];
+    free_codes = __builtin_amdgcn_readfirstlane(free_codes);                      // (the same in every lane: say so, for scalar branches)
+    for (int k = tid; k < K; k += FIN_THREADS) {
+        const float *cr = cbs + k * S;
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < E; ++j) a = __builtin_fmaf(cr[j], cr[j], a);
+        ccs[k] = a;
+    }
+    __syncthreads();
+
+    // ---- 3. keepers
+    for (int64_t pos = tid; pos < m; pos += FIN_THREADS) {
+        int64_t id;
+        const int c = code_of(pos, id);
+        if (c < 0 || cnt[c] < 2) continue;
+        float x[E];
+        load_row<E>(p.resid + id * E, x);
+        float xx = 0.f;
+#pragma unroll
+        for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
+        const float d = distance<E>(x, xx, cbs + c * S, ccs[c]);
+        atomicMin(&key[c], ((unsigned long long)ordered_bits(d) << 32) | (unsigned long long)(uint32_t)pos);
+    }
+    __syncthreads();
+
+    // ---- 4. movers, in position (= id) order, a chunk of 256 positions at a time
+    // free_codes, moved, late and step are the same in every thread: each derives them from the same LDS values.
+    unsigned long long moved = 0, late = 0;   // late: movers met after the last free code went, counted one by one
+    unsigned my_late = 0;                      // ... and those of whole chunks after that, counted in parallel
+    unsigned step = 0;
+    for (int64_t base = 0; base < m; base += FIN_THREADS) {
+        const int64_t pos = base + tid;
+        bool mover = false;
+        if (pos < m) {
+            int64_t id;
+            const int c = code_of(pos, id);
+            mover = c >= 0 && cnt[c] >= 2 && (uint32_t)key[c] != (uint32_t)pos;
+        }
+        if (free_codes == 0) { my_late += mover; continue; }
+        const unsigned long long mine = __ballot(mover);
+        if (lane == 0) wmask[wave] = mine;
+        __syncthreads();
+        unsigned long long masks[FIN_WAVES];
+#pragma unroll
+        for (int w = 0; w < FIN_WAVES; ++w) {
+            const unsigned long long v = wmask[w];
+            masks[w] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
+                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);   // (it returns int)
+        }
+#pragma unroll
+        for (int w = 0; w < FIN_WAVES; ++w) {
+            unsigned long long mask = masks[w];
+            while (mask) {
+                if (free_codes == 0) { late += __builtin_popcountll(mask); break; }
+                const int bit = __builtin_ctzll(mask);
+                mask &= mask - 1;
+                const int64_t id = mem[base + w * 64 + bit];                      // in range: it was found a mover above
+                float x[E];
+                load_row<E>(p.resid + id * E, x);
+                float xx = 0.f;
+#pragma unroll
+                for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
+                float best = __builtin_inff();
+                int bk = 0x7fffffff;
+                for (int k = tid; k < K; k += FIN_THREADS) {
+                    if (cnt[k] != 0) continue;
+                    float d = distance<E>(x, xx, cbs + k * S, ccs[k]);
+                    if (!(d == d)) d = __builtin_inff();
+                    if (bk == 0x7fffffff || d < best) { best = d; bk = k; }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const float od = __shfl_xor(best, o, 64);
+                    const int ok = __shfl_xor(bk, o, 64);
+                    if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
+                }
+                const int par = step & 1;   // two hand-over buffers: a wave can be one step ahead of another, never two
+                ++step;
+                if (lane == 0) { red_d[par][wave] = best; red_k[par][wave] = bk; }
+                __syncthreads();
+                best = red_d[par][0]; bk = red_k[par][0];
+#pragma unroll
+                for (int v = 1; v < FIN_WAVES; ++v) {
+                    const float od = red_d[par][v];
+                    const int ok = red_k[par][v];
+                    if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
+                }
+                bk = __builtin_amdgcn_readfirstlane(bk);
+                // free_codes > 0, so bk is a code; its owner is the only thread that reads cnt[bk] in this loop
+                if (tid == (bk & (FIN_THREADS - 1))) {
+                    cnt[bk] = 1;
+                    p.idx[id * L + (L - 1)] = (int64_t)bk;
+                }
+                ++moved;
+                --free_codes;
+            }
+        }
+        __syncthreads();   // wmask is rewritten by the next chunk
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) my_late += __shfl_xor(my_late, o, 64);
+    __syncthreads();
+    if (lane == 0) sum_sh[wave] = (int)my_late;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 0; w < FIN_WAVES; ++w) late += (unsigned)sum_sh[w];
+        if (moved) atomicAdd(&p.counters[0], moved);
+        if (late) atomicAdd(&p.counters[1], late);
+    }
+}
+
+static size_t finish_lds_bytes(int K, int e)
+{
+    return (size_t)K * (8 + (size_t)(e + 1) * 4 + 4 + 4);   // key, codebook row, cc, cnt
+}
+
+template <int E>
+static int finish_launch(const FinishParams &p, int64_t n_buckets, size_t lds, hipStream_t stream)
+{
+    auto kern = finish_nearest_free_kernel<E>;
+    hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (he != hipSuccess)
+        return fail(LCREC_EHIP, "finish_nearest_free: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(he));
+    TraceScope trace(K_FINISH, stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_buckets), dim3(FIN_THREADS), lds, stream, p);
+    return check_launch("finish_nearest_free_kernel");
+}
+
+int finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e, const float *codebook_last,
+                        const int64_t *bucket_members, const int64_t *bucket_offsets, int64_t n_buckets, int64_t *counters_out,
+                        hipStream_t stream)
+{
+    if (!counters_out) return fail(LCREC_EINVAL, "finish_nearest_free: counters_out is NULL");
+    if (!K) return fail(LCREC_EINVAL, "finish_nearest_free: K is NULL");
+    if (L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "finish_nearest_free: L=%d (1 .. %d)", L, LCREC_MAX_LEVELS);
+    if (n < 0 || n > 0xffffffffLL) return fail(LCREC_EINVAL, "finish_nearest_free: n=%lld (0 .. 2^32 - 1)", (long long)n);
+    if (n_buckets < 0 || n_buckets > 0x7fffffffLL)
+        return fail(LCREC_EINVAL, "finish_nearest_free: n_buckets=%lld (0 .. 2^31 - 1)", (long long)n_buckets);
+    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "finish_nearest_free: e_dim=%d (supported: 16, 32, 64)", e);
+    const int Kl = K[L - 1];
+    if (Kl <= 0) return fail(LCREC_EINVAL, "finish_nearest_free: K[%d]=%d", L - 1, Kl);
+    const size_t lds = finish_lds_bytes(Kl, e);
+    if (!rq_level_fits(Kl, e, L) || lds + 512 > 160 * 1024)
+        return fail(LCREC_EUNSUPPORTED, "finish_nearest_free: level %d (K=%d, e=%d) does not fit in 160 KB of LDS", L - 1, Kl, e);
+    if (((uintptr_t)resid_last | (uintptr_t)codebook_last) & 15)
+        return fail(LCREC_EINVAL, "finish_nearest_free: resid_last and codebook_last must be 16-byte aligned");
+    if (((uintptr_t)idx | (uintptr_t)bucket_members | (uintptr_t)bucket_offsets | (uintptr_t)counters_out) & 7)
+        return fail(LCREC_EINVAL, "finish_nearest_free: idx, bucket_members, bucket_offsets and counters_out must be 8-byte aligned");
+    if (n_buckets > 0 && (!idx || !resid_last || !codebook_last || !bucket_members || !bucket_offsets))
+        return fail(LCREC_EINVAL, "finish_nearest_free: NULL pointer");
+    hipError_t he = hipMemsetAsync(counters_out, 0, 2 * sizeof(int64_t), stream);
+    if (he != hipSuccess) return fail(LCREC_EHIP, "finish_nearest_free: %s", hipGetErrorString(he));
+    if (n_buckets == 0 || n == 0) return LCREC_OK;
+
+    FinishParams p;
+    p.idx = idx; p.n = n; p.L = L; p.K = Kl;
+    p.resid = resid_last; p.cb = codebook_last;
+    p.members = bucket_members; p.offsets = bucket_offsets;
+    p.counters = reinterpret_cast<unsigned long long *>(counters_out);
+    if (e == 16) return finish_launch<16>(p, n_buckets, lds, stream);
+    if (e == 32) return finish_launch<32>(p, n_buckets, lds, stream);
+    return finish_launch<64>(p, n_buckets, lds, stream);
+}
+
+}  // namespace lcrec

@@ -410,6 +410,8 @@ static size_t lds_bytes(int rows, int E, int L, int waves, bool split = false)
            (split ? (size_t)2 * waves * 64 * 3 * sizeof(float) : 0);      // the split form's hand-over buffers
 }
 
+bool rq_level_fits(int K, int e, int L) { return K > 0 && lds_bytes((K + 31) & ~31, e, L, 4) <= LDS_BUDGET; }
+
 static int threads_for(int e, int64_t n)
 {
     if (e == 64) return 256;             // 512-register budget per lane

@@ -17,6 +17,8 @@ re-assigned), so batching them does not change the result.
 
 Documented divergences from the reference script:
   * its 5-entry prefix list (:83) raises IndexError for L > 5; here prefixes continue <f_..>, <g_..>;
+  * --finish nearest_free (off by default; `none` writes the reference's bytes) goes BEYOND the reference: after the rounds every
+    item that still shares its tuple gets the nearest free last-level code (finish_collisions);
   * it stores tokens in fixed-width numpy unicode arrays (:98-99) which silently truncate a
     replacement longer than anything seen in pass 1; integer tuples are kept here, and a warning is
     logged if a run ever hits that case (the reference's output would be corrupt there).
@@ -35,6 +37,7 @@ from .rqvae import RQVAE
 
 PREFIX = ["<{}_{{}}>".format(chr(ord("a") + i)) for i in range(26)]   # "<a_{}>", "<b_{}>", ... (:83 has a..e)
 MAX_ROUNDS = 20                                                        # :110
+FINISH_MODES = ("none", "nearest_free")
 log = logging.getLogger(__name__)
 
 
@@ -195,6 +198,32 @@ def resolve_collisions(model, idx, resid_last, ks, max_rounds=MAX_ROUNDS, on_rou
     return idx, history
 
 
+# ---- opt-in: what the rounds leave colliding gets the nearest free last-level code (--finish nearest_free) ------------------------
+@torch.no_grad()
+def finish_collisions(model, idx, resid_last, ks):
+    """Beyond the reference (which stops at :128 and writes what still collides): ops.finish_nearest_free over the buckets of
+    items sharing idx[:, :L-1] -- include/lcrec.h, lcrec_finish_nearest_free, states the rule.  Only the last-level code of the
+    items that move changes.  Mutates idx; returns dict(moved, unresolved, buckets, largest_bucket).  Afterwards exactly
+    `unresolved` items still collide: 0 unless a bucket with a shared code holds more items than the last level has codes.
+    A function of its inputs alone: under torchrun every rank runs it on its identical copy, with no collective."""
+    levels = list(model.rq.vq_layers)
+    cb_last = levels[-1].embedding.weight.detach().contiguous()
+    n, L = idx.shape
+    dev = idx.device
+    if L == 1:                                             # one bucket of all items
+        members = torch.arange(n, dtype=torch.int64, device=dev)
+        offsets = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        buckets, largest = (1, n) if n else (0, 0)
+        if not n:
+            offsets = offsets[:1]
+    else:
+        found = ops.collision_groups(idx[:, :L - 1].contiguous(), ks[:-1], want_groups="device")
+        members, offsets = found["members"], found["offsets"]
+        buckets, largest = found["n_groups"], found["max_count"] if found["n_groups"] else 0
+    moved, unresolved = ops.finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets)
+    return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
+
+
 # ---- opt-in: re-evaluate near-tie items in the reference's own operation order (--recheck_neartie) -----------------------------
 def reference_order_indices(state_dict, n_layers, bn, levels, x, eps=1e-5):
     """RQVAE.get_indices(x, use_sk=False) (rqvae.py:68-72) as the reference's torch CPU op sequence on ONE batch `x` (a CPU
@@ -332,9 +361,10 @@ def sharded_assign(ctx, data, assign_fn, device):
 
 
 def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=True, ctx=None, trust_checkpoint=False,
-             recheck=False):
+             recheck=False, finish="none"):
     """Whole flow of generate_indices.py:51-145.  Returns a dict of the statistics it prints.
     recheck: re-evaluate the near-tie items of pass 1 in the reference's CPU operation order (recheck_neartie).
+    finish: "none" (the reference's bytes) or "nearest_free" (finish_collisions after the rounds; beyond the reference).
 
     Under torchrun (ctx = dist.init_from_env()) pass 1 is item-sharded over the ranks and each conflict round's
     groups are sharded too (resolve_collisions); rank 0 writes the file."""
@@ -342,6 +372,8 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
     ctx = ctx or ldist.current()
     lead = ctx.rank == 0
     verbose = verbose and lead
+    if finish not in FINISH_MODES:
+        raise ValueError(f"finish={finish!r}: one of {FINISH_MODES}")
     ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
     args = ckpt["args"]
     data = EmbDataset(data_path or args.data_path, mmap=ctx.enabled or str(device).startswith("cuda"))
@@ -374,12 +406,24 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
             print(n_groups)
 
     idx, history = resolve_collisions(model, idx, resid_last, ks, on_round=show, ctx=ctx)
+    finished = {"moved": 0, "unresolved": 0}
+    if finish == "nearest_free":
+        finished = finish_collisions(model, idx, resid_last, ks)          # every rank, on its identical copy: no collective
+        if lead:
+            log.info("--finish nearest_free: %d items moved to the nearest free last-level code, %d unresolved "
+                     "(%d buckets listed, largest %d items)", finished["moved"], finished["unresolved"], finished["buckets"],
+                     finished["largest_bucket"])
+            if finished["unresolved"]:
+                log.warning("--finish nearest_free: %d items still collide: the largest bucket (items sharing all codes but the "
+                            "last) holds %d items, the last level has %d codes", finished["unresolved"],
+                            finished["largest_bucket"], ks[-1])
     _warn_if_reference_would_truncate(first_pass, idx)
     final = ops.collision_groups(idx, ks, want_groups=False)
     n = idx.shape[0]
     stats = {"items": n, "max_conflicts": final["max_count"], "collision_rate": (n - final["unique"]) / n if n else 0.0,
              "rounds": len(history), "groups_per_round": history, "neartie_items": neartie_items,
-             "neartie_tau": ops.NEARTIE_TAU, "rechecked_items": rechecked[0], "recheck_changed": rechecked[1]}
+             "neartie_tau": ops.NEARTIE_TAU, "rechecked_items": rechecked[0], "recheck_changed": rechecked[1],
+             "finish": finish, "finish_moved": finished["moved"], "finish_unresolved": finished["unresolved"]}
     if lead:
         log.info("near-tie items in pass 1: %d of %d (top-2 code gap <= %.3g x distance magnitude at some level); only "
                  "these could receive a different tuple from a CPU run of the reference", neartie_items, n, ops.NEARTIE_TAU)
@@ -394,7 +438,7 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
     return stats
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Generate <dataset>.index.json from an RQ-VAE checkpoint")
     ap.add_argument("--dataset", type=str, default="Games")
     ap.add_argument("--ckpt_path", type=str, required=True)
@@ -407,13 +451,21 @@ def main(argv=None):
                          "CPU run of the reference can index differently; the outcome depends on the host's BLAS)")
     ap.add_argument("--trust_checkpoint", action="store_true",
                     help="load the checkpoint with the unrestricted unpickler (executes code from the file)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--finish", choices=FINISH_MODES, default="none",
+                    help="after the conflict rounds: none = write what still collides, as the reference does (byte-identical "
+                         "output); nearest_free = every item that still shares its tuple gets the nearest free last-level code "
+                         "(goes beyond the reference; only those items' last token changes)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     from . import dist as ldist
     ctx = ldist.init_from_env(a)                       # torchrun: one rank per GPU; plain python: inert
     out = os.path.join(a.output_dir, f"{a.dataset}.index.json")
     try:
         return generate(a.ckpt_path, out, device=a.device, data_path=a.data_path, ctx=ctx,
-                        trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie)
+                        trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish)
     finally:
         ldist.shutdown(ctx)
 

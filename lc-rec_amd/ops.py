@@ -701,6 +701,39 @@ def collision_groups(idx, ks, want_groups=True):
     return out
 
 
+def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
+    """The nearest-free-code finishing pass (lcrec_finish_nearest_free of include/lcrec.h, which states the rule): every item of
+    a bucket -- `members[offsets[b]:offsets[b+1]]`, the items sharing idx[:, :L-1], ids ascending -- that still shares its last
+    code with another gets the nearest free last-level code; the holder nearest to a shared code keeps it.  Beyond the reference,
+    which stops after its conflict rounds (generate_indices.py:107-136).
+
+    idx int64 [n, L] is updated IN PLACE (last column, movers only); resid_last float32 [n, e] is the residual entering the last
+    level, cb_last float32 [K_last, e]; members / offsets are int64 device tensors in collision_groups' "device" layout.
+    Returns (moved, unresolved); afterwards exactly `unresolved` items of the listed buckets still collide."""
+    lib = _lib.load()
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2 and idx.is_contiguous()):
+        raise _lib.LcrecError("idx must be a contiguous int64 [n, L] device tensor (it is updated in place)")
+    n, L = idx.shape
+    resid_last, cb_last = _dev(resid_last, "resid_last"), _dev(cb_last, "cb_last")
+    for name, t in (("members", members), ("offsets", offsets)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
+            raise _lib.LcrecError(f"{name} must be an int64 [*] device tensor")
+    members, offsets = members.contiguous(), offsets.contiguous()
+    if resid_last.dim() != 2 or cb_last.dim() != 2 or resid_last.shape[0] != n or resid_last.shape[1] != cb_last.shape[1]:
+        raise _lib.LcrecError(f"resid_last {tuple(resid_last.shape)} and cb_last {tuple(cb_last.shape)} do not go with idx {(n, L)}")
+    if len(ks) != L or int(ks[-1]) != cb_last.shape[0]:
+        raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}] and cb_last [{cb_last.shape[0]}, *]")
+    n_buckets = max(offsets.numel() - 1, 0)
+    dev = idx.device
+    counters = torch.empty(2, dtype=torch.int64, device=dev)
+    with _on(dev):
+        rc = lib.lcrec_finish_nearest_free(_ptr(idx), n, L, _ints(ks), _ptr(resid_last), resid_last.shape[1], _ptr(cb_last),
+                                           _ptr(members), _ptr(offsets), n_buckets, _ptr(counters), _stream_ptr())
+    _lib.check(rc, "lcrec_finish_nearest_free")
+    moved, unresolved = counters.tolist()
+    return moved, unresolved
+
+
 def index_json_text(idx_rows, first_item=0):
     """bytes of the `.index.json` entries of items first_item.. for a HOST int64 [n, L] array
     (generate_indices.py:83-92,138-145; see lcrec_index_json_format in include/lcrec.h)."""

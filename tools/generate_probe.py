@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Wall-clock of the index-emission flow (generate_indices.py:51-145) at BASELINE sizes on one GPU:
-pass 1 (encode + assign), the conflict rounds, the .index.json text.
+pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing pass, the .index.json text.
 
     python tools/generate_probe.py [--items 1000000] [--in_dim 768] [--levels 4] [--codes 256]
 """
@@ -73,6 +73,7 @@ def main():
 
     w_idx, w_resid, w_ks = gen.assign_all(model, x[:300_000])   # warm-up: every kernel form and both helper streams used once
     gen.resolve_collisions(model, w_idx, w_resid, w_ks)
+    gen.finish_collisions(model, w_idx, w_resid, w_ks)
     # Pass 1, first time at full size.  What the round-1 version of this probe timed here -- and sometimes saw take 185 ms
     # instead of 62 -- includes every first-time allocation at the 1 M-item sizes (idx 32 MB, latents 128 MB, the
     # [L][n][e] residual stack 512 MB, its clone): the allocator statistics around the call say whether it went to the device
@@ -105,6 +106,12 @@ def main():
     trace = ops.trace_collect()
     ops.trace_enable(False)
     final = ops.collision_groups(idx, ks, want_groups=False)
+    # --finish nearest_free on what the rounds left: the pass alone (the prefix sort that lists the buckets, then the kernel)
+    ops.trace_enable(True)
+    fin, t_finish = timed(lambda: gen.finish_collisions(model, idx, resid_last, ks))
+    ftrace = ops.trace_collect()
+    ops.trace_enable(False)
+    finished = ops.collision_groups(idx, ks, want_groups=False)
     _, t_json = timed(lambda: gen.dump_index_json(idx, a.out))
     size = os.path.getsize(a.out)
     os.remove(a.out)
@@ -113,6 +120,10 @@ def main():
     print(f"conflict rounds ({len(history):2d})     {t_rounds * 1e3:9.1f} ms   groups/round {history[:6]}{' ...' if len(history) > 6 else ''}")
     print("  kernels: " + ", ".join(f"{k} {v[1]:.1f} ms/{v[0]}" for k, v in sorted(trace.items(), key=lambda kv: -kv[1][1])))
     print(f"  collision rate {first['collision_rate']:.6f} -> {final['collision_rate']:.6f}")
+    print(f"finish nearest_free      {t_finish * 1e3:9.1f} ms   (conflict rounds: {t_rounds * 1e3:.1f} ms)   buckets {fin['buckets']}, "
+          f"largest {fin['largest_bucket']} items, moved {fin['moved']}, unresolved {fin['unresolved']}")
+    print("  kernels: " + ", ".join(f"{k} {v[1]:.2f} ms/{v[0]}" for k, v in sorted(ftrace.items(), key=lambda kv: -kv[1][1])))
+    print(f"  collision rate {final['collision_rate']:.6f} -> {finished['collision_rate']:.6f}")
     print(f".index.json ({size / 1e6:.0f} MB)     {t_json * 1e3:9.1f} ms   {a.items / t_json / 1e6:7.2f} M items/s (D2H + text + write)")
 
 

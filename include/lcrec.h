@@ -628,6 +628,43 @@ int lcrec_debug_sinkhorn_batch(const float *resid, int64_t n, int e, const float
                                unsigned int *ticket, void *stream, int form, int64_t *runner_out, double *ratio_out,
                                int *form_ran);
 
+/* lcrec_rq_assign picks a form of its kernel by shape: the split form (one 64-item tile per 256-thread workgroup, a level's
+ * 32-code blocks dealt over its four waves) or one tile per wave, 256 or 512 threads, a grid, and a greedy packing of consecutive
+ * levels into launches whose codebooks fit in LDS.  lcrec_debug_rq_assign_plan reports that choice and its geometry,
+ * lcrec_debug_rq_assign runs it.
+ *   force_split    -1 = what lcrec_rq_assign chooses; 0 = one tile per wave; 1 = the split form (256 threads)
+ *   force_threads  0 = what lcrec_rq_assign chooses; 256 or 512
+ *   force_grid     0 = what lcrec_rq_assign chooses; else 1 .. that choice for the form (fewer workgroups: more trips of the
+ *                  tile loop at a small n)
+ * A forced form that cannot take the shape is LCREC_EUNSUPPORTED, never another form: 512 threads with e = 64 or with the split
+ * form, the split form when its hand-over buffers push a level out of LDS, a grid out of range. */
+typedef struct {
+    int split;                /* 1 = split form */
+    int threads;              /* 256 or 512 */
+    int grid;                 /* workgroups of every launch */
+    int64_t tiles;            /* ceil(n / 64) */
+    int64_t trips_max, trips_min;   /* trips of the tile loop: per workgroup in the split form, per wave otherwise (0: a wave idles) */
+    int launches;
+    /* per launch i < launches: levels l0[i] .. l1[i]-1, their staged (padded) LDS rows, the launch's dynamic LDS bytes */
+    int l0[LCREC_MAX_LEVELS], l1[LCREC_MAX_LEVELS], rows[LCREC_MAX_LEVELS];
+    int64_t lds_bytes[LCREC_MAX_LEVELS];
+    int row_off[LCREC_MAX_LEVELS];          /* per level: its first LDS row within its launch */
+    /* per level, split form only (else 0): 32-code blocks in a wave's share, and waves whose share is empty */
+    int blocks_per_wave[LCREC_MAX_LEVELS], idle_waves[LCREC_MAX_LEVELS];
+    /* split form, some launch runs an odd number of levels and some workgroup makes more than one trip: the last level of a
+     * tile and the first of the next are then consecutive uses of the hand-over buffers with the same level parity */
+    int handover_reuse;
+} lcrec_rq_plan;
+/* Host only: nothing is launched, no device is needed.  n >= 1. */
+int lcrec_debug_rq_assign_plan(int64_t n, int e, const int *K, int L, int force_split, int force_threads, int force_grid,
+                               lcrec_rq_plan *out);
+/* lcrec_rq_assign with the three forcing arguments: the same launcher, plan and kernels. */
+int lcrec_debug_rq_assign(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L,
+                          int64_t *idx_out, int64_t idx_stride, float *xq_out, int xq_accumulate, double *sse_out,
+                          float *resid_out, float *margin_out, uint32_t *neartie_out, float tie_tau,
+                          void *workspace, size_t workspace_bytes, unsigned int *ticket, void *stream,
+                          int force_split, int force_threads, int force_grid);
+
 #ifdef __cplusplus
 }
 #endif

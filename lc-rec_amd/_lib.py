@@ -116,6 +116,11 @@ _SIGNATURES = {
     "lcrec_debug_sinkhorn_batch": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                                   _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp, _vp,
                                                   ctypes.POINTER(ctypes.c_int)]),
+    "lcrec_debug_rq_assign_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, _vp]),
+    "lcrec_debug_rq_assign": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int),
+                                             ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_float,
+                                             _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
 }
 
 
@@ -132,6 +137,19 @@ class SinkhornPlan(ctypes.Structure):
                 ("sets", ctypes.c_int), ("rows_per_workgroup", ctypes.c_int), ("padded_columns", ctypes.c_int),
                 ("ragged_wave", ctypes.c_int), ("ragged_workgroup", ctypes.c_int), ("batch_route", ctypes.c_int),
                 ("workspace_bytes", ctypes.c_int64)]
+
+
+MAX_LEVELS = 16                      # LCREC_MAX_LEVELS of include/lcrec.h
+
+
+class RqPlan(ctypes.Structure):
+    """lcrec_rq_plan of include/lcrec.h"""
+    _fields_ = [("split", ctypes.c_int), ("threads", ctypes.c_int), ("grid", ctypes.c_int), ("tiles", ctypes.c_int64),
+                ("trips_max", ctypes.c_int64), ("trips_min", ctypes.c_int64), ("launches", ctypes.c_int),
+                ("l0", ctypes.c_int * MAX_LEVELS), ("l1", ctypes.c_int * MAX_LEVELS), ("rows", ctypes.c_int * MAX_LEVELS),
+                ("lds_bytes", ctypes.c_int64 * MAX_LEVELS), ("row_off", ctypes.c_int * MAX_LEVELS),
+                ("blocks_per_wave", ctypes.c_int * MAX_LEVELS), ("idle_waves", ctypes.c_int * MAX_LEVELS),
+                ("handover_reuse", ctypes.c_int)]
 
 
 class TraceEntry(ctypes.Structure):

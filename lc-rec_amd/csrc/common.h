@@ -200,10 +200,11 @@ size_t linear_backward_weights_workspace(const lcrec_dw_problem *problems, int c
 int linear_backward_weights(const lcrec_dw_problem *problems, int count, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
 size_t rq_assign_workspace(int64_t n, int e, const int *K, int L);
+struct RqForce { int split, threads, grid; };   // lcrec_debug_rq_assign's forcing arguments (include/lcrec.h); NULL in production
 int rq_assign(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L,
               int64_t *idx_out, int64_t idx_stride, float *xq_out, int xq_accumulate, double *sse_out, float *resid_out,
               float *margin_out, uint32_t *neartie_out, float tie_tau,
-              void *workspace, size_t workspace_bytes, unsigned *ticket, hipStream_t stream);
+              void *workspace, size_t workspace_bytes, unsigned *ticket, hipStream_t stream, const RqForce *force = nullptr);
 
 size_t sinkhorn_workspace(int64_t n, int K, const int64_t *offs, int G);
 int sinkhorn_assign(const float *r, int64_t n, int e, const float *cb, int K, const int64_t *offs, int G, double eps,

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(THREADS) void rq_assign_kernel(RqParams p)
     float *cbs = smem;                       // [rows][S]
     float *ccs = smem + (size_t)p.rows * S;  // [rows]
     double *wave_sse = reinterpret_cast<double *>(ccs + ((p.rows + 3) & ~3));  // [WAVES][L]
-    // (split) per-level hand-over of the waves' partial argmins: [2 parities][WAVES][64 lanes] x {distance, index, second}
+    // (split) hand-over of the waves' partial argmins: [2 buffers][WAVES][64 lanes] x {distance, index, second}
     float *ex = reinterpret_cast<float *>(wave_sse + (size_t)WAVES * p.L);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -149,6 +149,10 @@ __global__ __launch_bounds__(THREADS) void rq_assign_kernel(RqParams p)
     const int64_t tiles = (p.n + 63) / 64;
     const int64_t gw = split ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * WAVES + wave;
     const int64_t GW = split ? (int64_t)gridDim.x : (int64_t)gridDim.x * WAVES;
+
+    // (split) which of the two hand-over buffers the next (tile, level) writes, as its float offset into ex (0 or WAVES * 64 * 3):
+    // toggled at every use, the same in every thread of the workgroup -- all its waves walk the same tiles and levels
+    int ex_use = 0;
 
     for (int64_t tile = gw; tile < tiles; tile += GW) {
         const int64_t item = tile * 64 + lane;
@@ -272,11 +276,18 @@ __global__ __launch_bounds__(THREADS) void rq_assign_kernel(RqParams p)
             }
             if (split) {
                 // this wave's (best, index, second) over ITS code blocks -> LDS; then every wave merges all of them in wave
-                // order.  Parity buffers: a wave may be a level ahead of another, never two (the barrier below).
-                float *mine = ex + ((size_t)((l & 1) * WAVES + wave) * 64 + lane) * 3;
+                // order.  Two buffers, alternating at every USE -- every (tile, level) the workgroup runs -- and not with the
+                // level number: with an odd run of levels the last level of a tile and the first of the next have the same
+                // parity, and nothing but this barrier separates them.  Use u writes buffer u & 1, passes barrier B_u and
+                // reads buffer u & 1.  The next write to that buffer is use u + 2's, made by a wave that has passed B_(u+1);
+                // B_(u+1) lets no wave pass before every wave has arrived at it, having finished its reads of use u (the
+                // barrier waits for the wave's outstanding LDS reads first).  So any two uses of one buffer have a barrier
+                // between them: a wave may be one use ahead of another, never two, across tiles too.
+                float *mine = ex + ex_use + ((size_t)wave * 64 + lane) * 3;
                 mine[0] = win; mine[1] = __int_as_float(bi); mine[2] = second;
                 __syncthreads();
-                const float *all = ex + ((size_t)(l & 1) * WAVES * 64 + lane) * 3;
+                const float *all = ex + ex_use + (size_t)lane * 3;
+                ex_use ^= WAVES * 64 * 3;
                 win = all[0]; bi = __float_as_int(all[1]); second = all[2];
 #pragma unroll
                 for (int w = 1; w < WAVES; ++w) {
@@ -468,10 +479,103 @@ static int dispatch(const RqParams &p, int threads, int grid, size_t lds, bool w
     return dispatch2<E, 256>(p, grid, lds, want_xq, stream);
 }
 
+// ---- which form a problem takes, as a pure function of (n, e, K, L), the tuning knobs and the debug entry's forcing arguments:
+// rq_assign() below executes this plan, lcrec_debug_rq_assign_plan() reports it; neither restates the other.
+struct RqKnobs {
+    int64_t split_tiles;   // LCREC_RQ_SPLIT_TILES (tuning): the split form up to this many 64-item tiles (512)
+    bool allow_split;      // LCREC_RQ_SPLIT=0: one tile per wave always
+};
+
+static const RqKnobs &rq_knobs()
+{
+    static const RqKnobs k = [] {
+        RqKnobs v;
+        const char *e = getenv("LCREC_RQ_SPLIT_TILES");
+        v.split_tiles = e ? atoi(e) : 512;
+        e = getenv("LCREC_RQ_SPLIT");
+        v.allow_split = !e || atoi(e) != 0;
+        return v;
+    }();
+    return k;
+}
+
+static int rq_plan(int64_t n, int e, const int *K, int L, const RqKnobs &kn, const RqForce &f, lcrec_rq_plan *o)
+{
+    if (!K || !o) return fail(LCREC_EINVAL, "rq_assign: NULL pointer");
+    if (n < 1 || L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "rq_assign: bad n=%lld or L=%d", (long long)n, L);
+    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "rq_assign: e_dim=%d (supported: 16, 32, 64)", e);
+    if (f.split < -1 || f.split > 1 || (f.threads != 0 && f.threads != 256 && f.threads != 512) || f.grid < 0)
+        return fail(LCREC_EINVAL, "rq_assign: forced split=%d (-1, 0, 1), threads=%d (0, 256, 512), grid=%d (>= 0)", f.split, f.threads, f.grid);
+    memset(o, 0, sizeof *o);
+    const int64_t tiles = (n + 63) / 64;
+    // batch-sized inputs with enough code blocks to deal out: the split form (see the kernel).  Up to 512 tiles of 64 items: below
+    // that the one-tile-per-wave form leaves most CUs without a wave while each wave walks its tile's levels alone (Games' 16 859
+    // items: 264 tiles on 66 workgroups, 55 us; LCREC_RQ_SPLIT_TILES, tuning)
+    int max_k = 0;
+    for (int l = 0; l < L; ++l) max_k = K[l] > max_k ? K[l] : max_k;
+    bool split = kn.allow_split && tiles <= kn.split_tiles && max_k >= 128;
+    for (int l = 0; split && l < L; ++l)       // (its hand-over buffers must not push a level out of LDS that fits without them)
+        if (K[l] > 0 && lds_bytes((K[l] + 31) & ~31, e, L, 4, true) > LDS_BUDGET) split = false;
+    if (f.split >= 0) split = f.split != 0;
+    int threads = split ? 256 : threads_for(e, n);
+    if (f.threads) {
+        if (f.threads == 512 && (e == 64 || split))
+            return fail(LCREC_EUNSUPPORTED, "rq_assign: %s runs 256-thread workgroups", split ? "the split form" : "e=64");
+        threads = f.threads;
+    }
+    const int waves = threads / 64;
+    for (int l = 0; l < L; ++l) {
+        if (K[l] <= 0) return fail(LCREC_EINVAL, "rq_assign: K[%d]=%d", l, K[l]);
+        if (lds_bytes((K[l] + 31) & ~31, e, L, waves, split) > LDS_BUDGET) {
+            if (split && lds_bytes((K[l] + 31) & ~31, e, L, waves, false) <= LDS_BUDGET)
+                return fail(LCREC_EUNSUPPORTED, "rq_assign: the split form cannot take level %d (K=%d, e=%d): its hand-over buffers push it "
+                            "out of 160 KB of LDS", l, K[l], e);
+            return fail(LCREC_EUNSUPPORTED, "rq_assign: level %d (K=%d, e=%d) does not fit in 160 KB of LDS", l, K[l], e);
+        }
+    }
+    // (split: the staged codebooks leave room for one workgroup per CU, so more than MAX_GRID of them would run in rounds and
+    // stage again; the tile loop takes the rest)
+    int grid = split ? (int)(tiles < MAX_GRID ? tiles : MAX_GRID) : grid_for(n, threads);
+    if (f.grid) {
+        if (f.grid > grid) return fail(LCREC_EUNSUPPORTED, "rq_assign: forced grid %d (1 .. %d for this form)", f.grid, grid);
+        grid = f.grid;
+    }
+    o->split = split ? 1 : 0;
+    o->threads = threads;
+    o->grid = grid;
+    o->tiles = tiles;
+    const int64_t walkers = split ? (int64_t)grid : (int64_t)grid * waves;     // who strides over the tiles: workgroups, or waves
+    o->trips_max = (tiles + walkers - 1) / walkers;
+    o->trips_min = tiles / walkers;
+
+    // Greedily pack consecutive levels into launches whose codebooks fit in LDS.
+    bool odd_run = false;
+    for (int l0 = 0; l0 < L;) {
+        int rows = 0, l1 = l0;
+        while (l1 < L && lds_bytes(rows + ((K[l1] + 31) & ~31), e, L, waves, split) <= LDS_BUDGET) {
+            o->row_off[l1] = rows;
+            rows += (K[l1] + 31) & ~31;
+            ++l1;
+        }
+        const int i = o->launches++;
+        o->l0[i] = l0; o->l1[i] = l1; o->rows[i] = rows;
+        o->lds_bytes[i] = (int64_t)lds_bytes(rows, e, L, waves, split);
+        odd_run = odd_run || ((l1 - l0) & 1);
+        l0 = l1;
+    }
+    for (int l = 0; split && l < L; ++l) {     // the kernel's deal: wave w takes blocks [w * per, min((w + 1) * per, nblk))
+        const int nblk = (K[l] + 31) >> 5, per = (nblk + waves - 1) / waves;
+        o->blocks_per_wave[l] = per;
+        o->idle_waves[l] = waves - (nblk + per - 1) / per;
+    }
+    o->handover_reuse = split && odd_run && o->trips_max > 1;
+    return LCREC_OK;
+}
+
 int rq_assign(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L,
               int64_t *idx_out, int64_t idx_stride, float *xq_out, int xq_accumulate, double *sse_out, float *resid_out,
               float *margin_out, uint32_t *neartie_out, float tie_tau,
-              void *workspace, size_t workspace_bytes, unsigned *ticket, hipStream_t stream)
+              void *workspace, size_t workspace_bytes, unsigned *ticket, hipStream_t stream, const RqForce *force)
 {
     if (n == 0 && K && L >= 1 && L <= LCREC_MAX_LEVELS) return LCREC_OK;   // empty batch
     if (!z || !codebooks || !K || !idx_out) return fail(LCREC_EINVAL, "rq_assign: NULL pointer");
@@ -482,24 +586,9 @@ int rq_assign(const float *z, int64_t n, int e, const float *codebooks, const in
     if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "rq_assign: e_dim=%d (supported: 16, 32, 64)", e);
     if (((uintptr_t)z | (uintptr_t)codebooks | (uintptr_t)xq_out | (uintptr_t)resid_out) & 15)
         return fail(LCREC_EINVAL, "rq_assign: buffers must be 16-byte aligned");
-    // batch-sized inputs with enough code blocks to deal out: the split form (see the kernel).  Up to 512 tiles of 64 items: below
-    // that the one-tile-per-wave form leaves most CUs without a wave while each wave walks its tile's levels alone (Games' 16 859
-    // items: 264 tiles on 66 workgroups, 55 us; LCREC_RQ_SPLIT_TILES, tuning)
-    static const int64_t split_tiles = [] { const char *v = getenv("LCREC_RQ_SPLIT_TILES"); return (int64_t)(v ? atoi(v) : 512); }();
-    int max_k = 0;
-    for (int l = 0; l < L; ++l) max_k = K[l] > max_k ? K[l] : max_k;
-    static const bool allow_split = [] { const char *v = getenv("LCREC_RQ_SPLIT"); return !v || atoi(v) != 0; }();
-    bool split = allow_split && n > 0 && (n + 63) / 64 <= split_tiles && max_k >= 128;
-    for (int l = 0; split && l < L; ++l)       // (its hand-over buffers must not push a level out of LDS that fits without them)
-        if (K[l] > 0 && lds_bytes((K[l] + 31) & ~31, e, L, 4, true) > LDS_BUDGET) split = false;
-    const int threads = split ? 256 : threads_for(e, n);
-    const int waves = threads / 64;
-    for (int l = 0; l < L; ++l) {
-        if (K[l] <= 0) return fail(LCREC_EINVAL, "rq_assign: K[%d]=%d", l, K[l]);
-        if (lds_bytes((K[l] + 31) & ~31, e, L, waves, split) > LDS_BUDGET)
-            return fail(LCREC_EUNSUPPORTED, "rq_assign: level %d (K=%d, e=%d) does not fit in 160 KB of LDS", l, K[l], e);
-    }
-    if (n == 0) return LCREC_OK;
+    lcrec_rq_plan pl;
+    const RqForce production = {-1, 0, 0};
+    if (int rc0 = rq_plan(n, e, K, L, rq_knobs(), force ? *force : production, &pl)) return rc0;
     if (workspace_bytes < rq_assign_workspace(n, e, K, L) || !workspace)
         return fail(LCREC_EWORKSPACE, "rq_assign: workspace %zu B < required %zu B", workspace_bytes, rq_assign_workspace(n, e, K, L));
 
@@ -507,31 +596,22 @@ int rq_assign(const float *z, int64_t n, int e, const float *codebooks, const in
     float *ping = reinterpret_cast<float *>(workspace);
     float *pong = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + resid_bytes);
     double *partial = reinterpret_cast<double *>(reinterpret_cast<char *>(workspace) + 2 * resid_bytes);
-    // (split: the staged codebooks leave room for one workgroup per CU, so more than MAX_GRID of them would run in rounds and
-    // stage again; the tile loop takes the rest)
-    const int grid = split ? (int)((n + 63) / 64 < MAX_GRID ? (n + 63) / 64 : MAX_GRID) : grid_for(n, threads);
 
-    // Greedily pack consecutive levels into launches whose codebooks fit in LDS.
     int64_t cb_offs[LCREC_MAX_LEVELS];
     {
         int64_t o = 0;
         for (int l = 0; l < L; ++l) { cb_offs[l] = o; o += (int64_t)K[l] * e; }
     }
     const float *zin = z;
-    int l0 = 0;
-    while (l0 < L) {
+    for (int i = 0; i < pl.launches; ++i) {
         RqParams p = {};
-        int rows = 0, l1 = l0;
-        while (l1 < L && lds_bytes(rows + ((K[l1] + 31) & ~31), e, L, waves, split) <= LDS_BUDGET) {
-            p.row_off[l1] = rows;
-            rows += (K[l1] + 31) & ~31;
-            ++l1;
-        }
+        const int l0 = pl.l0[i], l1 = pl.l1[i];
+        for (int l = l0; l < l1; ++l) p.row_off[l] = pl.row_off[l];
         for (int l = 0; l < L; ++l) { p.K[l] = K[l]; p.cb_off[l] = cb_offs[l]; }
         p.xq_accumulate = xq_accumulate;
         p.z_in = zin;
         p.cb = codebooks;
-        p.n = n; p.l0 = l0; p.l1 = l1; p.L = L; p.rows = rows;
+        p.n = n; p.l0 = l0; p.l1 = l1; p.L = L; p.rows = pl.rows[i];
         p.idx_out = idx_out;
         p.idx_stride = idx_stride;
         p.ticket = sse_out ? ticket : nullptr;
@@ -542,26 +622,45 @@ int rq_assign(const float *z, int64_t n, int e, const float *codebooks, const in
         p.margin = margin_out;
         p.neartie = neartie_out;
         p.tie_tau = tie_tau;
-        p.split = split ? 1 : 0;
+        p.split = pl.split;
         float *next = nullptr;
         if (l1 < L) next = (zin == ping) ? pong : ping;
         p.resid_next = next;
-        const size_t lds = lds_bytes(rows, e, L, waves, split);
+        const size_t lds = (size_t)pl.lds_bytes[i];
         int rc;
-        if (e == 16) rc = dispatch<16>(p, threads, grid, lds, xq_out != nullptr, stream);
-        else if (e == 32) rc = dispatch<32>(p, threads, grid, lds, xq_out != nullptr, stream);
-        else rc = dispatch<64>(p, threads, grid, lds, xq_out != nullptr, stream);
+        if (e == 16) rc = dispatch<16>(p, pl.threads, pl.grid, lds, xq_out != nullptr, stream);
+        else if (e == 32) rc = dispatch<32>(p, pl.threads, pl.grid, lds, xq_out != nullptr, stream);
+        else rc = dispatch<64>(p, pl.threads, pl.grid, lds, xq_out != nullptr, stream);
         if (rc) return rc;
         if (sse_out && !ticket) {
             TraceScope trace(K_RQ_SSE_FINALIZE, stream);
-            hipLaunchKernelGGL(rq_sse_finalize_kernel, dim3(1), dim3(64), 0, stream, partial, grid, L, l0, l1, sse_out);
+            hipLaunchKernelGGL(rq_sse_finalize_kernel, dim3(1), dim3(64), 0, stream, partial, pl.grid, L, l0, l1, sse_out);
             rc = check_launch("rq_sse_finalize_kernel");
             if (rc) return rc;
         }
         zin = next;
-        l0 = l1;
     }
     return LCREC_OK;
 }
 
 }  // namespace lcrec
+
+// ---- debug entries (include/lcrec.h): the plan above, reported; and the launcher above with the plan's forcing arguments
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_rq_assign_plan(int64_t n, int e, const int *K, int L, int force_split,
+                                                                                 int force_threads, int force_grid, lcrec_rq_plan *out)
+{
+    const lcrec::RqForce f = {force_split, force_threads, force_grid};
+    return lcrec::rq_plan(n, e, K, L, lcrec::rq_knobs(), f, out);
+}
+
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_rq_assign(const float *z, int64_t n, int e, const float *codebooks, const int *K,
+                                                                            int L, int64_t *idx_out, int64_t idx_stride, float *xq_out,
+                                                                            int xq_accumulate, double *sse_out, float *resid_out,
+                                                                            float *margin_out, uint32_t *neartie_out, float tie_tau,
+                                                                            void *workspace, size_t workspace_bytes, unsigned int *ticket,
+                                                                            void *stream, int force_split, int force_threads, int force_grid)
+{
+    const lcrec::RqForce f = {force_split, force_threads, force_grid};
+    return lcrec::rq_assign(z, n, e, codebooks, K, L, idx_out, idx_stride, xq_out, xq_accumulate, sse_out, resid_out, margin_out,
+                            neartie_out, tie_tau, workspace, workspace_bytes, ticket, (hipStream_t)stream, &f);
+}

@@ -376,6 +376,66 @@ def rq_assign(z, codebooks_flat, ks, want_xq=False, want_sse=False, want_resid=F
     return idx, xq, sse, resid
 
 
+def rq_assign_plan(n, e, ks, force_split=-1, force_threads=0, force_grid=0):
+    """The form lcrec_rq_assign takes for [n, e] items and codebooks of `ks` codes, or the forced one (include/lcrec.h,
+    lcrec_debug_rq_assign_plan), as a dict of the fields of lcrec_rq_plan: the per-launch fields as lists of `launches` entries,
+    the per-level fields as lists of len(ks).  Host only: no GPU is needed.  LcrecError when the form cannot take the shape."""
+    plan = _lib.RqPlan()
+    L = len(ks)
+    rc = _lib.load().lcrec_debug_rq_assign_plan(int(n), int(e), _ints(ks), L, int(force_split), int(force_threads), int(force_grid),
+                                                ctypes.addressof(plan))
+    _lib.check(rc, "lcrec_debug_rq_assign_plan")
+    out = {}
+    for name, ctype in _lib.RqPlan._fields_:
+        value = getattr(plan, name)
+        if name in ("l0", "l1", "rows", "lds_bytes"):
+            out[name] = [int(v) for v in value[:plan.launches]]
+        elif name in ("row_off", "blocks_per_wave", "idle_waves"):
+            out[name] = [int(v) for v in value[:L]]
+        else:
+            out[name] = int(value)
+    return out
+
+
+def rq_assign_into(z, codebooks_flat, ks, idx, idx_stride, xq=None, xq_accumulate=False, sse=None, resid=None, margin=None,
+                   neartie=None, tie_tau=0.0, ticket=True, force=None):
+    """lcrec_rq_assign (force=None) or lcrec_debug_rq_assign (force = (split, threads, grid), include/lcrec.h) into buffers the
+    caller owns -- each may be LARGER than the call needs, so that a test can look at what lies past the end: idx int64 with at
+    least n * idx_stride elements, xq [>= n, e], sse float64 [>= L], resid float32 with at least (L + 1) * n * e elements
+    (entry l at element l * n * e), margin float32 [>= n, L], neartie int32 [>= n].  ticket=False: the sums of squares are
+    finished by a launch of their own.  Nothing is returned."""
+    lib = _lib.load()
+    z = _dev(z, "z")
+    cb = _dev(codebooks_flat, "codebooks")
+    n, e = z.shape
+    L = len(ks)
+    dev = z.device
+    idx_stride = int(idx_stride)
+    if cb.numel() != sum(int(k) for k in ks) * e:
+        raise _lib.LcrecError(f"codebooks hold {cb.numel()} floats, {ks} x {e} need {sum(ks) * e}")
+    for name, t, dtype, need in (("idx", idx, torch.int64, n * idx_stride), ("xq", xq, torch.float32, n * e), ("sse", sse, torch.float64, L),
+                                 ("resid", resid, torch.float32, (L + 1) * n * e), ("margin", margin, torch.float32, n * L),
+                                 ("neartie", neartie, torch.int32, n)):
+        if t is None and name != "idx":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()
+                and t.numel() >= need):
+            raise _lib.LcrecError(f"{name} must be a contiguous {dtype} tensor on z's device with at least {need} elements")
+    if idx_stride < L:
+        raise _lib.LcrecError(f"idx_stride {idx_stride} < L = {L}")
+    karr = _ints(ks)
+    with _on(dev):
+        ws = _workspace(lib.lcrec_rq_assign_workspace(n, e, karr, L), dev)
+        args = (_ptr(z), n, e, _ptr(cb), karr, L, _ptr(idx), idx_stride, _ptr(xq), int(bool(xq_accumulate)), _ptr(sse), _ptr(resid),
+                _ptr(margin), _ptr(neartie), float(tie_tau), _ptr(ws), ws.numel(), _ptr(_ticket(dev, force=True)) if ticket else None,
+                _stream_ptr())
+        if force is None:
+            rc, what = lib.lcrec_rq_assign(*args), "lcrec_rq_assign"
+        else:
+            rc, what = lib.lcrec_debug_rq_assign(*args, *[int(v) for v in force]), "lcrec_debug_rq_assign"
+    _lib.check(rc, what)
+
+
 def encode_assign(x, weights, biases, codebooks_flat, ks, bn_scales=None, bn_shifts=None, want_latent=False,
                   want_xq=False, want_sse=False, audit=None, tie_tau=None):
     """RQVAE.get_indices(xs, use_sk=False) (rqvae.py:68-72): encoder MLP + L-level argmin assignment.

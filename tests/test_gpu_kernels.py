@@ -247,6 +247,8 @@ def test_grouped_weight_gradients_equal_per_layer_calls(hip, oracle):
         hip.ops.linear_backward_weights([problems[0]] * 17)
 
 
+# these shapes take whatever form the dispatch rule gives them.  tests/rq_cases.py has a row for every instantiation and every run-time
+# form of the kernel (forced through lcrec_debug_rq_assign), values included.
 @pytest.mark.parametrize("n,e,Ks", [
     (64, 32, [256] * 4),
     (1000, 32, [256] * 4),

@@ -568,6 +568,41 @@ int lcrec_finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, cons
                               const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets,
                               int64_t n_buckets, int64_t *counters_out, void *stream);
 
+/* Frozen-aware nearest free code: lcrec_finish_nearest_free's pass for a catalogue that GROWS.  Items with id < n_frozen are
+ * frozen: they were indexed before, their tuples are the vocabulary a downstream model was trained on, and they never change.  No
+ * residual exists for them.  Items n_frozen .. n-1 are new; each keeps its tuple unless that tuple is taken.  Beyond the reference,
+ * whose index/generate_indices.py only ever indexes a whole file from scratch.
+ *
+ * The rule.  d(i,k) is lcrec_finish_nearest_free's distance, bit for bit; wherever two distances are compared a NaN counts as +inf.
+ *   1. A bucket is the set of items, frozen and new together, that share idx[:, :L-1] (L = 1: one bucket of all items).  A bucket
+ *      is touched only if some last code is held by two or more of its items, at least one of them new.  A bucket with no new item
+ *      is never touched, however its frozen items collide.
+ *   2. For a last code held by two or more items of a touched bucket: if any holder is frozen, every new holder is a mover.
+ *      Otherwise the new holder with the smallest d(i,k) keeps the code, a tie goes to the lowest item id, and the others are movers.
+ *   3. Occupied codes: every code held by any item of the bucket, frozen or new.
+ *   4. Movers, in ascending item id: each takes the free code with the smallest d(i,k), the first minimum in code order; that code
+ *      is occupied from then on.  When no code is free, this mover and all later ones of the bucket keep their code and count as
+ *      unresolved.
+ * So the frozen rows are bit-identical afterwards; the number of colliding items afterwards (n minus the number of distinct
+ * tuples) equals the number colliding among the frozen items alone plus `unresolved`; unresolved is 0 whenever no touched bucket
+ * has more items than K[L-1]; and with n_frozen == 0 the result is lcrec_finish_nearest_free's, bit for bit.
+ *
+ * Arguments as lcrec_finish_nearest_free, except:
+ *   n_frozen        0 .. n
+ *   resid_last      device [n - n_frozen][e] float: the row of item i is i - n_frozen.  Nothing is read for a frozen id.  May be
+ *                   NULL when n_frozen == n.
+ *   codebook_last   as there, with 4 more bytes of LDS per code (the frozen holders per code): K[L-1] * (4 e + 24) + 512 bytes
+ *                   must fit in 160 KB, which refuses K[L-1] = 1856 .. 1920 at e = 16 and 1075 .. 1088 at e = 32 that
+ *                   lcrec_finish_nearest_free takes
+ *   bucket_members  item ids ascending inside a bucket (the layout lcrec_collision_groups emits): a bucket whose LAST member is
+ *                   frozen holds no new item and is left at once
+ * n_buckets == 0 or n_frozen == n: no launch, the counters are zeroed.  Same shape as lcrec_finish_nearest_free: one workgroup
+ * per bucket, no workspace, no allocation, no synchronisation, capturable; argument errors are reported before anything is
+ * enqueued.  Traced as "extend_nearest_free". */
+int lcrec_extend_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_last, int e,
+                              const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets,
+                              int64_t n_buckets, int64_t *counters_out, void *stream);
+
 /* Text of the `.index.json` entries for a run of items (host-side; no device work).  Replaces the
  * per-item Python of index/generate_indices.py:83-92 (token strings "<a_{i}>", "<b_{j}>", ...) and the
  * json.dump of :138-145, whose default separators (", " and ": ") every consumer relies on
@@ -580,6 +615,18 @@ int lcrec_finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, cons
  * Returns the number of bytes written, or a negative LCREC_E* code (LCREC_EWORKSPACE: cap too small). */
 int64_t lcrec_index_json_bound(int64_t n, int L);
 int64_t lcrec_index_json_format(const int64_t *idx, int64_t n, int L, int64_t first_item, char *out, int64_t cap);
+
+/* The reader of that text (host-side): the strict inverse of "{" + lcrec_index_json_format(items 0 .. n-1) + "}", which is what
+ * json.dump with default separators writes for {"0": ["<a_i>", "<b_j>", ...], "1": [...], ...}.  Accepted are exactly the texts
+ * the formatter can produce for non-negative codes: keys "0", "1", "2", ... in order, L tokens per item, the prefix letter of
+ * each level, codes as decimal digits without sign or leading zeros that fit an int64, ", " and ": " as the only white space,
+ * nothing after the closing brace.  So a text that is accepted is reproduced byte for byte by formatting the result.  "{}" gives
+ * 0 items.
+ *   text      HOST, len bytes, no terminator needed: nothing outside [text, text + len) is read
+ *   idx_out   HOST [cap_items][L] int64; rows 0 .. count-1 are written, never a row >= cap_items
+ * Returns the item count, or a negative LCREC_E* code with a last-error text that names the byte offset (LCREC_EINVAL: the text
+ * is not of that form; LCREC_EWORKSPACE: more than cap_items items; idx_out then holds the items read so far). */
+int64_t lcrec_index_json_parse(const char *text, int64_t len, int L, int64_t *idx_out, int64_t cap_items);
 
 /* Kernel tracing (diagnostic; the reference has no tracing on this path -- its only
  * timing is wall-clock per epoch, index/trainer.py:193-195).  While enabled, every

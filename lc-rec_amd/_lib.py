@@ -108,8 +108,11 @@ _SIGNATURES = {
                                               _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "lcrec_finish_nearest_free": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp, ctypes.c_int, _vp,
                                                  _vp, _vp, ctypes.c_int64, _vp, _vp]),
+    "lcrec_extend_nearest_free": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp,
+                                                 ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
     "lcrec_index_json_bound": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
     "lcrec_index_json_format": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int64]),
+    "lcrec_index_json_parse": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64]),
     "lcrec_trace_enable": (ctypes.c_int, [ctypes.c_int]),
     "lcrec_trace_collect": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lcrec_debug_sinkhorn_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),

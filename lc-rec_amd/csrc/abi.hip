@@ -28,7 +28,7 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "collision_groups", "linear_fwd_pp_256x128", "linear_fwd_64x64", "sinkhorn_slab",
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
-                                           "optim_step", "dropout", "cast_rows", "finish_nearest_free"};
+                                           "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -368,6 +368,11 @@ LCREC_API int64_t lcrec_index_json_format(const int64_t *idx, int64_t n, int L, 
     return index_json_format(idx, n, L, first_item, out, cap);
 }
 
+LCREC_API int64_t lcrec_index_json_parse(const char *text, int64_t len, int L, int64_t *idx_out, int64_t cap_items)
+{
+    return index_json_parse(text, len, L, idx_out, cap_items);
+}
+
 LCREC_API size_t lcrec_collision_groups_workspace(int64_t n, int L) { return collision_workspace(n, L); }
 
 LCREC_API int lcrec_collision_groups(const int64_t *idx, int64_t n, int L, const int *K, int64_t *members_out,
@@ -384,6 +389,14 @@ LCREC_API int lcrec_finish_nearest_free(int64_t *idx, int64_t n, int L, const in
 {
     return finish_nearest_free(idx, n, L, K, resid_last, e, codebook_last, bucket_members, bucket_offsets, n_buckets, counters_out,
                                (hipStream_t)stream);
+}
+
+LCREC_API int lcrec_extend_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_last, int e,
+                                        const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets,
+                                        int64_t n_buckets, int64_t *counters_out, void *stream)
+{
+    return extend_nearest_free(idx, n, n_frozen, L, K, resid_last, e, codebook_last, bucket_members, bucket_offsets, n_buckets,
+                               counters_out, (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_bn_relu_forward(const float *t, int64_t n, int features, const float *gamma, const float *beta, float eps,

@@ -31,7 +31,7 @@ inline int check_launch(const char *what)
 enum KernelId { K_LINEAR_128x128 = 0, K_LINEAR_128x64, K_LINEAR_128x32, K_RQ_ASSIGN, K_RQ_SSE_FINALIZE,
                 K_VQ_DISTANCE, K_SINKHORN, K_SINKHORN_SMALL, K_APPLY_LEVEL, K_CODE_STATS, K_EMA_UPDATE, K_COLLISION,
                 K_LINEAR_PP, K_LINEAR_64x64, K_SINKHORN_SLAB, K_SINKHORN_TINY, K_BN_FWD, K_BN_BWD, K_RELU_BIAS_BWD, K_LOSS,
-                K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_FINISH, K_COUNT };
+                K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_FINISH, K_EXTEND, K_COUNT };
 extern const char *const kKernelNames[K_COUNT];
 bool trace_on();
 void trace_begin(int kernel, hipStream_t stream);
@@ -224,6 +224,9 @@ bool rq_level_fits(int K, int e, int L);   // whether rq_assign takes a level of
 int finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e, const float *codebook_last,
                         const int64_t *bucket_members, const int64_t *bucket_offsets, int64_t n_buckets, int64_t *counters_out,
                         hipStream_t stream);
+int extend_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_last, int e,
+                        const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets, int64_t n_buckets,
+                        int64_t *counters_out, hipStream_t stream);
 int ema_update(float *ema_count, float *ema_sum, float *codebook, const float *count, const float *sum, int K, int e,
                float decay, float alpha, float keep, float eps, const unsigned char *skip, hipStream_t stream);
 
@@ -279,5 +282,6 @@ int cast_rows(const void *src, int src_dtype, int64_t count, float *dst, hipStre
 // host-side text (index_json.hip)
 int64_t index_json_bound(int64_t n, int L);
 int64_t index_json_format(const int64_t *idx, int64_t n, int L, int64_t first_item, char *out, int64_t cap);
+int64_t index_json_parse(const char *text, int64_t len, int L, int64_t *idx_out, int64_t cap_items);
 
 }  // namespace lcrec

@@ -26,6 +26,8 @@
 // sequential steps whatever its size.  Nothing crosses workgroups: no flag, no spin; the only global atomics are the two counters.
 #include "common.h"
 
+#include <type_traits>
+
 namespace lcrec {
 
 constexpr int FIN_THREADS = 256;
@@ -39,6 +41,11 @@ struct FinishParams {
     const float *cb;         // [K][E]
     const int64_t *members, *offsets;
     unsigned long long *counters;   // {moved, unresolved}
+};
+
+// lcrec_extend_nearest_free: items with id < n_frozen never move, and resid holds the rows of the new items only
+struct ExtendParams : FinishParams {
+    int64_t n_frozen;
 };
 
 // unsigned order of the result == float order of d; NaN -> +inf, -0 -> +0
@@ -71,8 +78,10 @@ __device__ __forceinline__ float distance(const float (&x)[E], float xx, const f
     return t - 2.0f * dot;
 }
 
-template <int E>
-__global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(FinishParams p)
+// FROZEN = false is lcrec_finish_nearest_free (every `if constexpr (FROZEN)` drops out); FROZEN = true adds the frozen holders of
+// lcrec_extend_nearest_free: fro[k] counts them per code, a code with one has no keeper, and no row of a frozen id is ever read.
+template <int E, bool FROZEN>
+__global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(std::conditional_t<FROZEN, ExtendParams, FinishParams> p)
 {
     constexpr int S = E + 1;   // LDS row stride (floats)
     extern __shared__ __attribute__((aligned(16))) unsigned char fin_smem[];
@@ -81,6 +90,7 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(Finish
     float *cbs = reinterpret_cast<float *>(key + K);                              // [K][S]
     float *ccs = cbs + (size_t)K * S;                                             // [K]
     int *cnt = reinterpret_cast<int *>(ccs + K);                                  // [K] holders, then 1 for a code a mover took
+    int *fro = cnt + K;                                                           // [K] frozen holders (FROZEN only: not allocated otherwise)
     __shared__ unsigned long long wmask[FIN_WAVES];
     __shared__ float red_d[2][FIN_WAVES];
     __shared__ int red_k[2][FIN_WAVES];
@@ -91,6 +101,12 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(Finish
     const int64_t m = hi > lo ? hi - lo : 0;
     const int64_t *mem = p.members + lo;
     const int L = p.L;
+    int64_t nf = 0;                                                               // ids below it are frozen
+    if constexpr (FROZEN) {
+        nf = p.n_frozen;
+        // ids ascend inside a bucket: a frozen last member means no new item, and such a bucket is never touched
+        if (m == 0 || mem[m - 1] < nf) return;
+    }
 
     // a member takes part when its id and its code are in range; any other is left alone (nothing is read or written for it)
     auto code_of = [&](int64_t pos, int64_t &id) -> int {
@@ -101,17 +117,24 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(Finish
     };
 
     // ---- 1. holders per code
-    for (int k = tid; k < K; k += FIN_THREADS) { cnt[k] = 0; key[k] = ~0ull; }
+    for (int k = tid; k < K; k += FIN_THREADS) {
+        cnt[k] = 0; key[k] = ~0ull;
+        if constexpr (FROZEN) fro[k] = 0;
+    }
     __syncthreads();
     for (int64_t pos = tid; pos < m; pos += FIN_THREADS) {
         int64_t id;
         const int c = code_of(pos, id);
-        if (c >= 0) atomicAdd(&cnt[c], 1);
+        if (c >= 0) {
+            atomicAdd(&cnt[c], 1);
+            if constexpr (FROZEN) { if (id < nf) atomicAdd(&fro[c], 1); }
+        }
     }
     __syncthreads();
     int twice = 0, used = 0;
     for (int k = tid; k < K; k += FIN_THREADS) {
-        twice |= cnt[k] >= 2;
+        if constexpr (FROZEN) twice |= cnt[k] >= 2 && cnt[k] > fro[k];           // ... with a new item among its holders
+        else twice |= cnt[k] >= 2;
         used += cnt[k] > 0;
     }
     if (!__syncthreads_or(twice)) return;                                         // untouched bucket (the whole workgroup leaves)
@@ -145,8 +168,9 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(Finish
         int64_t id;
         const int c = code_of(pos, id);
         if (c < 0 || cnt[c] < 2) continue;
+        if constexpr (FROZEN) { if (fro[c] > 0 || id < nf) continue; }           // a frozen holder keeps the code: no keeper among the new
         float x[E];
-        load_row<E>(p.resid + id * E, x);
+        load_row<E>(p.resid + (id - nf) * E, x);
         float xx = 0.f;
 #pragma unroll
         for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
@@ -166,7 +190,8 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(Finish
         if (pos < m) {
             int64_t id;
             const int c = code_of(pos, id);
-            mover = c >= 0 && cnt[c] >= 2 && (uint32_t)key[c] != (uint32_t)pos;
+            if constexpr (FROZEN) mover = c >= 0 && id >= nf && cnt[c] >= 2 && (fro[c] > 0 || (uint32_t)key[c] != (uint32_t)pos);
+            else mover = c >= 0 && cnt[c] >= 2 && (uint32_t)key[c] != (uint32_t)pos;
         }
         if (free_codes == 0) { my_late += mover; continue; }
         const unsigned long long mine = __ballot(mover);
@@ -188,7 +213,7 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(Finish
                 mask &= mask - 1;
                 const int64_t id = mem[base + w * 64 + bit];                      // in range: it was found a mover above
                 float x[E];
-                load_row<E>(p.resid + id * E, x);
+                load_row<E>(p.resid + (id - nf) * E, x);                          // a mover is never frozen: id >= nf
                 float xx = 0.f;
 #pragma unroll
                 for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
@@ -241,57 +266,90 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(Finish
     }
 }
 
-static size_t finish_lds_bytes(int K, int e)
+static size_t finish_lds_bytes(int K, int e, bool frozen)
 {
-    return (size_t)K * (8 + (size_t)(e + 1) * 4 + 4 + 4);   // key, codebook row, cc, cnt
+    return (size_t)K * (8 + (size_t)(e + 1) * 4 + 4 + 4 + (frozen ? 4 : 0));   // key, codebook row, cc, cnt, (fro)
 }
 
-template <int E>
-static int finish_launch(const FinishParams &p, int64_t n_buckets, size_t lds, hipStream_t stream)
+template <int E, bool FROZEN>
+static int finish_launch(const ExtendParams &p, int64_t n_buckets, size_t lds, hipStream_t stream)
 {
-    auto kern = finish_nearest_free_kernel<E>;
+    const char *who = FROZEN ? "extend_nearest_free" : "finish_nearest_free";
+    auto kern = finish_nearest_free_kernel<E, FROZEN>;
     hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (he != hipSuccess)
-        return fail(LCREC_EHIP, "finish_nearest_free: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(he));
-    TraceScope trace(K_FINISH, stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_buckets), dim3(FIN_THREADS), lds, stream, p);
-    return check_launch("finish_nearest_free_kernel");
+        return fail(LCREC_EHIP, "%s: hipFuncSetAttribute(%zu B LDS): %s", who, lds, hipGetErrorString(he));
+    TraceScope trace(FROZEN ? K_EXTEND : K_FINISH, stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_buckets), dim3(FIN_THREADS), lds, stream, p);   // (FROZEN = false: sliced to FinishParams)
+    return check_launch(FROZEN ? "extend_nearest_free_kernel" : "finish_nearest_free_kernel");
+}
+
+// Both entries: `frozen` selects lcrec_extend_nearest_free's checks, texts, LDS need and kernel.
+static int nearest_free(bool frozen, int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_last, int e,
+                        const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets, int64_t n_buckets,
+                        int64_t *counters_out, hipStream_t stream)
+{
+    const char *who = frozen ? "extend_nearest_free" : "finish_nearest_free";
+    if (!counters_out) return fail(LCREC_EINVAL, "%s: counters_out is NULL", who);
+    if (!K) return fail(LCREC_EINVAL, "%s: K is NULL", who);
+    if (L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "%s: L=%d (1 .. %d)", who, L, LCREC_MAX_LEVELS);
+    if (n < 0 || n > 0xffffffffLL) return fail(LCREC_EINVAL, "%s: n=%lld (0 .. 2^32 - 1)", who, (long long)n);
+    if (n_frozen < 0 || n_frozen > n)
+        return fail(LCREC_EINVAL, "%s: n_frozen=%lld (0 .. n=%lld)", who, (long long)n_frozen, (long long)n);
+    if (n_buckets < 0 || n_buckets > 0x7fffffffLL)
+        return fail(LCREC_EINVAL, "%s: n_buckets=%lld (0 .. 2^31 - 1)", who, (long long)n_buckets);
+    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
+    const int Kl = K[L - 1];
+    if (Kl <= 0) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, L - 1, Kl);
+    const size_t lds = finish_lds_bytes(Kl, e, frozen);
+    if (!rq_level_fits(Kl, e, L) || lds + 512 > 160 * 1024) {
+        if (frozen)
+            return fail(LCREC_EUNSUPPORTED, "%s: level %d (K=%d, e=%d) does not fit in 160 KB of LDS with the frozen-holder counts "
+                        "(%zu B: 4 more per code than finish_nearest_free)", who, L - 1, Kl, e, lds);
+        return fail(LCREC_EUNSUPPORTED, "%s: level %d (K=%d, e=%d) does not fit in 160 KB of LDS", who, L - 1, Kl, e);
+    }
+    if (((uintptr_t)resid_last | (uintptr_t)codebook_last) & 15)
+        return fail(LCREC_EINVAL, "%s: resid_last and codebook_last must be 16-byte aligned", who);
+    if (((uintptr_t)idx | (uintptr_t)bucket_members | (uintptr_t)bucket_offsets | (uintptr_t)counters_out) & 7)
+        return fail(LCREC_EINVAL, "%s: idx, bucket_members, bucket_offsets and counters_out must be 8-byte aligned", who);
+    if (n_buckets > 0 && (!idx || !codebook_last || !bucket_members || !bucket_offsets || (!frozen && !resid_last)))
+        return fail(LCREC_EINVAL, "%s: NULL pointer", who);
+    if (frozen && n_buckets > 0 && !resid_last && n_frozen < n)   // (no new item: there is no row, and NULL is fine)
+        return fail(LCREC_EINVAL, "%s: NULL pointer (resid_last, with %lld new items)", who, (long long)(n - n_frozen));
+    hipError_t he = hipMemsetAsync(counters_out, 0, 2 * sizeof(int64_t), stream);
+    if (he != hipSuccess) return fail(LCREC_EHIP, "%s: %s", who, hipGetErrorString(he));
+    if (n_buckets == 0 || n == 0 || n_frozen == n) return LCREC_OK;   // (no new item: nothing can move)
+
+    ExtendParams p;
+    p.idx = idx; p.n = n; p.L = L; p.K = Kl;
+    p.resid = resid_last; p.cb = codebook_last;
+    p.members = bucket_members; p.offsets = bucket_offsets;
+    p.counters = reinterpret_cast<unsigned long long *>(counters_out);
+    p.n_frozen = n_frozen;
+    if (frozen) {
+        if (e == 16) return finish_launch<16, true>(p, n_buckets, lds, stream);
+        if (e == 32) return finish_launch<32, true>(p, n_buckets, lds, stream);
+        return finish_launch<64, true>(p, n_buckets, lds, stream);
+    }
+    if (e == 16) return finish_launch<16, false>(p, n_buckets, lds, stream);
+    if (e == 32) return finish_launch<32, false>(p, n_buckets, lds, stream);
+    return finish_launch<64, false>(p, n_buckets, lds, stream);
 }
 
 int finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e, const float *codebook_last,
                         const int64_t *bucket_members, const int64_t *bucket_offsets, int64_t n_buckets, int64_t *counters_out,
                         hipStream_t stream)
 {
-    if (!counters_out) return fail(LCREC_EINVAL, "finish_nearest_free: counters_out is NULL");
-    if (!K) return fail(LCREC_EINVAL, "finish_nearest_free: K is NULL");
-    if (L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "finish_nearest_free: L=%d (1 .. %d)", L, LCREC_MAX_LEVELS);
-    if (n < 0 || n > 0xffffffffLL) return fail(LCREC_EINVAL, "finish_nearest_free: n=%lld (0 .. 2^32 - 1)", (long long)n);
-    if (n_buckets < 0 || n_buckets > 0x7fffffffLL)
-        return fail(LCREC_EINVAL, "finish_nearest_free: n_buckets=%lld (0 .. 2^31 - 1)", (long long)n_buckets);
-    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "finish_nearest_free: e_dim=%d (supported: 16, 32, 64)", e);
-    const int Kl = K[L - 1];
-    if (Kl <= 0) return fail(LCREC_EINVAL, "finish_nearest_free: K[%d]=%d", L - 1, Kl);
-    const size_t lds = finish_lds_bytes(Kl, e);
-    if (!rq_level_fits(Kl, e, L) || lds + 512 > 160 * 1024)
-        return fail(LCREC_EUNSUPPORTED, "finish_nearest_free: level %d (K=%d, e=%d) does not fit in 160 KB of LDS", L - 1, Kl, e);
-    if (((uintptr_t)resid_last | (uintptr_t)codebook_last) & 15)
-        return fail(LCREC_EINVAL, "finish_nearest_free: resid_last and codebook_last must be 16-byte aligned");
-    if (((uintptr_t)idx | (uintptr_t)bucket_members | (uintptr_t)bucket_offsets | (uintptr_t)counters_out) & 7)
-        return fail(LCREC_EINVAL, "finish_nearest_free: idx, bucket_members, bucket_offsets and counters_out must be 8-byte aligned");
-    if (n_buckets > 0 && (!idx || !resid_last || !codebook_last || !bucket_members || !bucket_offsets))
-        return fail(LCREC_EINVAL, "finish_nearest_free: NULL pointer");
-    hipError_t he = hipMemsetAsync(counters_out, 0, 2 * sizeof(int64_t), stream);
-    if (he != hipSuccess) return fail(LCREC_EHIP, "finish_nearest_free: %s", hipGetErrorString(he));
-    if (n_buckets == 0 || n == 0) return LCREC_OK;
+    return nearest_free(false, idx, n, 0, L, K, resid_last, e, codebook_last, bucket_members, bucket_offsets, n_buckets, counters_out,
+                        stream);
+}
 
-    FinishParams p;
-    p.idx = idx; p.n = n; p.L = L; p.K = Kl;
-    p.resid = resid_last; p.cb = codebook_last;
-    p.members = bucket_members; p.offsets = bucket_offsets;
-    p.counters = reinterpret_cast<unsigned long long *>(counters_out);
-    if (e == 16) return finish_launch<16>(p, n_buckets, lds, stream);
-    if (e == 32) return finish_launch<32>(p, n_buckets, lds, stream);
-    return finish_launch<64>(p, n_buckets, lds, stream);
+int extend_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_last, int e,
+                        const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets, int64_t n_buckets,
+                        int64_t *counters_out, hipStream_t stream)
+{
+    return nearest_free(true, idx, n, n_frozen, L, K, resid_last, e, codebook_last, bucket_members, bucket_offsets, n_buckets,
+                        counters_out, stream);
 }
 
 }  // namespace lcrec

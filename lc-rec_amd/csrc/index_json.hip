@@ -98,4 +98,83 @@ int64_t index_json_format(const int64_t *idx, int64_t n, int L, int64_t first_it
     return p - out;
 }
 
+// ---- the reader: the strict inverse of index_json_format inside "{" ... "}" (include/lcrec.h: lcrec_index_json_parse)
+namespace {
+
+struct Scan {
+    const char *p, *end, *begin;
+    int64_t at() const { return p - begin; }
+    bool lit(const char *s, int n)   // the next n bytes are s: consumed; otherwise nothing is
+    {
+        if (end - p < n || memcmp(p, s, (size_t)n) != 0) return false;
+        p += n;
+        return true;
+    }
+    // decimal digits as json.dump writes an int >= 0: no sign, no leading zero, at most INT64_MAX.  0 ok, 1 malformed, 2 overflow
+    int number(int64_t *v)
+    {
+        if (p == end || *p < '0' || *p > '9') return 1;
+        if (*p == '0' && end - p > 1 && p[1] >= '0' && p[1] <= '9') return 1;
+        uint64_t u = 0;
+        while (p != end && *p >= '0' && *p <= '9') {
+            const unsigned d = (unsigned)(*p - '0');
+            if (u > (uint64_t)INT64_MAX / 10 || (u == (uint64_t)INT64_MAX / 10 && d > (uint64_t)INT64_MAX % 10)) return 2;
+            u = u * 10 + d;
+            ++p;
+        }
+        *v = (int64_t)u;
+        return 0;
+    }
+};
+
+}  // namespace
+
+int64_t index_json_parse(const char *text, int64_t len, int L, int64_t *idx_out, int64_t cap_items)
+{
+    if (L < 1 || L > 26) return fail(LCREC_EINVAL, "index_json_parse: need 1 <= L <= 26 (got L=%d)", L);
+    if (len < 0 || cap_items < 0) return fail(LCREC_EINVAL, "index_json_parse: len=%lld, cap_items=%lld", (long long)len, (long long)cap_items);
+    if (!text || (cap_items > 0 && !idx_out)) return fail(LCREC_EINVAL, "index_json_parse: NULL pointer");
+    Scan s{text, text + len, text};
+#define LCREC_PARSE_FAIL(what) \
+    return fail(LCREC_EINVAL, "index_json_parse: byte %lld (item %lld): expected %s", (long long)s.at(), (long long)item, what)
+    int64_t item = 0;
+    if (!s.lit("{", 1)) LCREC_PARSE_FAIL("'{'");
+    if (s.lit("}", 1)) {
+        if (s.p != s.end) LCREC_PARSE_FAIL("the end of the text after '}'");
+        return 0;
+    }
+    for (;;) {
+        int64_t v;
+        if (!s.lit("\"", 1)) LCREC_PARSE_FAIL("'\"' opening a key");
+        const char *key = s.p;
+        const int kr = s.number(&v);
+        if (kr != 0 || v != item) {
+            s.p = key;
+            LCREC_PARSE_FAIL("the key of this item: keys are \"0\", \"1\", ... in order");
+        }
+        if (!s.lit("\": [", 4)) LCREC_PARSE_FAIL("'\": ['");
+        if (item >= cap_items)
+            return fail(LCREC_EWORKSPACE, "index_json_parse: byte %lld: item %lld does not fit in cap_items=%lld rows", (long long)s.at(),
+                        (long long)item, (long long)cap_items);
+        int64_t *row = idx_out + item * L;
+        for (int l = 0; l < L; ++l) {
+            if (l && !s.lit(", ", 2)) LCREC_PARSE_FAIL("', ' and another token: every item has L tokens");
+            const char head[4] = {'"', '<', (char)('a' + l), '_'};
+            if (!s.lit(head, 4)) LCREC_PARSE_FAIL("a token '\"<x_' with the prefix letter of its level");
+            const int cr = s.number(&v);
+            if (cr == 2) LCREC_PARSE_FAIL("a code that fits a signed 64-bit value");
+            if (cr != 0) LCREC_PARSE_FAIL("a non-negative decimal code without leading zeros");
+            if (!s.lit(">\"", 2)) LCREC_PARSE_FAIL("'>\"' closing a token");
+            row[l] = v;
+        }
+        if (!s.lit("]", 1)) LCREC_PARSE_FAIL("']' after L tokens");
+        ++item;
+        if (s.lit(", ", 2)) continue;
+        if (!s.lit("}", 1)) LCREC_PARSE_FAIL("', ' or '}'");
+        if (s.p != s.end) LCREC_PARSE_FAIL("the end of the text after '}'");
+        return item;
+    }
+#undef LCREC_PARSE_FAIL
+}
+
 }  // namespace lcrec

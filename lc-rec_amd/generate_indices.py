@@ -19,14 +19,18 @@ Documented divergences from the reference script:
   * its 5-entry prefix list (:83) raises IndexError for L > 5; here prefixes continue <f_..>, <g_..>;
   * --finish nearest_free (off by default; `none` writes the reference's bytes) goes BEYOND the reference: after the rounds every
     item that still shares its tuple gets the nearest free last-level code (finish_collisions);
+  * --extend BASE.index.json goes BEYOND the reference too: the data file holds a catalogue that has grown, the items of BASE keep
+    their tuples byte for byte, and only the new items are indexed, around them (generate_extended);
   * it stores tokens in fixed-width numpy unicode arrays (:98-99) which silently truncate a
     replacement longer than anything seen in pass 1; integer tuples are kept here, and a warning is
     logged if a run ever hits that case (the reference's output would be corrupt there).
 """
 import argparse
 import collections
+import json
 import logging
 import os
+import re
 
 import numpy as np
 import torch
@@ -224,6 +228,153 @@ def finish_collisions(model, idx, resid_last, ks):
     return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
 
 
+# ---- opt-in: new items around an index file whose tuples are frozen (--extend BASE.index.json) -------------------------------------
+_TOKEN = re.compile(r"<([a-z])_(0|[1-9][0-9]*)>")
+
+
+def load_index_json(path, ks):
+    """int64 [N0, L] numpy array of the tuples in an `.index.json`, L = len(ks).  The library's strict reader
+    (ops.index_json_parse) takes the files this project and the reference write -- json.dump with default separators, keys "0",
+    "1", ... in order -- in one scan.  What it refuses goes through json.load and a token regex: any valid JSON whose keys are
+    exactly "0" .. "N0-1", in any order, with any white space.  Anything else raises ValueError naming the item and the level: a
+    wrong level count, a wrong prefix letter, a code >= ks[l] of the checkpoint, missing or duplicate keys."""
+    L = len(ks)
+    if L > len(PREFIX):
+        raise ValueError(f"{L} levels: no token prefix beyond <z_..>")
+    with open(path, "rb") as fp:
+        text = fp.read()
+    try:
+        idx = ops.index_json_parse(text, L)
+    except ops._lib.LcrecError as strict:
+        log.info("%s is not in the writer's own form (%s): reading it with json.load", path, strict)
+        idx = _load_index_json_slow(path, text, L)
+    for l in range(L):
+        bad = np.flatnonzero(idx[:, l] >= int(ks[l]))
+        if bad.size:
+            raise ValueError(f"{path}: item {int(bad[0])}, level {l}: code {int(idx[bad[0], l])} but the checkpoint's level {l} has "
+                             f"{int(ks[l])} codes")
+    return idx
+
+
+def _load_index_json_slow(path, text, L):
+    seen = []
+
+    def pairs(items):                                     # (json.load alone would keep the last of two equal keys silently)
+        seen.extend(k for k, _ in items)
+        return dict(items)
+    try:
+        doc = json.loads(text.decode("utf-8"), object_pairs_hook=pairs)
+    except (UnicodeDecodeError, ValueError) as exc:
+        raise ValueError(f"{path}: not an index file: {exc}") from exc
+    if not isinstance(doc, dict):
+        raise ValueError(f"{path}: not an index file: the top level is not an object")
+    n0 = len(doc)
+    if len(seen) != n0:
+        dup = collections.Counter(seen).most_common(1)[0][0]
+        raise ValueError(f"{path}: duplicate key {dup!r}")
+    idx = np.empty((n0, L), dtype=np.int64)
+    for i in range(n0):
+        toks = doc.get(str(i))
+        if str(i) not in doc:
+            extra = next(k for k in doc if not (k.isascii() and k.isdigit() and str(int(k)) == k and int(k) < n0))
+            raise ValueError(f"{path}: {n0} entries but no item {i} (keys must be \"0\" .. \"{n0 - 1}\"; found {extra!r})")
+        if not isinstance(toks, list) or len(toks) != L:
+            raise ValueError(f"{path}: item {i}: {len(toks) if isinstance(toks, list) else 'no'} tokens, the checkpoint has {L} levels")
+        for l, t in enumerate(toks):
+            m = _TOKEN.fullmatch(t) if isinstance(t, str) else None
+            if m is None or m.group(1) != chr(ord("a") + l) or int(m.group(2)) >= 1 << 63:
+                raise ValueError(f"{path}: item {i}, level {l}: {t!r} is not a token <{chr(ord('a') + l)}_CODE>")
+            idx[i, l] = int(m.group(2))
+    return idx
+
+
+@torch.no_grad()
+def extend_collisions(model, idx, n_frozen, resid_new, ks):
+    """ops.extend_nearest_free over the buckets of ALL items sharing idx[:, :L-1] -- include/lcrec.h, lcrec_extend_nearest_free,
+    states the rule.  Rows 0 .. n_frozen-1 of idx never change; resid_new holds the rows of the new items only.  Mutates idx;
+    returns dict(moved, unresolved, buckets, largest_bucket)."""
+    levels = list(model.rq.vq_layers)
+    cb_last = levels[-1].embedding.weight.detach().contiguous()
+    n, L = idx.shape
+    dev = idx.device
+    if L == 1:                                             # one bucket of all items, as finish_collisions
+        members = torch.arange(n, dtype=torch.int64, device=dev)
+        offsets = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        buckets, largest = 1, n
+    else:
+        found = ops.collision_groups(idx[:, :L - 1].contiguous(), ks[:-1], want_groups="device")
+        members, offsets = found["members"], found["offsets"]
+        buckets, largest = found["n_groups"], found["max_count"] if found["n_groups"] else 0
+    moved, unresolved = ops.extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets)
+    return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
+
+
+def _colliding(rows):
+    """items that share their tuple with an earlier one, on the host (the N == N0 path launches nothing)"""
+    return int(rows.shape[0] - np.unique(rows, axis=0).shape[0]) if rows.shape[0] else 0
+
+
+def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_path=None, verbose=True, trust_checkpoint=False):
+    """--extend: the data file holds the whole catalogue, its first N0 rows are the items of `base_file` (keys "0" .. "N0-1") and
+    rows N0 .. N-1 are new.  The output holds all N items; the first N0 entries carry exactly the base file's tuples (and, for a
+    base written by this project or by the reference, the output's first len(base) - 1 bytes are the base file's without its
+    closing brace); each new item gets its pass-1 tuple unless that tuple is taken, and then the nearest free last-level code
+    of its bucket (extend_collisions).
+
+    The Sinkhorn conflict rounds are NOT run here: they re-assign within a group of colliding items and know nothing of codes held
+    outside it, so beside a frozen catalogue most of their work would be undone again.  The distance rule alone decides.
+    --finish is ignored for the same reason.  N == N0 launches nothing and rewrites the base."""
+    ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
+    args = ckpt["args"]
+    data = EmbDataset(data_path or args.data_path, mmap=str(device).startswith("cuda"))
+    model = build_model_from_args(args, data.dim)
+    model.load_state_dict(ckpt["state_dict"])
+    ks = [int(q.embedding.weight.shape[0]) for q in model.rq.vq_layers]
+    base = load_index_json(base_file, ks)
+    n0, n = base.shape[0], len(data)
+    if n < n0:
+        raise ValueError(f"--extend: {base_file} holds {n0} items but the data file only {n} rows: the data file must hold the whole "
+                         "catalogue, the base's items first")
+    stats = {"items": n, "base_items": n0, "new_items": n - n0, "extend_moved": 0, "extend_unresolved": 0, "buckets": 0,
+             "largest_bucket": 0, "neartie_items": 0, "neartie_tau": ops.NEARTIE_TAU}
+    if n == n0:
+        final = base
+        stats["base_colliding"] = _colliding(base)
+        stats["collision_rate"] = stats["base_colliding"] / n if n else 0.0
+        stats["max_conflicts"] = int(np.unique(base, axis=0, return_counts=True)[1].max()) if n else 0
+    else:
+        dev = torch.device(device)
+        model = model.to(dev).eval()
+        audit = {}
+        idx_new, resid_new, ks = assign_all(model, data.to_device(dev, rows=(n0, n)), audit=audit)
+        stats["neartie_items"] = int((audit["neartie"] != 0).sum())
+        base_dev = torch.from_numpy(base).to(dev)
+        stats["base_colliding"] = n0 - ops.collision_groups(base_dev, ks, want_groups=False)["unique"] if n0 else 0
+        idx = torch.cat([base_dev, idx_new])
+        first_pass = idx.clone()
+        done = extend_collisions(model, idx, n0, resid_new, ks)
+        stats.update(extend_moved=done["moved"], extend_unresolved=done["unresolved"], buckets=done["buckets"],
+                     largest_bucket=done["largest_bucket"])
+        log.info("--extend: %d base items kept, %d new items, %d of them moved to the nearest free last-level code, %d unresolved "
+                 "(%d buckets listed, largest %d items)", n0, n - n0, done["moved"], done["unresolved"], done["buckets"],
+                 done["largest_bucket"])
+        if done["unresolved"]:
+            log.warning("--extend: %d new items still collide: the largest bucket (items sharing all codes but the last) holds %d "
+                        "items, the last level has %d codes", done["unresolved"], done["largest_bucket"], ks[-1])
+        _warn_if_reference_would_truncate(first_pass, idx)
+        after = ops.collision_groups(idx, ks, want_groups=False)
+        stats["collision_rate"] = (n - after["unique"]) / n
+        stats["max_conflicts"] = after["max_count"]
+        final = idx
+    if verbose:
+        print("All indices number: ", n)
+        print("Max number of conflicts: ", stats["max_conflicts"])
+        print("Collision Rate", stats["collision_rate"])
+    os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
+    dump_index_json(final, output_file)
+    return stats
+
+
 # ---- opt-in: re-evaluate near-tie items in the reference's own operation order (--recheck_neartie) -----------------------------
 def reference_order_indices(state_dict, n_layers, bn, levels, x, eps=1e-5):
     """RQVAE.get_indices(x, use_sk=False) (rqvae.py:68-72) as the reference's torch CPU op sequence on ONE batch `x` (a CPU
@@ -361,15 +512,26 @@ def sharded_assign(ctx, data, assign_fn, device):
 
 
 def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=True, ctx=None, trust_checkpoint=False,
-             recheck=False, finish="none"):
+             recheck=False, finish="none", extend=None):
     """Whole flow of generate_indices.py:51-145.  Returns a dict of the statistics it prints.
     recheck: re-evaluate the near-tie items of pass 1 in the reference's CPU operation order (recheck_neartie).
     finish: "none" (the reference's bytes) or "nearest_free" (finish_collisions after the rounds; beyond the reference).
+
+    extend: path of an existing `.index.json` whose items are the first rows of the data file: their tuples are kept and only
+        the new rows are indexed, around them (generate_extended, which says why neither the conflict rounds nor `finish` run).
 
     Under torchrun (ctx = dist.init_from_env()) pass 1 is item-sharded over the ranks and each conflict round's
     groups are sharded too (resolve_collisions); rank 0 writes the file."""
     from . import dist as ldist
     ctx = ctx or ldist.current()
+    if extend is not None:
+        if recheck:
+            raise ValueError("--extend with --recheck_neartie is not supported: the re-evaluation works on the reference's 64-row "
+                             "batches of a whole file")
+        if ctx.enabled:
+            raise ValueError("--extend under torchrun is not supported: run it in a single process")
+        return generate_extended(ckpt_path, output_file, extend, device=device, data_path=data_path, verbose=verbose,
+                                 trust_checkpoint=trust_checkpoint)
     lead = ctx.rank == 0
     verbose = verbose and lead
     if finish not in FINISH_MODES:
@@ -455,6 +617,11 @@ def parse_args(argv=None):
                     help="after the conflict rounds: none = write what still collides, as the reference does (byte-identical "
                          "output); nearest_free = every item that still shares its tuple gets the nearest free last-level code "
                          "(goes beyond the reference; only those items' last token changes)")
+    ap.add_argument("--extend", type=str, default=None, metavar="BASE.index.json",
+                    help="the data file holds a catalogue that has grown: its first N0 rows are the items of BASE.index.json, which "
+                         "keep their tuples byte for byte; only the rows after them are indexed, each new item keeping its tuple "
+                         "unless it is taken and then moving to the nearest free last-level code (goes beyond the reference).  The "
+                         "conflict rounds are not run and --finish is ignored; not with --recheck_neartie or torchrun")
     return ap.parse_args(argv)
 
 
@@ -465,7 +632,7 @@ def main(argv=None):
     out = os.path.join(a.output_dir, f"{a.dataset}.index.json")
     try:
         return generate(a.ckpt_path, out, device=a.device, data_path=a.data_path, ctx=ctx,
-                        trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish)
+                        trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish, extend=a.extend)
     finally:
         ldist.shutdown(ctx)
 

@@ -794,6 +794,42 @@ def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
     return moved, unresolved
 
 
+def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets):
+    """The frozen-aware nearest-free-code pass (lcrec_extend_nearest_free of include/lcrec.h, which states the rule): items
+    0 .. n_frozen-1 of idx never change; a new item that shares its tuple with a frozen one moves to the nearest free last-level
+    code of its bucket, and among new items only the holder nearest to a shared code keeps it.
+
+    idx int64 [n, L] is updated IN PLACE (last column, new movers only); resid_new float32 [n - n_frozen, e] holds the residual
+    entering the last level of the NEW items only (row i - n_frozen for item i); cb_last float32 [K_last, e]; members / offsets
+    are int64 device tensors in collision_groups' "device" layout over all n items.  Returns (moved, unresolved)."""
+    lib = _lib.load()
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2 and idx.is_contiguous()):
+        raise _lib.LcrecError("idx must be a contiguous int64 [n, L] device tensor (it is updated in place)")
+    n, L = idx.shape
+    n_frozen = int(n_frozen)
+    if not 0 <= n_frozen <= n:
+        raise _lib.LcrecError(f"n_frozen={n_frozen} does not go with idx {(n, L)} (0 .. {n})")
+    resid_new, cb_last = _dev(resid_new, "resid_new"), _dev(cb_last, "cb_last")
+    for name, t in (("members", members), ("offsets", offsets)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
+            raise _lib.LcrecError(f"{name} must be an int64 [*] device tensor")
+    members, offsets = members.contiguous(), offsets.contiguous()
+    if resid_new.dim() != 2 or cb_last.dim() != 2 or resid_new.shape[0] != n - n_frozen or resid_new.shape[1] != cb_last.shape[1]:
+        raise _lib.LcrecError(f"resid_new {tuple(resid_new.shape)} and cb_last {tuple(cb_last.shape)} do not go with idx {(n, L)} "
+                              f"and n_frozen={n_frozen}: one row per new item")
+    if len(ks) != L or int(ks[-1]) != cb_last.shape[0]:
+        raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}] and cb_last [{cb_last.shape[0]}, *]")
+    n_buckets = max(offsets.numel() - 1, 0)
+    dev = idx.device
+    counters = torch.empty(2, dtype=torch.int64, device=dev)
+    with _on(dev):
+        rc = lib.lcrec_extend_nearest_free(_ptr(idx), n, n_frozen, L, _ints(ks), _ptr(resid_new), resid_new.shape[1], _ptr(cb_last),
+                                           _ptr(members), _ptr(offsets), n_buckets, _ptr(counters), _stream_ptr())
+    _lib.check(rc, "lcrec_extend_nearest_free")
+    moved, unresolved = counters.tolist()
+    return moved, unresolved
+
+
 def index_json_text(idx_rows, first_item=0):
     """bytes of the `.index.json` entries of items first_item.. for a HOST int64 [n, L] array
     (generate_indices.py:83-92,138-145; see lcrec_index_json_format in include/lcrec.h)."""
@@ -811,6 +847,26 @@ def index_json_text(idx_rows, first_item=0):
     if got < 0:
         _lib.check(int(got), "lcrec_index_json_format")
     return buf[:got].tobytes()
+
+
+def index_json_parse(text, L):
+    """int64 [n, L] numpy array of the codes in an `.index.json` text (bytes), by the library's strict reader
+    (lcrec_index_json_parse of include/lcrec.h): exactly the texts index_json_text / json.dump with default separators write for
+    keys "0", "1", ... in order.  Anything else raises LcrecError, whose text names the byte offset."""
+    import numpy as np
+    lib = _lib.load()
+    if not isinstance(text, (bytes, bytearray, memoryview)):
+        raise _lib.LcrecError("text must be bytes")
+    L = int(L)
+    if not 1 <= L <= 26:
+        raise _lib.LcrecError(f"L={L}: 1 .. 26 levels (prefix letters a .. z)")
+    raw = np.frombuffer(text, dtype=np.uint8)
+    cap = raw.size // (9 * L + 7) + 1                      # the shortest item, `"0": ["<a_0>", ...], `, takes 9 L + 7 bytes
+    out = np.empty((cap, L), dtype=np.int64)
+    got = lib.lcrec_index_json_parse(raw.ctypes.data, raw.size, L, out.ctypes.data, cap)
+    if got < 0:
+        _lib.check(int(got), "lcrec_index_json_parse")
+    return out[:got].copy()
 
 
 # ---- training-step kernels (csrc/train_ops.hip)

@@ -3,17 +3,44 @@
 pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing pass, the .index.json text.
 
     python tools/generate_probe.py [--items 1000000] [--in_dim 768] [--levels 4] [--codes 256]
+    python tools/generate_probe.py --extend_new 10000,100000   # then --extend: the finished tuples as base, that many new items
 """
 import argparse
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lcrec_amd  # noqa: E402
 from lcrec_amd import generate_indices as gen, ops  # noqa: E402
+
+
+def extend_probe(model, x_new, base_file, n0, timed):
+    """The steps of generate_indices.generate_extended on a base file of n0 items and the rows x_new, each timed on its own; the
+    yardstick (a full flow over all N items) is the caller's.  Returns the lines to print."""
+    dev = x_new.device
+    ks = [int(q.embedding.weight.shape[0]) for q in model.rq.vq_layers]
+    base, t_read = timed(lambda: gen.load_index_json(base_file, ks))
+    base_dev, t_up = timed(lambda: torch.from_numpy(base).to(dev))
+    ops.trace_enable(True)
+    (idx_new, resid_new, ks), t_pass1 = timed(lambda: gen.assign_all(model, x_new))
+    tr1 = ops.trace_collect()
+    idx = torch.cat([base_dev, idx_new])
+    done, t_ext = timed(lambda: gen.extend_collisions(model, idx, n0, resid_new, ks))
+    tr2 = ops.trace_collect()
+    ops.trace_enable(False)
+    after = ops.collision_groups(idx, ks, want_groups=False)
+    assert bool((idx[:n0] == base_dev).all())
+    k = lambda tr, name: tr.get(name, (0, 0.0))[1]
+    return [f"--extend, {n0} base + {x_new.shape[0]} new items: read + parse {t_read * 1e3:.1f} ms, upload {t_up * 1e3:.2f} ms, "
+            f"pass 1 (new rows) {t_pass1 * 1e3:.1f} ms (kernel brackets {sum(v[1] for v in tr1.values()):.1f}), buckets + kernel "
+            f"{t_ext * 1e3:.2f} ms (collision_groups {k(tr2, 'collision_groups'):.2f}, extend_nearest_free "
+            f"{k(tr2, 'extend_nearest_free'):.2f} by the trace brackets)",
+            f"  buckets {done['buckets']}, largest {done['largest_bucket']} items, moved {done['moved']}, unresolved "
+            f"{done['unresolved']}, collision rate afterwards {after['collision_rate']:.6f}"]
 
 
 def main():
@@ -23,6 +50,8 @@ def main():
     ap.add_argument("--levels", type=int, default=4)
     ap.add_argument("--codes", type=int, default=256)
     ap.add_argument("--out", type=str, default="/tmp/probe.index.json")
+    ap.add_argument("--extend_new", type=str, default="", help="comma-separated counts of new items: time --extend's steps for each, "
+                    "with the run's finished tuples as the base file")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.manual_seed(2024)
@@ -114,6 +143,21 @@ def main():
     finished = ops.collision_groups(idx, ks, want_groups=False)
     _, t_json = timed(lambda: gen.dump_index_json(idx, a.out))
     size = os.path.getsize(a.out)
+    extend_lines = []
+    for count in [int(c) for c in a.extend_new.split(",") if c]:
+        x_new = torch.randn((count, a.in_dim), generator=g, device=dev)
+        extend_probe(model, x_new[:min(count, 4096)], a.out, a.items, timed)       # warm-up of the small-launch forms
+        extend_lines += extend_probe(model, x_new, a.out, a.items, timed)
+        # the yardstick: what a user does today, the whole flow again over all N items (without the file's text)
+        x_all = torch.cat([x, x_new])
+        def full():
+            i, r, k = gen.assign_all(model, x_all)
+            i, _ = gen.resolve_collisions(model, i, r, k)
+            return gen.finish_collisions(model, i, r, k)
+        fin_all, t_full = timed(full)
+        extend_lines.append(f"  yardstick, pass 1 + rounds + finish nearest_free over all {x_all.shape[0]} items: {t_full * 1e3:.1f} ms "
+                            f"(moved {fin_all['moved']}, unresolved {fin_all['unresolved']})")
+        del x_all
     os.remove(a.out)
     print(f"items {a.items}  in_dim {a.in_dim}  {a.levels} x {a.codes} codes")
     print(f"pass 1 (encode+assign)   {t_pass1 * 1e3:9.1f} ms   {a.items / t_pass1 / 1e6:7.2f} M items/s")
@@ -125,6 +169,8 @@ def main():
     print("  kernels: " + ", ".join(f"{k} {v[1]:.2f} ms/{v[0]}" for k, v in sorted(ftrace.items(), key=lambda kv: -kv[1][1])))
     print(f"  collision rate {final['collision_rate']:.6f} -> {finished['collision_rate']:.6f}")
     print(f".index.json ({size / 1e6:.0f} MB)     {t_json * 1e3:9.1f} ms   {a.items / t_json / 1e6:7.2f} M items/s (D2H + text + write)")
+    for line in extend_lines:
+        print(line)
 
 
 if __name__ == "__main__":

@@ -712,6 +712,19 @@ int lcrec_debug_rq_assign(const float *z, int64_t n, int e, const float *codeboo
                           void *workspace, size_t workspace_bytes, unsigned int *ticket, void *stream,
                           int force_split, int force_threads, int force_grid);
 
+/* The BatchNorm strip calls pick a kernel form by shape and alignment; lcrec_debug_bn_plan reports it.  Host only: nothing is
+ * launched.  call: LCREC_BN_*; aligned: whether every pointer the call would be given sits on 16 bytes; 1 <= n <= 2^20. */
+enum { LCREC_BN_FORWARD = 0, LCREC_BN_BACKWARD, LCREC_BN_STATS, LCREC_BN_BACKWARD_REDUCE, LCREC_BN_BACKWARD_APPLY };
+typedef struct {
+    int float4;               /* 1 = float4 strips (features % 4 == 0, aligned, <= 8 rows per lane, n * features < 2^29), 0 = dword */
+    int cols;                 /* strip width in columns: 4, 8 or 16 (float4); 8, 16 or 32 (dword) */
+    int rows_per_lane;        /* float4: 1, 2, 4 or 8 (the kernel's template argument); dword: 0 (a loop over the rows) */
+    int cached;               /* dword forward / backward: the lane's rows stay in registers between the passes (1025 <= n <= 32 rows per lane) */
+    int grid;                 /* workgroups, one per strip: ceil(features / cols) */
+    int xcd_order;            /* workgroup b takes strip (b % 8) * (grid / 8) + b / 8, not strip b (grid a multiple of 8) */
+} lcrec_bn_plan;
+int lcrec_debug_bn_plan(int call, int64_t n, int features, int aligned, lcrec_bn_plan *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,7 @@ _SIGNATURES = {
     "lcrec_debug_rq_assign": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int),
                                              ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_float,
                                              _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "lcrec_debug_bn_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
 }
 
 
@@ -153,6 +154,12 @@ class RqPlan(ctypes.Structure):
                 ("lds_bytes", ctypes.c_int64 * MAX_LEVELS), ("row_off", ctypes.c_int * MAX_LEVELS),
                 ("blocks_per_wave", ctypes.c_int * MAX_LEVELS), ("idle_waves", ctypes.c_int * MAX_LEVELS),
                 ("handover_reuse", ctypes.c_int)]
+
+
+class BnPlan(ctypes.Structure):
+    """lcrec_bn_plan of include/lcrec.h"""
+    _fields_ = [("float4", ctypes.c_int), ("cols", ctypes.c_int), ("rows_per_lane", ctypes.c_int), ("cached", ctypes.c_int), ("grid", ctypes.c_int),
+                ("xcd_order", ctypes.c_int)]
 
 
 class TraceEntry(ctypes.Structure):

@@ -512,6 +512,11 @@ LCREC_API int lcrec_bn_stats(const float *t, int64_t n, int features, float *mea
     return bn_stats(t, n, features, mean_out, m2_out, (hipStream_t)stream);
 }
 
+LCREC_API int lcrec_debug_bn_plan(int call, int64_t n, int features, int aligned, lcrec_bn_plan *out)
+{
+    return debug_bn_plan(call, n, features, aligned, out);
+}
+
 LCREC_API int lcrec_bn_relu_apply(const float *t, int64_t n, int features, const float *gamma, const float *beta, const float *mean,
                                   const float *rstd, int relu, float *y, void *stream)
 {

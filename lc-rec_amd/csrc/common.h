@@ -47,6 +47,10 @@ struct TraceScope {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// an int as a type: how a dispatch hands a runtime choice to a generic lambda as a template argument
+template <int N>
+struct IntC { static constexpr int value = N; };
+
 }  // namespace lcrec
 
 // lcrec_context (include/lcrec.h): the only library-owned resources that outlive a call.
@@ -238,6 +242,7 @@ int bn_relu_backward(const float *gy, const float *t, const float *y, int64_t n,
                      const float *rstd, int relu, float *dt, float *dgamma, float *dbeta, float *dbias, const float *fold_scale,
                      const float *fold_shift, hipStream_t stream);
 int bn_stats(const float *t, int64_t n, int F, float *mean_out, float *m2_out, hipStream_t stream);
+int debug_bn_plan(int call, int64_t n, int F, int aligned, lcrec_bn_plan *out);
 int bn_merge_stats(const float *rows, int world, int F, float eps, float momentum, float *mean_out, float *rstd_out,
                    float *running_mean, float *running_var, hipStream_t stream);
 int bn_relu_apply(const float *t, int64_t n, int F, const float *gamma, const float *beta, const float *mean, const float *rstd,

@@ -80,9 +80,6 @@ __device__ unsigned long long g_gen_stamps[4][64][6];
 #define LCREC_GMARK(slot) do { } while (0)
 #endif
 
-template <int N>
-struct IntC { static constexpr int value = N; };
-
 // f(IntC<0>{}) ... f(IntC<N-1>{}): a loop whose index is a compile-time constant in the body
 template <int N, int I = 0, class F>
 __device__ __forceinline__ void static_for(F &&f)

@@ -32,6 +32,17 @@ constexpr int CR_WAVES = CR_THREADS / 64;
 #endif
 constexpr int CR_UNROLL = LCREC_CR_UNROLL;
 
+// Strips are narrower than a 128-byte line (32 floats), so neighbours share lines -- and consecutive workgroups go to different
+// XCDs (round-robin over 8), each with an L2 of its own that would fetch the shared line again.  When the grid is a multiple
+// of 8, workgroup b takes strip (b % 8) * (grid / 8) + b / 8: the strips of one XCD are neighbours (measured on the float4
+// form below: backward of 1024 x 2048 in 16-column strips 13.3 -> 8.0 us).  The dword and the float4 strips share it.
+template <int COLS>
+__device__ __forceinline__ int strip_of_block()
+{
+    const int b = blockIdx.x, g = gridDim.x;
+    return (COLS < 32 && (g & 7) == 0) ? (b & 7) * (g >> 3) + (b >> 3) : b;
+}
+
 // Strip geometry: COLS columns x RGS = 1024 / COLS row groups; lane l of a wave holds column l % COLS, so a wave spans
 // 64 / COLS consecutive row groups.  Row group g owns rows g, g + RGS, ... (each lane adds its rows in ascending order,
 // CR_UNROLL loads in flight); the groups of a wave are added by xor-shuffles (a fixed tree), the 16 waves through LDS in
@@ -41,16 +52,7 @@ struct Strip {
     static constexpr int RGS = CR_THREADS / COLS;
     int c, rg, col;
     bool live;
-    // Strips are narrower than a 128-byte line (32 floats), so neighbours share lines -- and consecutive workgroups go to different
-    // XCDs (round-robin over 8), each with an L2 of its own that would fetch the shared line again.  When the grid is a multiple
-    // of 8, workgroup b takes strip (b % 8) * (grid / 8) + b / 8: the strips of one XCD are neighbours (measured on the float4
-    // form below: backward of 1024 x 2048 in 16-column strips 13.3 -> 8.0 us).
-    static __device__ __forceinline__ int strip_of_block()
-    {
-        const int b = blockIdx.x, g = gridDim.x;
-        return (COLS < 32 && (g & 7) == 0) ? (b & 7) * (g >> 3) + (b >> 3) : b;
-    }
-    __device__ Strip(int F) : c(threadIdx.x % COLS), rg(threadIdx.x / COLS), col(strip_of_block() * COLS + threadIdx.x % COLS), live(col < F) {}
+    __device__ Strip(int F) : c(threadIdx.x % COLS), rg(threadIdx.x / COLS), col(strip_of_block<COLS>() * COLS + threadIdx.x % COLS), live(col < F) {}
 
     // f(row) -> value; returns the sum over this lane's rows in ascending row order
     template <typename Fn>
@@ -108,11 +110,13 @@ struct Strip {
 
 // Training-mode BatchNorm1d (+ReLU).  torch semantics: batch mean, biased variance for the normalisation,
 // running_mean/var updated with `momentum` (running_var from the unbiased variance), eps inside the square root.
-// CACHED (n <= CR_MAXR rows per lane): the lane's rows stay in registers between the statistics pass and the apply pass --
-// t is read from memory once.  Same sums in the same order as the two-pass form, hence the same bits.
+// STATS: only the local statistics of a rank's rows (lcrec_bn_stats: mean -> mean_out, M2 = sum (t - mean)^2 -> rstd_out, to be
+// merged over ranks, Chan et al.), nothing applied.
+// CACHED (n <= CR_MAXR rows per lane, not with STATS): the lane's rows stay in registers between the statistics pass and the
+// apply pass -- t is read from memory once.  Same sums in the same order as the two-pass form, hence the same bits.
 constexpr int CR_MAXR = 32;
 
-template <int COLS, bool CACHED>
+template <int COLS, bool STATS = false, bool CACHED = false>
 __global__ __launch_bounds__(CR_THREADS) void bn_relu_forward_kernel(const float *__restrict__ t, int64_t n, int F,
                                                                       const float *__restrict__ gamma, const float *__restrict__ beta,
                                                                       float eps, float momentum, float *running_mean,
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_forward_kernel(const float
         }
 #pragma unroll
         for (int u = 0; u < CR_MAXR; ++u) {
-            const float d = tv[u] - pivot;          // rows past n contribute exact zeros, which change no sum
+            const float d = tv[u] - pivot;
             if (st.rg + (int64_t)u * RGS < n) { s1 += d; s2 += d * d; }
         }
     } else {
@@ -147,10 +151,14 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_forward_kernel(const float
     }
     s1 = st.sum(s1, sm);
     s2 = st.sum(s2, sm);
-    const float dmean = s1 * inv_n;
+    const float dmean = STATS ? s1 / (float)n : s1 * inv_n;        // (the statistics form divides; its bits are in the exchange rows)
     const float mean = pivot + dmean;
     float m2 = s2 - s1 * dmean;
     m2 = m2 > 0.f ? m2 : 0.f;
+    if (STATS) {
+        if (st.live && st.rg == 0) { mean_out[col] = mean; rstd_out[col] = m2; }
+        return;
+    }
     const float var = m2 * inv_n;
     const float rstd = 1.0f / __builtin_sqrtf(var + eps);
     if (!st.live) return;
@@ -188,27 +196,40 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_forward_kernel(const float
 // Backward of y = [relu](bn(t)) for gy = dL/dy:
 //   g = gy * [y > 0];  dbeta = sum g;  dgamma = sum g * xhat;  dt = gamma * rstd * (g - dbeta/n - xhat * dgamma/n)
 // and the gradient of the Linear bias that produced t: dbias = sum dt (zero up to rounding, as in autograd).
-template <int COLS, bool CACHED>
-__global__ __launch_bounds__(CR_THREADS) void bn_relu_backward_kernel(const float *gy, const float *__restrict__ t,
-                                                                       const float *__restrict__ y, int64_t n, int F,
-                                                                       const float *__restrict__ gamma, const float *__restrict__ mean,
-                                                                       const float *__restrict__ rstd, int relu, float *dt,
-                                                                       float *dgamma, float *dbeta, float *dbias,
-                                                                       const float *__restrict__ fold_scale,
-                                                                       const float *__restrict__ fold_shift)
+struct BnBwd {
+    const float *gy, *t, *y;
+    int64_t n;
+    int F;
+    const float *gamma, *mean, *rstd;
+    int relu;
+    float *dt, *dgamma, *dbeta, *dbias;
+    const float *fold_scale, *fold_shift;
+    float *sum_g, *sum_gx;      // MODE 1: out, this rank's column sums of g and g * xhat; MODE 2: in, the sums over all ranks
+    float n_total;              // MODE 2: rows of the global batch
+};
+// MODE 0: the whole backward of one process.  The data-parallel split (SyncBatchNorm semantics: the batch is the union of the
+// ranks' rows, xhat from the GLOBAL statistics; lcrec_amd/layers.py all-reduces between the halves): MODE 1 =
+// lcrec_bn_backward_reduce (the two column sums of this rank's rows, nothing written to dt), MODE 2 = lcrec_bn_backward_apply (dt
+// and dbias from the global sums).  The halves take the ReLU mask from y alone (their host entries pass no fold).
+// CACHED (MODE 0 only): the lane's masked gradients and xhat stay in registers, as in the forward.
+template <int COLS, int MODE = 0, bool CACHED = false>
+__global__ __launch_bounds__(CR_THREADS) void bn_relu_backward_kernel(BnBwd p)
 {
     __shared__ float sm[CR_WAVES][COLS];
     constexpr int RGS = Strip<COLS>::RGS;
+    const float *gy = p.gy, *__restrict__ t = p.t, *__restrict__ y = p.y;
+    const int64_t n = p.n;
+    const int F = p.F, relu = p.relu;
     const Strip<COLS> st(F);
     const int col = st.live ? st.col : 0;
-    const float mu = mean[col], rs = rstd[col], gm = gamma ? gamma[col] : 1.0f;
+    const float mu = p.mean[col], rs = p.rstd[col], gm = p.gamma ? p.gamma[col] : 1.0f;
     const float *gc = gy + col, *tc = t + col, *yc = (relu && y) ? y + col : nullptr;
     // the ReLU mask from the stored activation y, or -- when the forward never wrote one (lcrec_linear_bn_forward hands t to the
     // next layer, which applies max(t * scale + shift, 0) itself) -- from the same fused expression the consumer evaluated; or,
     // with fold_shift alone (= beta), from lcrec_bn_relu_forward's own expression (t - mean) * rstd * gamma + beta: the bits of
     // the y it wrote, without reading it
-    const bool from_beta = relu && !y && !fold_scale;
-    const float fs = (relu && !y && fold_scale) ? fold_scale[col] : 0.f, fh = (relu && !y) ? fold_shift[col] : 0.f;
+    const bool from_beta = relu && !y && !p.fold_scale;
+    const float fs = (relu && !y && p.fold_scale) ? p.fold_scale[col] : 0.f, fh = (relu && !y) ? p.fold_shift[col] : 0.f;
     auto gval = [&](int64_t r) {
         float g = gc[r * F];
         if (relu) {
@@ -218,9 +239,12 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_backward_kernel(const floa
         }
         return g;
     };
-    float gv[CACHED ? CR_MAXR : 1], xv[CACHED ? CR_MAXR : 1];     // CACHED: the lane's masked gradients and xhat, read once
+    float gv[CACHED ? CR_MAXR : 1], xv[CACHED ? CR_MAXR : 1];
     float db = 0.f, dg = 0.f;
-    if (CACHED) {
+    if (MODE == 2) {
+        db = p.sum_g[col];
+        dg = p.sum_gx[col];
+    } else if (CACHED) {
 #pragma unroll
         for (int u = 0; u < CR_MAXR; ++u) {
             const int64_t r = st.rg + (int64_t)u * RGS;
@@ -231,41 +255,50 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_backward_kernel(const floa
 #pragma unroll
         for (int u = 0; u < CR_MAXR; ++u)
             if (st.rg + (int64_t)u * RGS < n) { db += gv[u]; dg += gv[u] * xv[u]; }
+        db = st.sum(db, sm);
+        dg = st.sum(dg, sm);
     } else {
         st.rows2(n, db, dg, [&](int64_t r, float &a, float &b) { const float g = gval(r); a = g; b = g * ((tc[r * F] - mu) * rs); });
+        db = st.sum(db, sm);
+        dg = st.sum(dg, sm);
     }
-    db = st.sum(db, sm);
-    dg = st.sum(dg, sm);
-    const float inv_n = 1.0f / (float)n;
+    if (MODE == 1) {
+        if (st.live && st.rg == 0) {
+            p.sum_g[col] = db;
+            p.sum_gx[col] = dg;
+            if (p.dbeta) p.dbeta[col] = db;          // this rank's share of the parameter gradients (the gradient all-reduce sums them)
+            if (p.dgamma) p.dgamma[col] = dg;
+        }
+        return;
+    }
+    const float inv_n = 1.0f / (MODE == 2 ? p.n_total : (float)n);
     const float k = gm * rs, mdb = db * inv_n, mdg = dg * inv_n;
-    float *dc = dt + col;
+    float *dc = p.dt + col;
     float sdt = 0.f;
-    if (st.live) {
-        if (CACHED) {
+    if (st.live && CACHED) {
 #pragma unroll
-            for (int u = 0; u < CR_MAXR; ++u) {
-                const int64_t r = st.rg + (int64_t)u * RGS;
-                if (r < n) {
-                    const float v = k * (gv[u] - mdb - xv[u] * mdg);
-                    dc[r * F] = v;
-                    sdt += v;
-                }
-            }
-        } else {
-#pragma unroll 4
-            for (int64_t r = st.rg; r < n; r += RGS) {
-                const float xh = (tc[r * F] - mu) * rs;
-                const float v = k * (gval(r) - mdb - xh * mdg);
+        for (int u = 0; u < CR_MAXR; ++u) {
+            const int64_t r = st.rg + (int64_t)u * RGS;
+            if (r < n) {
+                const float v = k * (gv[u] - mdb - xv[u] * mdg);
                 dc[r * F] = v;
                 sdt += v;
             }
         }
+    } else if (st.live) {
+#pragma unroll 4
+        for (int64_t r = st.rg; r < n; r += RGS) {
+            const float xh = (tc[r * F] - mu) * rs;
+            const float v = k * (gval(r) - mdb - xh * mdg);
+            dc[r * F] = v;
+            sdt += v;
+        }
     }
     const float dbs = st.sum(sdt, sm);
     if (st.live && st.rg == 0) {
-        if (dgamma) dgamma[col] = dg;
-        if (dbeta) dbeta[col] = db;
-        if (dbias) dbias[col] = dbs;
+        if (MODE == 0 && p.dgamma) p.dgamma[col] = dg;
+        if (MODE == 0 && p.dbeta) p.dbeta[col] = db;
+        if (p.dbias) p.dbias[col] = dbs;
     }
 }
 
@@ -281,13 +314,7 @@ struct Strip4 {
     static constexpr int L4 = COLS / 4, RGS = CR_THREADS / L4;
     int c4, rg, col;
     bool live;
-    // the strip of a workgroup: neighbours on one XCD, as in Strip::strip_of_block
-    static __device__ __forceinline__ int strip_of_block()
-    {
-        const int b = blockIdx.x, g = gridDim.x;
-        return (COLS < 32 && (g & 7) == 0) ? (b & 7) * (g >> 3) + (b >> 3) : b;
-    }
-    __device__ Strip4(int F) : c4(threadIdx.x % L4), rg(threadIdx.x / L4), col(strip_of_block() * COLS + 4 * (threadIdx.x % L4)), live(col < F) {}
+    __device__ Strip4(int F) : c4(threadIdx.x % L4), rg(threadIdx.x / L4), col(strip_of_block<COLS>() * COLS + 4 * (threadIdx.x % L4)), live(col < F) {}
 
     // v + (v rotated right by N lanes within its row of 16 lanes): one v_add_f32 with a DPP operand, no LDS crossbar
     template <int N>
@@ -389,7 +416,7 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_forward_v4_kernel(const fl
     float mean[4], rstd[4], m2[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float dmean = STATS ? s[0][e] / (float)n : s[0][e] * inv_n;        // (bn_stats_kernel divides; keep its expression)
+        const float dmean = STATS ? s[0][e] / (float)n : s[0][e] * inv_n;        // (the dword statistics form divides; keep its expression)
         mean[e] = pivot[e] + dmean;
         const float m = s[1][e] - s[0][e] * dmean;
         m2[e] = m > 0.f ? m : 0.f;
@@ -435,22 +462,11 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_forward_v4_kernel(const fl
     }
 }
 
-struct Bn4Bwd {
-    const float *gy, *t, *y;
-    int64_t n;
-    int F;
-    const float *gamma, *mean, *rstd;
-    int relu;
-    float *dt, *dgamma, *dbeta, *dbias;
-    const float *fold_scale, *fold_shift;
-    float *sum_g, *sum_gx;      // MODE 1: out, this rank's column sums of g and g * xhat; MODE 2: in, the sums over all ranks
-    float n_total;              // MODE 2: rows of the global batch
-};
 // MODE 0: the whole backward of one process.  The data-parallel split (SyncBatchNorm semantics, lcrec_amd/layers.py all-reduces
 // between the halves): MODE 1 = lcrec_bn_backward_reduce (the two column sums of this rank's rows, nothing written to dt),
 // MODE 2 = lcrec_bn_backward_apply (dt and dbias from the global sums).
 template <int COLS, int RMAX, int MODE = 0>
-__global__ __launch_bounds__(CR_THREADS) void bn_relu_backward_v4_kernel(Bn4Bwd p)
+__global__ __launch_bounds__(CR_THREADS) void bn_relu_backward_v4_kernel(BnBwd p)
 {
     using S = Strip4<COLS>;
     __shared__ __attribute__((aligned(16))) float sm[S::SM_FLOATS];
@@ -546,28 +562,8 @@ __global__ __launch_bounds__(CR_THREADS) void bn_relu_backward_v4_kernel(Bn4Bwd 
     }
 }
 
-// ---- the same, split at the points where a data-parallel run exchanges statistics (SyncBatchNorm semantics: the
-// batch is the union of the ranks' rows; lcrec_amd/layers.py all-reduces between the halves)
+// ---- the rest of the data-parallel split (the strip kernels above have the halves as modes)
 //
-// local statistics of a rank's rows: mean and M2 = sum (t - mean)^2, to be merged over ranks (Chan et al.)
-template <int COLS>
-__global__ __launch_bounds__(CR_THREADS) void bn_stats_kernel(const float *__restrict__ t, int64_t n, int F, float *mean_out, float *m2_out)
-{
-    __shared__ float sm[CR_WAVES][COLS];
-    const Strip<COLS> st(F);
-    const int col = st.live ? st.col : 0;
-    const float *tc = t + col;
-    const float pivot = tc[0];
-    float s1, s2;
-    st.rows2(n, s1, s2, [&](int64_t r, float &a, float &b) { const float d = tc[r * F] - pivot; a = d; b = d * d; });
-    s1 = st.sum(s1, sm);
-    s2 = st.sum(s2, sm);
-    const float dmean = s1 / (float)n;
-    float m2 = s2 - s1 * dmean;
-    m2 = m2 > 0.f ? m2 : 0.f;
-    if (st.live && st.rg == 0) { mean_out[col] = pivot + dmean; m2_out[col] = m2; }
-}
-
 // Statistics of the union of the ranks' rows from their (n_r, mean_r[F], M2_r[F]) rows (Chan et al., merged in rank order so
 // every rank computes the same bits): mean = sum n_r mean_r / N, M2 = sum (M2_r + n_r (mean_r - mean)^2); rstd and the
 // running statistics as nn.BatchNorm1d keeps them (biased variance normalises, unbiased goes into running_var).
@@ -608,67 +604,6 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const float *__restr
         if (relu) v = v > 0.f ? v : 0.f;
         y[i] = v;
     }
-}
-
-// local sums of the backward: sum g and sum g * xhat over this rank's rows (g = gy * [y > 0], xhat from the GLOBAL statistics)
-template <int COLS>
-__global__ __launch_bounds__(CR_THREADS) void bn_backward_reduce_kernel(const float *__restrict__ gy, const float *__restrict__ t,
-                                                                        const float *__restrict__ y, int64_t n, int F,
-                                                                        const float *__restrict__ mean, const float *__restrict__ rstd,
-                                                                        int relu, float *sum_g, float *sum_gx, float *dbeta, float *dgamma)
-{
-    __shared__ float sm[CR_WAVES][COLS];
-    const Strip<COLS> st(F);
-    const int col = st.live ? st.col : 0;
-    const float mu = mean[col], rs = rstd[col];
-    const float *gc = gy + col, *tc = t + col, *yc = relu ? y + col : nullptr;
-    float db, dg;
-    st.rows2(n, db, dg, [&](int64_t r, float &a, float &b) {
-        float g = gc[r * F];
-        if (relu && !(yc[r * F] > 0.f)) g = 0.f;
-        a = g;
-        b = g * ((tc[r * F] - mu) * rs);
-    });
-    db = st.sum(db, sm);
-    dg = st.sum(dg, sm);
-    if (st.live && st.rg == 0) {
-        sum_g[col] = db; sum_gx[col] = dg;
-        if (dbeta) dbeta[col] = db;          // this rank's share of the parameter gradients (the gradient all-reduce sums them)
-        if (dgamma) dgamma[col] = dg;
-    }
-}
-
-// dt = gamma * rstd * (g - sum_g / n_total - xhat * sum_gx / n_total) with the GLOBAL sums; dbias = local column sums of dt
-template <int COLS>
-__global__ __launch_bounds__(CR_THREADS) void bn_backward_apply_kernel(const float *gy, const float *__restrict__ t,
-                                                                       const float *__restrict__ y, int64_t n, int F,
-                                                                       const float *__restrict__ gamma, const float *__restrict__ mean,
-                                                                       const float *__restrict__ rstd, int relu,
-                                                                       const float *__restrict__ sum_g, const float *__restrict__ sum_gx,
-                                                                       float n_total, float *dt, float *dbias)
-{
-    __shared__ float sm[CR_WAVES][COLS];
-    const Strip<COLS> st(F);
-    const int col = st.live ? st.col : 0;
-    const float mu = mean[col], rs = rstd[col], gm = gamma ? gamma[col] : 1.0f;
-    const float *gc = gy + col, *tc = t + col, *yc = relu ? y + col : nullptr;
-    const float inv_n = 1.0f / n_total;
-    const float k = gm * rs, mdb = sum_g[col] * inv_n, mdg = sum_gx[col] * inv_n;
-    float *dc = dt + col;
-    float sdt = 0.f;
-    if (st.live) {
-#pragma unroll 4
-        for (int64_t r = st.rg; r < n; r += Strip<COLS>::RGS) {
-            float g = gc[r * F];
-            if (relu && !(yc[r * F] > 0.f)) g = 0.f;
-            const float xh = (tc[r * F] - mu) * rs;
-            const float v = k * (g - mdb - xh * mdg);
-            dc[r * F] = v;
-            sdt += v;
-        }
-    }
-    const float dbs = st.sum(sdt, sm);
-    if (st.live && st.rg == 0 && dbias) dbias[col] = dbs;
 }
 
 // g = gy * [y > 0] (in place allowed), dbias = column sums of g
@@ -1212,7 +1147,7 @@ __global__ __launch_bounds__(CAST_THREADS) void cast_rows_kernel(const SRC *__re
 
 // ---------------------------------------------------------------- host side
 
-// strip width by feature count: wide layers read 128-byte row segments; narrow ones take narrower strips so that more
+// dword strip width by feature count: wide layers read 128-byte row segments; narrow ones take narrower strips so that more
 // than a handful of CUs work (their whole input is a few hundred KB)
 static int strip_cols(int F)
 {
@@ -1222,66 +1157,120 @@ static int strip_cols(int F)
     // measured again after the step had become GPU-bound (batch 1024, ms per step at 768-d / 4096-d): this table's
     // predecessor (32 from 1024 columns, 16 from 256, else 8) 1.259 / 1.848, 8 everywhere 1.293 / 1.920, 32 everywhere
     // 1.354 / 1.929, 16 everywhere 1.241 / 1.839
-    (void)F;
     return 16;
 }
-#define LCREC_STRIP_LAUNCH(KERN, F, stream, ...)                                                                      \
-    do {                                                                                                              \
-        const int cols_ = strip_cols(F);                                                                              \
-        const dim3 grid_((unsigned)(((F) + cols_ - 1) / cols_));                                                      \
-        if (cols_ == 32) hipLaunchKernelGGL(KERN<32>, grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__);               \
-        else if (cols_ == 16) hipLaunchKernelGGL(KERN<16>, grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__);          \
-        else hipLaunchKernelGGL(KERN<8>, grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__);                            \
-    } while (0)
 
-// the same for the kernels with a register-cached form: narrower strips when that lets the lane's rows fit (n <= 32 rows per
-// lane: 1024 rows at 32 columns, 2048 at 16, 4096 at 8), the cached form whenever they do
-#define LCREC_STRIP_LAUNCH_N(KERN, F, n, stream, ...)                                                                  \
-    do {                                                                                                              \
-        int cols_ = strip_cols(F);                                                                                    \
-        while (cols_ > 8 && (int64_t)(n) > (int64_t)CR_MAXR * (CR_THREADS / cols_)) cols_ /= 2;                       \
-        /* measured (768-d recipe): at 1024 rows the second pass hits L2 anyway and the cached form is ~1 % slower; at */ \
-        /* 2048 rows the narrower strips + cached rows are ~3 % of the step faster                                    */ \
-        static const int cached_min_ = [] { const char *e = getenv("LCREC_BN_CACHED_MIN"); return e ? atoi(e) : 1025; }();   /* tuning */ \
-        const bool cached_ = (int64_t)(n) >= cached_min_ && (int64_t)(n) <= (int64_t)CR_MAXR * (CR_THREADS / cols_);  \
-        const dim3 grid_((unsigned)(((F) + cols_ - 1) / cols_));                                                      \
-        if (cols_ == 32) { if (cached_) hipLaunchKernelGGL((KERN<32, true>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); else hipLaunchKernelGGL((KERN<32, false>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); } \
-        else if (cols_ == 16) { if (cached_) hipLaunchKernelGGL((KERN<16, true>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); else hipLaunchKernelGGL((KERN<16, false>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); } \
-        else { if (cached_) hipLaunchKernelGGL((KERN<8, true>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); else hipLaunchKernelGGL((KERN<8, false>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); } \
-    } while (0)
-
-// The float4 strip kernels: strip width for (n, F), or 0 when the shape is not theirs (F not a multiple of 4, a pointer off
-// 16-byte alignment, or more rows than rmax per lane at the narrowest strip) -- then the dword kernels above run.
-static int strip4_cols(int64_t n, int F, int rmax, std::initializer_list<const void *> ptrs)
+// ---- the plan of a BatchNorm strip launch: which kernel family, strip width, rows per lane and grid a call gets for its shape.
+// The five host entries below launch by it and lcrec_debug_bn_plan() reports it; neither restates the other.
+//
+// float4 strips (F a multiple of 4, every pointer on 16 bytes, n * F < 2^29 for the kernels' 32-bit offsets): 16 columns
+// (64-byte row segments) where that makes at least 32 strips; narrower strips for narrower layers, whose whole input is a few
+// hundred KB that a handful of CUs would pull from memory one after the other (in the step the operands are cold: written by a
+// GEMM on other XCDs, or a whole forward pass ago).  32-column strips: measured no better than 16 once the strips of an XCD are
+// neighbours (tools/bn_probe.py).  Narrowed while n exceeds 8 rows per lane; beyond that at 4 columns the shape is not theirs.
+// dword strips (everything else): strip_cols(F); the whole forward and backward narrow it towards 8 columns while n exceeds
+// CR_MAXR rows per lane, so that the register-cached form fits (the halves of the data-parallel split have none and do not
+// narrow): the width sets the number of row groups, hence the order of the sums and the bits.  Cached from 1025 rows -- measured
+// (768-d recipe): at 1024 rows the second pass hits L2 anyway and the cached form is ~1 % slower; at 2048 rows the narrower
+// strips + cached rows are ~3 % of the step faster.
+constexpr int V4_MAX_ROWS = 8;
+static lcrec_bn_plan bn_plan(int call, int64_t n, int F, bool aligned)
 {
-    static const int mode = [] { const char *e = getenv("LCREC_BN_V4"); return e ? atoi(e) : 1; }();   // 0 off; 4 / 8 / 16 force a strip width (tuning)
-    if (!mode || (F & 3) || n * F >= ((int64_t)1 << 29)) return 0;       // 32-bit byte offsets inside the kernels
-    for (const void *p : ptrs)
-        if ((uintptr_t)p & 15) return 0;
-    // 16 columns (64-byte row segments) where that makes at least 32 strips; narrower strips for narrower layers, whose whole
-    // input is a few hundred KB that a handful of CUs would pull from memory one after the other (in the step the operands are
-    // cold: written by a GEMM on other XCDs, or a whole forward pass ago).  32-column strips: measured no better than 16 once
-    // the strips of an XCD are neighbours (tools/bn_probe.py).
-    int cols = mode == 4 || mode == 8 || mode == 16 ? mode : (F >= 512 ? 16 : (F >= 256 ? 8 : 4));
-    while (cols > 4 && n > (int64_t)rmax * (CR_THREADS / (cols / 4))) cols /= 2;
-    return n <= (int64_t)rmax * (CR_THREADS / (cols / 4)) ? cols : 0;
+    static const int v4 = [] { const char *e = getenv("LCREC_BN_V4"); return e ? atoi(e) : 1; }();   // 0 off; 4 / 8 / 16 force a strip width (tuning)
+    lcrec_bn_plan p = {};
+    if (v4 && !(F & 3) && aligned && n * F < ((int64_t)1 << 29)) {
+        int cols = v4 == 4 || v4 == 8 || v4 == 16 ? v4 : (F >= 512 ? 16 : (F >= 256 ? 8 : 4));
+        while (cols > 4 && n > (int64_t)V4_MAX_ROWS * (CR_THREADS / (cols / 4))) cols /= 2;
+        const int64_t rgs = CR_THREADS / (cols / 4);
+        if (n <= V4_MAX_ROWS * rgs) {
+            p.float4 = 1;
+            p.cols = cols;
+            p.rows_per_lane = n <= rgs ? 1 : (n <= 2 * rgs ? 2 : (n <= 4 * rgs ? 4 : 8));
+        }
+    }
+    if (!p.float4) {
+        p.cols = strip_cols(F);
+        if (call == LCREC_BN_FORWARD || call == LCREC_BN_BACKWARD) {
+            static const int cached_min = [] { const char *e = getenv("LCREC_BN_CACHED_MIN"); return e ? atoi(e) : 1025; }();   // tuning
+            while (p.cols > 8 && n > (int64_t)CR_MAXR * (CR_THREADS / p.cols)) p.cols /= 2;
+            p.cached = n >= cached_min && n <= (int64_t)CR_MAXR * (CR_THREADS / p.cols);
+        }
+    }
+    p.grid = (F + p.cols - 1) / p.cols;
+    p.xcd_order = p.cols < 32 && (p.grid & 7) == 0;          // strip_of_block()
+    return p;
 }
-// rows per lane: 1, 2, 4 or 8 by n
-#define LCREC_STRIP4_R8(KERN, COLS_, MODE_, n, grid_, stream, ...)                                                     \
-    do {                                                                                                              \
-        const int64_t rgs_ = CR_THREADS / (COLS_ / 4);                                                                \
-        if ((n) <= rgs_) hipLaunchKernelGGL((KERN<COLS_, 1, MODE_>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); \
-        else if ((n) <= 2 * rgs_) hipLaunchKernelGGL((KERN<COLS_, 2, MODE_>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); \
-        else if ((n) <= 4 * rgs_) hipLaunchKernelGGL((KERN<COLS_, 4, MODE_>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERN<COLS_, 8, MODE_>), grid_, dim3(CR_THREADS), 0, stream, __VA_ARGS__);             \
-    } while (0)
-#define LCREC_STRIP4_LAUNCH(KERN, MODE_, cols, n, F, stream, ...)                                                      \
-    do {                                                                                                              \
-        const dim3 grid_((unsigned)(((F) + (cols) - 1) / (cols)));                                                    \
-        if ((cols) == 16) LCREC_STRIP4_R8(KERN, 16, MODE_, n, grid_, stream, __VA_ARGS__);                            \
-        else if ((cols) == 8) LCREC_STRIP4_R8(KERN, 8, MODE_, n, grid_, stream, __VA_ARGS__);                         \
-        else LCREC_STRIP4_R8(KERN, 4, MODE_, n, grid_, stream, __VA_ARGS__);                                          \
-    } while (0)
+
+static bool aligned16(std::initializer_list<const void *> ptrs)
+{
+    for (const void *p : ptrs)
+        if ((uintptr_t)p & 15) return false;
+    return true;
+}
+
+// the one place a strip width (and the float4 rows per lane) becomes template arguments: f(IntC<COLS>{}) / f(IntC<COLS>{}, IntC<RMAX>{})
+template <class Fn>
+static void with_strip(int cols, Fn &&f) { cols == 32 ? f(IntC<32>{}) : cols == 16 ? f(IntC<16>{}) : f(IntC<8>{}); }
+template <class Fn>
+static void with_strip4(const lcrec_bn_plan &p, Fn &&f)
+{
+    auto rows = [&](auto cols) {
+        const int r = p.rows_per_lane;
+        r == 1 ? f(cols, IntC<1>{}) : r == 2 ? f(cols, IntC<2>{}) : r == 4 ? f(cols, IntC<4>{}) : f(cols, IntC<8>{});
+    };
+    p.cols == 16 ? rows(IntC<16>{}) : p.cols == 8 ? rows(IntC<8>{}) : rows(IntC<4>{});
+}
+
+template <bool STATS>
+static void launch_bn_forward(const lcrec_bn_plan &p, hipStream_t stream, const float *t, int64_t n, int F, const float *gamma,
+                              const float *beta, float eps, float momentum, float *running_mean, float *running_var, float *y,
+                              float *mean_out, float *rstd_out, int relu)
+{
+    const dim3 grid((unsigned)p.grid), block(CR_THREADS);
+    if (p.float4)
+        with_strip4(p, [&](auto cols, auto rmax) {
+            hipLaunchKernelGGL((bn_relu_forward_v4_kernel<decltype(cols)::value, decltype(rmax)::value, STATS>), grid, block, 0, stream, t, n, F,
+                               gamma, beta, eps, momentum, running_mean, running_var, y, mean_out, rstd_out, relu);
+        });
+    else
+        with_strip(p.cols, [&](auto cols) {
+            auto go = [&](auto cached) {
+                hipLaunchKernelGGL((bn_relu_forward_kernel<decltype(cols)::value, STATS, decltype(cached)::value != 0>), grid, block, 0, stream, t, n,
+                                   F, gamma, beta, eps, momentum, running_mean, running_var, y, mean_out, rstd_out, relu);
+            };
+            if constexpr (!STATS)
+                if (p.cached) return go(IntC<1>{});
+            go(IntC<0>{});
+        });
+}
+
+template <int MODE>
+static void launch_bn_backward(const lcrec_bn_plan &p, hipStream_t stream, const BnBwd &a)
+{
+    const dim3 grid((unsigned)p.grid), block(CR_THREADS);
+    if (p.float4)
+        with_strip4(p, [&](auto cols, auto rmax) {
+            hipLaunchKernelGGL((bn_relu_backward_v4_kernel<decltype(cols)::value, decltype(rmax)::value, MODE>), grid, block, 0, stream, a);
+        });
+    else
+        with_strip(p.cols, [&](auto cols) {
+            auto go = [&](auto cached) {
+                hipLaunchKernelGGL((bn_relu_backward_kernel<decltype(cols)::value, MODE, decltype(cached)::value != 0>), grid, block, 0, stream, a);
+            };
+            if constexpr (MODE == 0)
+                if (p.cached) return go(IntC<1>{});
+            go(IntC<0>{});
+        });
+}
+
+int debug_bn_plan(int call, int64_t n, int F, int aligned, lcrec_bn_plan *out)
+{
+    if (!out) return fail(LCREC_EINVAL, "debug_bn_plan: NULL pointer");
+    if (call < LCREC_BN_FORWARD || call > LCREC_BN_BACKWARD_APPLY) return fail(LCREC_EINVAL, "debug_bn_plan: no such call (%d)", call);
+    if (n < 1 || n > (1 << 20) || F < 1) return fail(LCREC_EUNSUPPORTED, "debug_bn_plan: sized for training batches (n=%lld)", (long long)n);
+    *out = bn_plan(call, n, F, aligned != 0);
+    return LCREC_OK;
+}
 
 int bn_relu_forward(const float *t, int64_t n, int F, const float *gamma, const float *beta, float eps, float momentum,
                     float *running_mean, float *running_var, float *y, float *mean_out, float *rstd_out, int relu,
@@ -1292,15 +1281,9 @@ int bn_relu_forward(const float *t, int64_t n, int F, const float *gamma, const 
     if (n < 2) return fail(LCREC_EINVAL, "bn_relu_forward: training-mode BatchNorm needs more than 1 row (n=%lld)", (long long)n);
     if (n > (1 << 20) || F < 1) return fail(LCREC_EUNSUPPORTED, "bn_relu_forward: sized for training batches (n=%lld)", (long long)n);
     TraceScope trace(K_BN_FWD, stream);
-    const int v4 = strip4_cols(n, F, 8, {t, y, gamma, beta, running_mean, running_var, mean_out, rstd_out});
-    if (v4) {
-        LCREC_STRIP4_LAUNCH(bn_relu_forward_v4_kernel, false, v4, n, F, stream, t, n, F, gamma, beta, eps, momentum, running_mean, running_var, y,
-                            mean_out, rstd_out, relu);
-        return check_launch("bn_relu_forward_v4_kernel");
-    }
-    LCREC_STRIP_LAUNCH_N(bn_relu_forward_kernel, F, n, stream, t, n, F, gamma, beta, eps, momentum, running_mean, running_var, y,
-                         mean_out, rstd_out, relu);
-    return check_launch("bn_relu_forward_kernel");
+    const lcrec_bn_plan p = bn_plan(LCREC_BN_FORWARD, n, F, aligned16({t, y, gamma, beta, running_mean, running_var, mean_out, rstd_out}));
+    launch_bn_forward<false>(p, stream, t, n, F, gamma, beta, eps, momentum, running_mean, running_var, y, mean_out, rstd_out, relu);
+    return check_launch(p.float4 ? "bn_relu_forward_v4_kernel" : "bn_relu_forward_kernel");
 }
 
 int bn_relu_backward(const float *gy, const float *t, const float *y, int64_t n, int F, const float *gamma, const float *mean,
@@ -1312,15 +1295,9 @@ int bn_relu_backward(const float *gy, const float *t, const float *y, int64_t n,
         return fail(LCREC_EINVAL, "bn_relu_backward: NULL pointer (with relu: y, or fold_scale and fold_shift, or fold_shift = beta alone)");
     if (n > (1 << 20) || F < 1) return fail(LCREC_EUNSUPPORTED, "bn_relu_backward: sized for training batches (n=%lld)", (long long)n);
     TraceScope trace(K_BN_BWD, stream);
-    const int v4 = strip4_cols(n, F, 8, {gy, t, y, gamma, mean, rstd, dt, dgamma, dbeta, dbias, fold_scale, fold_shift});
-    if (v4) {
-        const Bn4Bwd p{gy, t, y, n, F, gamma, mean, rstd, relu, dt, dgamma, dbeta, dbias, fold_scale, fold_shift, nullptr, nullptr, 0.f};
-        LCREC_STRIP4_LAUNCH(bn_relu_backward_v4_kernel, 0, v4, n, F, stream, p);
-        return check_launch("bn_relu_backward_v4_kernel");
-    }
-    LCREC_STRIP_LAUNCH_N(bn_relu_backward_kernel, F, n, stream, gy, t, y, n, F, gamma, mean, rstd, relu, dt, dgamma, dbeta, dbias,
-                         fold_scale, fold_shift);
-    return check_launch("bn_relu_backward_kernel");
+    const lcrec_bn_plan p = bn_plan(LCREC_BN_BACKWARD, n, F, aligned16({gy, t, y, gamma, mean, rstd, dt, dgamma, dbeta, dbias, fold_scale, fold_shift}));
+    launch_bn_backward<0>(p, stream, BnBwd{gy, t, y, n, F, gamma, mean, rstd, relu, dt, dgamma, dbeta, dbias, fold_scale, fold_shift, nullptr, nullptr, 0.f});
+    return check_launch(p.float4 ? "bn_relu_backward_v4_kernel" : "bn_relu_backward_kernel");
 }
 
 int bn_stats(const float *t, int64_t n, int F, float *mean_out, float *m2_out, hipStream_t stream)
@@ -1328,14 +1305,9 @@ int bn_stats(const float *t, int64_t n, int F, float *mean_out, float *m2_out, h
     if (!t || !mean_out || !m2_out) return fail(LCREC_EINVAL, "bn_stats: NULL pointer");
     if (n < 1 || n > (1 << 20) || F < 1) return fail(LCREC_EUNSUPPORTED, "bn_stats: sized for training batches (n=%lld)", (long long)n);
     TraceScope trace(K_BN_FWD, stream);
-    const int v4 = strip4_cols(n, F, 8, {t, mean_out, m2_out});
-    if (v4) {
-        LCREC_STRIP4_LAUNCH(bn_relu_forward_v4_kernel, true, v4, n, F, stream, t, n, F, (const float *)nullptr, (const float *)nullptr, 0.f, 0.f,
-                            (float *)nullptr, (float *)nullptr, (float *)nullptr, mean_out, m2_out, 0);
-        return check_launch("bn_relu_forward_v4_kernel<stats>");
-    }
-    LCREC_STRIP_LAUNCH(bn_stats_kernel, F, stream, t, n, F, mean_out, m2_out);
-    return check_launch("bn_stats_kernel");
+    const lcrec_bn_plan p = bn_plan(LCREC_BN_STATS, n, F, aligned16({t, mean_out, m2_out}));
+    launch_bn_forward<true>(p, stream, t, n, F, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, nullptr, mean_out, m2_out, 0);
+    return check_launch(p.float4 ? "bn_relu_forward_v4_kernel<stats>" : "bn_relu_forward_kernel<stats>");
 }
 
 int bn_merge_stats(const float *rows, int world, int F, float eps, float momentum, float *mean_out, float *rstd_out,
@@ -1367,14 +1339,9 @@ int bn_backward_reduce(const float *gy, const float *t, const float *y, int64_t 
     if (!gy || !t || !mean || !rstd || !sum_g || !sum_gx || (relu && !y)) return fail(LCREC_EINVAL, "bn_backward_reduce: NULL pointer");
     if (n < 1 || n > (1 << 20) || F < 1) return fail(LCREC_EUNSUPPORTED, "bn_backward_reduce: sized for training batches");
     TraceScope trace(K_BN_BWD, stream);
-    const int v4 = strip4_cols(n, F, 8, {gy, t, y, mean, rstd, sum_g, sum_gx, dbeta, dgamma});
-    if (v4) {
-        const Bn4Bwd p{gy, t, y, n, F, nullptr, mean, rstd, relu, nullptr, dgamma, dbeta, nullptr, nullptr, nullptr, sum_g, sum_gx, 0.f};
-        LCREC_STRIP4_LAUNCH(bn_relu_backward_v4_kernel, 1, v4, n, F, stream, p);
-        return check_launch("bn_relu_backward_v4_kernel<reduce>");
-    }
-    LCREC_STRIP_LAUNCH(bn_backward_reduce_kernel, F, stream, gy, t, y, n, F, mean, rstd, relu, sum_g, sum_gx, dbeta, dgamma);
-    return check_launch("bn_backward_reduce_kernel");
+    const lcrec_bn_plan p = bn_plan(LCREC_BN_BACKWARD_REDUCE, n, F, aligned16({gy, t, y, mean, rstd, sum_g, sum_gx, dbeta, dgamma}));
+    launch_bn_backward<1>(p, stream, BnBwd{gy, t, y, n, F, nullptr, mean, rstd, relu, nullptr, dgamma, dbeta, nullptr, nullptr, nullptr, sum_g, sum_gx, 0.f});
+    return check_launch(p.float4 ? "bn_relu_backward_v4_kernel<reduce>" : "bn_relu_backward_kernel<reduce>");
 }
 
 int bn_backward_apply(const float *gy, const float *t, const float *y, int64_t n, int F, const float *gamma, const float *mean,
@@ -1384,15 +1351,10 @@ int bn_backward_apply(const float *gy, const float *t, const float *y, int64_t n
     if (!gy || !t || !mean || !rstd || !sum_g || !sum_gx || !dt || (relu && !y)) return fail(LCREC_EINVAL, "bn_backward_apply: NULL pointer");
     if (n < 1 || n > (1 << 20) || F < 1 || !(n_total >= 1.0f)) return fail(LCREC_EUNSUPPORTED, "bn_backward_apply: sized for training batches");
     TraceScope trace(K_BN_BWD, stream);
-    const int v4 = strip4_cols(n, F, 8, {gy, t, y, gamma, mean, rstd, sum_g, sum_gx, dt, dbias});
-    if (v4) {
-        const Bn4Bwd p{gy, t, y, n, F, gamma, mean, rstd, relu, dt, nullptr, nullptr, dbias, nullptr, nullptr,
-                       const_cast<float *>(sum_g), const_cast<float *>(sum_gx), n_total};
-        LCREC_STRIP4_LAUNCH(bn_relu_backward_v4_kernel, 2, v4, n, F, stream, p);
-        return check_launch("bn_relu_backward_v4_kernel<apply>");
-    }
-    LCREC_STRIP_LAUNCH(bn_backward_apply_kernel, F, stream, gy, t, y, n, F, gamma, mean, rstd, relu, sum_g, sum_gx, n_total, dt, dbias);
-    return check_launch("bn_backward_apply_kernel");
+    const lcrec_bn_plan p = bn_plan(LCREC_BN_BACKWARD_APPLY, n, F, aligned16({gy, t, y, gamma, mean, rstd, sum_g, sum_gx, dt, dbias}));
+    launch_bn_backward<2>(p, stream, BnBwd{gy, t, y, n, F, gamma, mean, rstd, relu, dt, nullptr, nullptr, dbias, nullptr, nullptr,
+                                           const_cast<float *>(sum_g), const_cast<float *>(sum_gx), n_total});
+    return check_launch(p.float4 ? "bn_relu_backward_v4_kernel<apply>" : "bn_relu_backward_kernel<apply>");
 }
 
 int relu_bias_backward(const float *gy, const float *y, int64_t n, int F, int relu, float *g_out, float *dbias, hipStream_t stream)
@@ -1401,7 +1363,11 @@ int relu_bias_backward(const float *gy, const float *y, int64_t n, int F, int re
     if (!gy || (relu && !y)) return fail(LCREC_EINVAL, "relu_bias_backward: NULL pointer");
     if (n > (1 << 20) || F < 1) return fail(LCREC_EUNSUPPORTED, "relu_bias_backward: sized for training batches (n=%lld)", (long long)n);
     TraceScope trace(K_RELU_BIAS_BWD, stream);
-    LCREC_STRIP_LAUNCH(relu_bias_backward_kernel, F, stream, gy, y, n, F, relu, g_out, dbias);
+    const int cols = strip_cols(F);
+    with_strip(cols, [&](auto c) {
+        hipLaunchKernelGGL(relu_bias_backward_kernel<decltype(c)::value>, dim3((unsigned)((F + cols - 1) / cols)), dim3(CR_THREADS), 0, stream, gy, y,
+                           n, F, relu, g_out, dbias);
+    });
     return check_launch("relu_bias_backward_kernel");
 }
 

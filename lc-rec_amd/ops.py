@@ -941,6 +941,19 @@ def bn_stats(t, row_out=None):
     return mean, m2
 
 
+BN_CALLS = ("forward", "backward", "stats", "reduce", "apply")      # LCREC_BN_* of include/lcrec.h, in order
+
+
+def bn_plan(call, n, F, aligned=True):
+    """The kernel form the BatchNorm strip call `call` (one of BN_CALLS) takes for [n, F] rows, `aligned` saying whether every
+    pointer of the call sits on 16 bytes (include/lcrec.h, lcrec_debug_bn_plan), as a dict of the fields of lcrec_bn_plan.
+    Host only: no GPU is needed."""
+    plan = _lib.BnPlan()
+    rc = _lib.load().lcrec_debug_bn_plan(BN_CALLS.index(call), int(n), int(F), int(bool(aligned)), ctypes.addressof(plan))
+    _lib.check(rc, "lcrec_debug_bn_plan")
+    return {name: int(getattr(plan, name)) for name, _ in _lib.BnPlan._fields_}
+
+
 def bn_merge_stats(rows, eps, momentum=0.0, running_mean=None, running_var=None):
     """(mean, rstd) of the union of the ranks' rows from rows [world, 2F+1] = (n_r, mean_r, m2_r); updates the running
     statistics in place when given (lcrec_bn_merge_stats)."""

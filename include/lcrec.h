@@ -603,6 +603,66 @@ int lcrec_extend_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, 
                               const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets,
                               int64_t n_buckets, int64_t *counters_out, void *stream);
 
+/* Spill to a sibling bucket: what lcrec_finish_nearest_free and lcrec_extend_nearest_free leave unresolved.  Those two passes change
+ * last-level codes only, so a bucket (the items sharing all codes but the last) that holds more items than the last level has codes
+ * keeps colliding items.  This entry runs after either of them (opt-in, --spill; beyond the reference, as they are): an item with no
+ * room in its bucket takes the next-nearest code ONE level up -- what residual quantisation itself suggests -- and the nearest free
+ * last-level code there.  The tuple length does not change.  No cascade further up, and the two codes are chosen one after the
+ * other, not jointly.
+ *
+ * Notation: `a` is the second-to-last level L-2, with K2 = K[L-2] codes and codebook C2; the last level L-1 has K1 = K[L-1] codes and
+ * codebook C1.  r2_i / r1_i are item i's residuals entering levels L-2 / L-1.  L >= 2.
+ *
+ * The rule.  d(x, c) = (xx + cc) - 2*dot is lcrec_finish_nearest_free's distance, bit for bit: xx, cc and dot each one fp32 fma
+ * chain over the dimension ascending from 0.  Wherever two distances are compared a NaN counts as +inf, and the first minimum in code
+ * order wins.  Items with id < n_frozen are frozen (the --extend case); with n_frozen == 0 there are none.
+ *   1. Movers.  For each full tuple held by two or more items: if any holder is frozen, every new holder is a mover.  Otherwise the
+ *      new holder with the smallest d(r1_i, C1[k]), k the shared last code, keeps the tuple, a tie goes to the lowest id, and the
+ *      others are movers.  Frozen items never move; a tuple whose holders are all frozen has no mover.  This is rule 2 of the two
+ *      passes above: after either of them it names that pass's unresolved items and nobody else.
+ *   2. Super-buckets.  A super-bucket is the set of items, frozen and new, sharing idx[:, :L-2] (L = 2: one super-bucket of all
+ *      items).  A cell (a, k) is occupied when any item of the super-bucket holds idx[L-2] = a and idx[L-1] = k.  A super-bucket
+ *      without a mover is not touched.
+ *   3. Serving.  The movers of a super-bucket are served in ascending item id.  Among the codes a' whose row still has a free cell --
+ *      the mover's own row included -- the one with the smallest d(r2_i, C2[a']) is taken.  The residual entering the last level
+ *      behind it is computed as lcrec_rq_assign computes it, three fp32 operations per element with c = C2[a'] and r = r2_i:
+ *      t = c - r; s = r + t; r' = r - s.  Among the free cells of row a' the k with the smallest d(r', C1[k]) is taken.  Both codes
+ *      are written and the cell is occupied from then on.  When no row has a free cell, this mover and all later ones of the
+ *      super-bucket keep their tuple and count as unresolved.
+ * So columns 0 .. L-3 never change; only movers' rows change; frozen rows are bit-identical; a moved item collides with nobody; the
+ * number of colliding items afterwards (n minus the number of distinct tuples) equals the number colliding among the frozen items
+ * alone plus `unresolved`; unresolved is 0 whenever no touched super-bucket holds more than K2 * K1 items; and the result is a
+ * function of the inputs alone.
+ *
+ *   idx             device [n][L] int64, in/out (columns L-2 and L-1 of the items that move are rewritten); n < 2^32
+ *   n_frozen        0 .. n
+ *   K               host [L]; K[L-2] and K[L-1] are used
+ *   resid_prev      device [n - n_frozen][e] float: the residual entering level L-2 (L = 2: the latent); the row of item i is
+ *   resid_last      i - n_frozen.  resid_last likewise, entering level L-1.  Nothing is read for a frozen id.  e in {16, 32, 64}
+ *   codebook_prev   device [K2][e] and [K1][e] float.  Both are staged in LDS with an occupancy bit per cell:
+ *   codebook_last       (K2 + K1) * (4 e + 8) + K2 * (4 ceil(K1 / 32) + 4) + 512 bytes
+ *                   must fit in 160 KB (256 + 256 codes at e = 64: 144 896); a pair that does not is LCREC_EUNSUPPORTED
+ *   tuple_members, tuple_offsets, n_tuple_groups     the groups of the full idx (the shared tuples), and
+ *   super_members, super_offsets, n_super_buckets    the groups of idx[:, :L-2] (the super-buckets; L = 2: all items, one group):
+ *                   device int64, both in the layout lcrec_collision_groups emits -- group g = members[off[g] .. off[g+1]), item
+ *                   ids ascending inside a group.  A member whose id is outside [0, n), or whose code of level L-2 or L-1 is out of
+ *                   range, takes no part: it is no holder, occupies no cell and is never written.  A mover is served by the
+ *                   super-bucket that lists it.
+ *   counters_out    device int64[2]: {moved, unresolved}, zeroed by the call
+ *   workspace       device, lcrec_spill_nearest_free_workspace(n) bytes: one mover flag per item (the keeper step needs no more)
+ * Two launches: the keepers, one wave per shared tuple, set the flags; then one 256-thread workgroup per super-bucket serves its
+ * movers one after the other (two rounds of K2 and K1 distances each).  A two-level model therefore puts ALL items in one
+ * workgroup's sequential loop: correct, and slow when many items move (DESIGN.md section 8 has the measurement).
+ * No tuple group, no super-bucket or n_frozen == n: no launch, the counters are zeroed.  The float arrays 16-byte aligned, the int64
+ * arrays 8-byte.  Argument errors are reported before anything is enqueued and name the argument (workspace too small:
+ * LCREC_EWORKSPACE).  No allocation, no synchronisation, capturable.  Traced as "spill_keepers" and "spill_nearest_free". */
+size_t lcrec_spill_nearest_free_workspace(int64_t n);
+int lcrec_spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_prev,
+                             const float *resid_last, int e, const float *codebook_prev, const float *codebook_last,
+                             const int64_t *tuple_members, const int64_t *tuple_offsets, int64_t n_tuple_groups,
+                             const int64_t *super_members, const int64_t *super_offsets, int64_t n_super_buckets,
+                             int64_t *counters_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Text of the `.index.json` entries for a run of items (host-side; no device work).  Replaces the
  * per-item Python of index/generate_indices.py:83-92 (token strings "<a_{i}>", "<b_{j}>", ...) and the
  * json.dump of :138-145, whose default separators (", " and ": ") every consumer relies on

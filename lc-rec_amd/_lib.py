@@ -17,7 +17,10 @@ _vp = ctypes.c_void_p
 
 
 class LcrecError(RuntimeError):
-    pass
+    code = None                      # the LCREC_E* code of a refused library call (check); None: raised by the binding itself
+
+
+EUNSUPPORTED = -2                    # LCREC_EUNSUPPORTED of include/lcrec.h
 
 
 _SIGNATURES = {
@@ -110,6 +113,10 @@ _SIGNATURES = {
                                                  _vp, _vp, ctypes.c_int64, _vp, _vp]),
     "lcrec_extend_nearest_free": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp,
                                                  ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
+    "lcrec_spill_nearest_free_workspace": (ctypes.c_size_t, [ctypes.c_int64]),
+    "lcrec_spill_nearest_free": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp, _vp,
+                                                ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                                                ctypes.c_size_t, _vp]),
     "lcrec_index_json_bound": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
     "lcrec_index_json_format": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int64]),
     "lcrec_index_json_parse": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64]),
@@ -199,4 +206,6 @@ def load():
 def check(rc, what):
     if rc != 0:
         msg = load().lcrec_last_error().decode("utf-8", "replace")
-        raise LcrecError(f"{what} failed ({rc}): {msg}")
+        err = LcrecError(f"{what} failed ({rc}): {msg}")
+        err.code = rc
+        raise err

@@ -28,7 +28,8 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "collision_groups", "linear_fwd_pp_256x128", "linear_fwd_64x64", "sinkhorn_slab",
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
-                                           "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free"};
+                                           "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free",
+                                           "spill_nearest_free", "spill_keepers"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -397,6 +398,19 @@ LCREC_API int lcrec_extend_nearest_free(int64_t *idx, int64_t n, int64_t n_froze
 {
     return extend_nearest_free(idx, n, n_frozen, L, K, resid_last, e, codebook_last, bucket_members, bucket_offsets, n_buckets,
                                counters_out, (hipStream_t)stream);
+}
+
+LCREC_API size_t lcrec_spill_nearest_free_workspace(int64_t n) { return spill_workspace(n); }
+
+LCREC_API int lcrec_spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_prev,
+                                       const float *resid_last, int e, const float *codebook_prev, const float *codebook_last,
+                                       const int64_t *tuple_members, const int64_t *tuple_offsets, int64_t n_tuple_groups,
+                                       const int64_t *super_members, const int64_t *super_offsets, int64_t n_super_buckets,
+                                       int64_t *counters_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return spill_nearest_free(idx, n, n_frozen, L, K, resid_prev, resid_last, e, codebook_prev, codebook_last, tuple_members,
+                              tuple_offsets, n_tuple_groups, super_members, super_offsets, n_super_buckets, counters_out, workspace,
+                              workspace_bytes, (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_bn_relu_forward(const float *t, int64_t n, int features, const float *gamma, const float *beta, float eps,

@@ -352,4 +352,367 @@ int extend_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const 
                         counters_out, stream);
 }
 
+// ---- lcrec_spill_nearest_free: what the two passes above leave unresolved moves to a sibling bucket (opt-in, --spill) ----------
+//
+// A bucket that holds more items than the last level has codes cannot be separated by last codes alone.  Such an item takes
+// another code one level up -- the nearest one whose row still has a free cell -- and the nearest free last code there, both by the
+// quantiser's own distance.  include/lcrec.h, lcrec_spill_nearest_free, is the contract; tests/spill_ref.py restates it in numpy.
+//   a = level L-2 (K2 codes, codebook C2, residual r2 entering it); the last level L-1 has K1 codes, C1, r1
+//   movers       : of every full tuple held by >= 2 items -- a frozen holder: every new holder; else all new holders but the one
+//                  nearest to the shared last code (tie: lowest id)
+//   super-bucket : the items sharing idx[:, :L-2]; cell (a, k) is occupied when any of them holds it
+//   serving      : movers in ascending id; a' = nearest code (r2, C2) among the rows with a free cell, r' = r2 after C2[a'] by the
+//                  quantiser's three-op update, k = nearest free cell of row a' (r', C1); no free cell anywhere: unresolved
+//
+// Two kernels.
+//   1. spill_keepers_kernel: one wave per shared tuple (a handful of items): the holders are counted, the keeper is a wave
+//      reduction on {ordered distance bits, item id}, and the movers' flags are set in the workspace.
+//   2. spill_movers_kernel: one 256-thread workgroup per super-bucket, shaped like finish_nearest_free_kernel.  A super-bucket
+//      without a flagged member ends before anything is staged.  LDS: both codebooks (row stride E + 1), both cc vectors, one
+//      occupancy bit per cell (K2 rows of ceil(K1 / 32) words, the bits past K1 of a row's last word set for good) and the free
+//      cells per row.  Per mover two rounds of "every thread evaluates its share, wave64 shuffle reduction, one LDS step across the
+//      four waves": rows a = t, t + 256, ... with a free cell, then the free cells k = t, t + 256, ... of the row that won.
+//      fre[a] is read and written only by thread a & 255, so no barrier is needed between one mover's update and the next mover's
+//      first round; an occupancy bit is read in the second round, a barrier after the update.
+// Nothing crosses workgroups; the only global atomics are the two counters.
+struct SpillParams {
+    int64_t *idx;             // [n][L]
+    int64_t n, n_frozen;
+    int L, K2, K1;
+    const float *r2, *r1;     // [n - n_frozen][E]: the residuals entering levels L-2 and L-1
+    const float *cb2, *cb1;
+    const int64_t *tmem, *toff;   // the shared tuples
+    const int64_t *smem, *soff;   // the super-buckets
+    unsigned char *flag;      // [n] (workspace): 1 = mover
+    unsigned long long *counters;
+};
+
+template <int E>
+__global__ __launch_bounds__(FIN_THREADS) void spill_keepers_kernel(SpillParams p, int64_t n_groups)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * FIN_WAVES + (threadIdx.x >> 6);
+    if (g >= n_groups) return;                                                    // (the whole wave)
+    const int64_t lo = p.toff[g], hi = p.toff[g + 1];
+    const int64_t m = hi > lo ? hi - lo : 0;
+    const int64_t *mem = p.tmem + lo;
+    const int L = p.L;
+    const int64_t nf = p.n_frozen;
+
+    // a member is a holder when its id and both its codes are in range; any other takes no part
+    auto holder = [&](int64_t pos, int64_t &id) -> int {
+        id = mem[pos];
+        if (id < 0 || id >= p.n) return -1;
+        const int64_t a = p.idx[id * L + (L - 2)], c = p.idx[id * L + (L - 1)];
+        return (a < 0 || a >= p.K2 || c < 0 || c >= p.K1) ? -1 : (int)c;
+    };
+
+    int holders = 0, frozen = 0;
+    for (int64_t pos = lane; pos < m; pos += 64) {
+        int64_t id;
+        if (holder(pos, id) >= 0) { ++holders; frozen += id < nf; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { holders += __shfl_xor(holders, o, 64); frozen += __shfl_xor(frozen, o, 64); }
+    if (holders < 2 || holders == frozen) return;                                 // not shared, or no new holder: no mover
+
+    uint32_t kd = ~0u, ki = ~0u;                                                  // the keeper: {ordered distance, item id}
+    if (frozen == 0) {
+        for (int64_t pos = lane; pos < m; pos += 64) {
+            int64_t id;
+            const int c = holder(pos, id);
+            if (c < 0) continue;
+            float x[E];
+            load_row<E>(p.r1 + (id - nf) * E, x);
+            const float *cr = p.cb1 + (size_t)c * E;
+            float xx = 0.f, cc = 0.f;
+#pragma unroll
+            for (int j = 0; j < E; ++j) { xx = __builtin_fmaf(x[j], x[j], xx); cc = __builtin_fmaf(cr[j], cr[j], cc); }
+            const uint32_t d = ordered_bits(distance<E>(x, xx, cr, cc));
+            if (d < kd || (d == kd && (uint32_t)id < ki)) { kd = d; ki = (uint32_t)id; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t od = __shfl_xor(kd, o, 64), oi = __shfl_xor(ki, o, 64);
+            if (od < kd || (od == kd && oi < ki)) { kd = od; ki = oi; }
+        }
+    }
+    for (int64_t pos = lane; pos < m; pos += 64) {
+        int64_t id;
+        if (holder(pos, id) < 0 || id < nf) continue;
+        if (frozen > 0 || (uint32_t)id != ki) p.flag[id] = 1;
+    }
+}
+
+// (best, bk) of the whole workgroup, the same in every thread: smallest distance, lowest code on a tie; bk = 0x7fffffff: no candidate
+__device__ __forceinline__ int spill_argmin(float best, int bk, float (*red_d)[FIN_WAVES], int (*red_k)[FIN_WAVES], unsigned &step,
+                                            int lane, int wave)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float od = __shfl_xor(best, o, 64);
+        const int ok = __shfl_xor(bk, o, 64);
+        if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
+    }
+    const int par = step & 1;   // two hand-over buffers: a wave can be one reduction ahead of another, never two
+    ++step;
+    if (lane == 0) { red_d[par][wave] = best; red_k[par][wave] = bk; }
+    __syncthreads();
+    best = red_d[par][0]; bk = red_k[par][0];
+#pragma unroll
+    for (int v = 1; v < FIN_WAVES; ++v) {
+        const float od = red_d[par][v];
+        const int ok = red_k[par][v];
+        if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
+    }
+    return __builtin_amdgcn_readfirstlane(bk);
+}
+
+template <int E>
+__global__ __launch_bounds__(FIN_THREADS) void spill_movers_kernel(SpillParams p)
+{
+    constexpr int S = E + 1;   // LDS row stride (floats)
+    extern __shared__ __attribute__((aligned(16))) unsigned char spill_smem[];
+    const int K2 = p.K2, K1 = p.K1, W = (K1 + 31) >> 5;
+    float *cb2s = reinterpret_cast<float *>(spill_smem);                          // [K2][S]
+    float *cb1s = cb2s + (size_t)K2 * S;                                          // [K1][S]
+    float *cc2s = cb1s + (size_t)K1 * S;                                          // [K2]
+    float *cc1s = cc2s + K2;                                                      // [K1]
+    uint32_t *occ = reinterpret_cast<uint32_t *>(cc1s + K1);                      // [K2][W] bit k & 31 of word k >> 5: cell (a, k)
+    int *fre = reinterpret_cast<int *>(occ + (size_t)K2 * W);                     // [K2] free cells of the row
+    __shared__ unsigned long long wmask[FIN_WAVES];
+    __shared__ float red_d[2][FIN_WAVES];
+    __shared__ int red_k[2][FIN_WAVES];
+    __shared__ int sum_sh[FIN_WAVES];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t lo = p.soff[blockIdx.x], hi = p.soff[blockIdx.x + 1];
+    const int64_t m = hi > lo ? hi - lo : 0;
+    const int64_t *mem = p.smem + lo;
+    const int L = p.L;
+    const int64_t nf = p.n_frozen;
+
+    // a mover is a member the keepers flagged: a new item (id >= nf, so it has rows) whose id and codes were in range
+    auto is_mover = [&](int64_t pos) -> bool {
+        const int64_t id = mem[pos];
+        return id >= nf && id < p.n && p.flag[id] != 0;
+    };
+
+    // ---- 1. a super-bucket without a mover is not touched (the whole workgroup leaves)
+    int any = 0;
+    for (int64_t pos = tid; pos < m; pos += FIN_THREADS) any |= is_mover(pos);
+    if (!__syncthreads_or(any)) return;
+
+    // ---- 2. codebooks, cc, and the occupied cells
+    for (int q = tid; q < (K2 + K1) * (E / 4); q += FIN_THREADS) {
+        const int row = q / (E / 4), g = q % (E / 4);
+        const float *src = row < K2 ? p.cb2 + (size_t)row * E : p.cb1 + (size_t)(row - K2) * E;
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(src + 4 * g);
+        float *dst = cb2s + row * S + 4 * g;                                      // (cb1s follows cb2s: one array of K2 + K1 rows)
+        dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
+    }
+    for (int q = tid; q < K2 * W; q += FIN_THREADS)
+        occ[q] = ((q % W) == W - 1 && (K1 & 31)) ? ~0u << (K1 & 31) : 0u;        // cells past K1 never become free
+    __syncthreads();
+    for (int k = tid; k < K2 + K1; k += FIN_THREADS) {
+        const float *cr = cb2s + k * S;
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < E; ++j) a = __builtin_fmaf(cr[j], cr[j], a);
+        cc2s[k] = a;                                                              // (cc1s follows cc2s)
+    }
+    for (int64_t pos = tid; pos < m; pos += FIN_THREADS) {
+        const int64_t id = mem[pos];
+        if (id < 0 || id >= p.n) continue;
+        const int64_t a = p.idx[id * L + (L - 2)], c = p.idx[id * L + (L - 1)];
+        if (a < 0 || a >= K2 || c < 0 || c >= K1) continue;
+        atomicOr(&occ[(int)a * W + ((int)c >> 5)], 1u << ((int)c & 31));
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int a = tid; a < K2; a += FIN_THREADS) {
+        int f = 32 * W;
+        for (int w = 0; w < W; ++w) f -= __builtin_popcount(occ[a * W + w]);
+        fre[a] = f;
+        mine += f;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if (lane == 0) sum_sh[wave] = mine;
+    __syncthreads();
+    long long free_cells = 0;                                                     // K2 * K1 < 2^62
+#pragma unroll
+    for (int w = 0; w < FIN_WAVES; ++w) free_cells += sum_sh[w];
+
+    // ---- 3. movers, in position (= id) order, a chunk of 256 positions at a time
+    // free_cells, moved, late and step are the same in every thread: each derives them from the same LDS values.
+    unsigned long long moved = 0, late = 0;
+    unsigned my_late = 0;
+    unsigned step = 0;
+    for (int64_t base = 0; base < m; base += FIN_THREADS) {
+        const int64_t pos = base + tid;
+        const bool mover = pos < m && is_mover(pos);
+        if (free_cells == 0) { my_late += mover; continue; }
+        const unsigned long long own = __ballot(mover);
+        if (lane == 0) wmask[wave] = own;
+        __syncthreads();
+        unsigned long long masks[FIN_WAVES];
+#pragma unroll
+        for (int w = 0; w < FIN_WAVES; ++w) {
+            const unsigned long long v = wmask[w];
+            masks[w] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
+                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
+        }
+#pragma unroll
+        for (int w = 0; w < FIN_WAVES; ++w) {
+            unsigned long long mask = masks[w];
+            while (mask) {
+                if (free_cells == 0) { late += __builtin_popcountll(mask); break; }
+                const int bit = __builtin_ctzll(mask);
+                mask &= mask - 1;
+                const int64_t id = mem[base + w * 64 + bit];                      // in range and new: it was found a mover above
+                float x[E];
+                load_row<E>(p.r2 + (id - nf) * E, x);
+                float xx = 0.f;
+#pragma unroll
+                for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
+                // round 1: the nearest code of level L-2 among the rows with a free cell
+                float best = __builtin_inff();
+                int ba = 0x7fffffff;
+                for (int a = tid; a < K2; a += FIN_THREADS) {
+                    if (fre[a] <= 0) continue;
+                    float d = distance<E>(x, xx, cb2s + a * S, cc2s[a]);
+                    if (!(d == d)) d = __builtin_inff();
+                    if (ba == 0x7fffffff || d < best) { best = d; ba = a; }
+                }
+                ba = spill_argmin(best, ba, red_d, red_k, step, lane, wave);      // free_cells > 0, so ba is a row
+                // the residual entering the last level behind code ba: t = c - r; s = r + t; r' = r - s
+                const float *c2 = cb2s + ba * S;
+                xx = 0.f;
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    const float t = c2[j] - x[j];
+                    const float s = x[j] + t;
+                    x[j] = x[j] - s;
+                }
+#pragma unroll
+                for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
+                // round 2: the nearest free cell of that row
+                best = __builtin_inff();
+                int bk = 0x7fffffff;
+                const uint32_t *row = occ + ba * W;
+                for (int k = tid; k < K1; k += FIN_THREADS) {
+                    if ((row[k >> 5] >> (k & 31)) & 1u) continue;
+                    float d = distance<E>(x, xx, cb1s + k * S, cc1s[k]);
+                    if (!(d == d)) d = __builtin_inff();
+                    if (bk == 0x7fffffff || d < best) { best = d; bk = k; }
+                }
+                bk = spill_argmin(best, bk, red_d, red_k, step, lane, wave);      // fre[ba] > 0, so bk is a cell
+                if (tid == (bk & (FIN_THREADS - 1))) {
+                    atomicOr(&occ[ba * W + (bk >> 5)], 1u << (bk & 31));
+                    p.idx[id * L + (L - 2)] = (int64_t)ba;
+                    p.idx[id * L + (L - 1)] = (int64_t)bk;
+                }
+                if (tid == (ba & (FIN_THREADS - 1))) fre[ba] -= 1;                // its owner: the only thread that reads it
+                ++moved;
+                --free_cells;
+            }
+        }
+        __syncthreads();   // wmask is rewritten by the next chunk
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) my_late += __shfl_xor(my_late, o, 64);
+    __syncthreads();
+    if (lane == 0) sum_sh[wave] = (int)my_late;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 0; w < FIN_WAVES; ++w) late += (unsigned)sum_sh[w];
+        if (moved) atomicAdd(&p.counters[0], moved);
+        if (late) atomicAdd(&p.counters[1], late);
+    }
+}
+
+// include/lcrec.h states this formula
+static size_t spill_lds_bytes(int K2, int K1, int e)
+{
+    const size_t words = (size_t)(K1 + 31) / 32;
+    return ((size_t)K2 + K1) * ((size_t)(e + 1) * 4 + 4) + (size_t)K2 * (words * 4 + 4);   // codebook rows + cc, bitmap + free count
+}
+
+size_t spill_workspace(int64_t n) { return align_up((size_t)(n > 0 ? n : 1), 256); }
+
+template <int E>
+static int spill_launch(const SpillParams &p, int64_t n_tuples, int64_t n_supers, size_t lds, hipStream_t stream)
+{
+    auto kern = spill_movers_kernel<E>;
+    hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (he != hipSuccess)
+        return fail(LCREC_EHIP, "spill_nearest_free: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(he));
+    he = hipMemsetAsync(p.flag, 0, (size_t)p.n, stream);
+    if (he != hipSuccess) return fail(LCREC_EHIP, "spill_nearest_free: %s", hipGetErrorString(he));
+    {
+        TraceScope trace(K_SPILL_KEEPERS, stream);
+        const int64_t blocks = (n_tuples + FIN_WAVES - 1) / FIN_WAVES;
+        hipLaunchKernelGGL(spill_keepers_kernel<E>, dim3((unsigned)blocks), dim3(FIN_THREADS), 0, stream, p, n_tuples);
+        const int rc = check_launch("spill_keepers_kernel");
+        if (rc != LCREC_OK) return rc;
+    }
+    TraceScope trace(K_SPILL, stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_supers), dim3(FIN_THREADS), lds, stream, p);
+    return check_launch("spill_movers_kernel");
+}
+
+int spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_prev, const float *resid_last,
+                       int e, const float *codebook_prev, const float *codebook_last, const int64_t *tuple_members,
+                       const int64_t *tuple_offsets, int64_t n_tuples, const int64_t *super_members, const int64_t *super_offsets,
+                       int64_t n_supers, int64_t *counters_out, void *workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    const char *who = "spill_nearest_free";
+    if (!counters_out) return fail(LCREC_EINVAL, "%s: counters_out is NULL", who);
+    if (!K) return fail(LCREC_EINVAL, "%s: K is NULL", who);
+    if (L < 2 || L > LCREC_MAX_LEVELS)
+        return fail(LCREC_EINVAL, "%s: L=%d (2 .. %d: the pass moves an item one level above the last)", who, L, LCREC_MAX_LEVELS);
+    if (n < 0 || n > 0xffffffffLL) return fail(LCREC_EINVAL, "%s: n=%lld (0 .. 2^32 - 1)", who, (long long)n);
+    if (n_frozen < 0 || n_frozen > n)
+        return fail(LCREC_EINVAL, "%s: n_frozen=%lld (0 .. n=%lld)", who, (long long)n_frozen, (long long)n);
+    if (n_tuples < 0 || n_tuples > 0x7fffffffLL)
+        return fail(LCREC_EINVAL, "%s: n_tuple_groups=%lld (0 .. 2^31 - 1)", who, (long long)n_tuples);
+    if (n_supers < 0 || n_supers > 0x7fffffffLL)
+        return fail(LCREC_EINVAL, "%s: n_super_buckets=%lld (0 .. 2^31 - 1)", who, (long long)n_supers);
+    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
+    const int K2 = K[L - 2], K1 = K[L - 1];
+    if (K2 <= 0) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, L - 2, K2);
+    if (K1 <= 0) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, L - 1, K1);
+    const size_t lds = spill_lds_bytes(K2, K1, e);
+    if (lds + 512 > 160 * 1024)
+        return fail(LCREC_EUNSUPPORTED, "%s: levels %d and %d (K=%d and K=%d, e=%d) need %zu B of LDS together: more than 160 KB", who,
+                    L - 2, L - 1, K2, K1, e, lds + 512);
+    if (((uintptr_t)resid_prev | (uintptr_t)resid_last | (uintptr_t)codebook_prev | (uintptr_t)codebook_last) & 15)
+        return fail(LCREC_EINVAL, "%s: resid_prev, resid_last, codebook_prev and codebook_last must be 16-byte aligned", who);
+    if (((uintptr_t)idx | (uintptr_t)tuple_members | (uintptr_t)tuple_offsets | (uintptr_t)super_members | (uintptr_t)super_offsets |
+         (uintptr_t)counters_out) & 7)
+        return fail(LCREC_EINVAL, "%s: idx, the group tables and counters_out must be 8-byte aligned", who);
+    const bool work = n_tuples > 0 && n_supers > 0 && n_frozen < n;
+    if (work && (!idx || !resid_prev || !resid_last || !codebook_prev || !codebook_last || !tuple_members || !tuple_offsets ||
+                 !super_members || !super_offsets))
+        return fail(LCREC_EINVAL, "%s: NULL pointer", who);
+    const size_t need = spill_workspace(n);
+    if (work && (!workspace || workspace_bytes < need))
+        return fail(LCREC_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (lcrec_spill_nearest_free_workspace)", who,
+                    workspace ? workspace_bytes : (size_t)0, need);
+    hipError_t he = hipMemsetAsync(counters_out, 0, 2 * sizeof(int64_t), stream);
+    if (he != hipSuccess) return fail(LCREC_EHIP, "%s: %s", who, hipGetErrorString(he));
+    if (!work) return LCREC_OK;   // (no shared tuple, or no new item: nothing can move)
+
+    SpillParams p;
+    p.idx = idx; p.n = n; p.n_frozen = n_frozen; p.L = L; p.K2 = K2; p.K1 = K1;
+    p.r2 = resid_prev; p.r1 = resid_last; p.cb2 = codebook_prev; p.cb1 = codebook_last;
+    p.tmem = tuple_members; p.toff = tuple_offsets; p.smem = super_members; p.soff = super_offsets;
+    p.flag = static_cast<unsigned char *>(workspace);
+    p.counters = reinterpret_cast<unsigned long long *>(counters_out);
+    if (e == 16) return spill_launch<16>(p, n_tuples, n_supers, lds, stream);
+    if (e == 32) return spill_launch<32>(p, n_tuples, n_supers, lds, stream);
+    return spill_launch<64>(p, n_tuples, n_supers, lds, stream);
+}
+
 }  // namespace lcrec

@@ -21,6 +21,8 @@ Documented divergences from the reference script:
     item that still shares its tuple gets the nearest free last-level code (finish_collisions);
   * --extend BASE.index.json goes BEYOND the reference too: the data file holds a catalogue that has grown, the items of BASE keep
     their tuples byte for byte, and only the new items are indexed, around them (generate_extended);
+  * --spill (off by default) follows either of the two: an item they leave colliding, because its bucket holds more items than the
+    last level has codes, takes the next-nearest code one level up and the nearest free last-level code there (spill_collisions);
   * it stores tokens in fixed-width numpy unicode arrays (:98-99) which silently truncate a
     replacement longer than anything seen in pass 1; integer tuples are kept here, and a warning is
     logged if a run ever hits that case (the reference's output would be corrupt there).
@@ -125,14 +127,15 @@ def build_model_from_args(args, in_dim):
 
 
 @torch.no_grad()
-def assign_all(model, data, chunk_rows=1 << 20, audit=None):
+def assign_all(model, data, chunk_rows=1 << 20, audit=None, want_prev=False):
     """Pass 1 (:77-95): int64 [N, L] hard indices plus the residual entering the last level.
-    audit: optional dict; receives "neartie" (int32 [N], ops.NEARTIE_TAU) -- the near-tie flags of pass 1."""
+    audit: optional dict; receives "neartie" (int32 [N], ops.NEARTIE_TAU) -- the near-tie flags of pass 1.
+    want_prev: a fourth value is returned, the residual entering level L-2 (L = 2: the latent; L = 1: None) -- spill_collisions'."""
     levels = list(model.rq.vq_layers)
     Ws, bs, scs, shs = model.encoder.folded()
     cbs = [q.embedding.weight.detach() for q in levels]
     flat, ks = ops.flatten_codebooks(cbs)
-    idx_parts, last_parts, tie_parts = [], [], []
+    idx_parts, last_parts, tie_parts, prev_parts = [], [], [], []
     for lo in range(0, data.shape[0], chunk_rows):
         x = data[lo:lo + chunk_rows]
         a = {} if audit is not None else None
@@ -145,10 +148,14 @@ def assign_all(model, data, chunk_rows=1 << 20, audit=None):
             pflat, pks = ops.flatten_codebooks(cbs[:-1])
             _, _, _, resid = ops.rq_assign(latent, pflat, pks, want_resid=True)
             last_parts.append(resid[len(levels) - 1].clone())
+            if want_prev:
+                prev_parts.append(resid[len(levels) - 2].clone())
         else:
             last_parts.append(latent)
     if audit is not None:
         audit["neartie"] = torch.cat(tie_parts) if tie_parts else torch.zeros(0, dtype=torch.int32, device=data.device)
+    if want_prev:
+        return torch.cat(idx_parts), torch.cat(last_parts), ks, torch.cat(prev_parts) if prev_parts else None
     return torch.cat(idx_parts), torch.cat(last_parts), ks
 
 
@@ -309,12 +316,71 @@ def extend_collisions(model, idx, n_frozen, resid_new, ks):
     return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
 
 
+# ---- opt-in: what the two passes above leave colliding moves to a sibling bucket (--spill) ---------------------------------------
+@torch.no_grad()
+def spill_collisions(model, idx, n_frozen, resid_prev, resid_last, ks):
+    """ops.spill_nearest_free over the shared tuples and the super-buckets (the items sharing idx[:, :L-2]) -- include/lcrec.h,
+    lcrec_spill_nearest_free, states the rule.  An item whose bucket holds more items than the last level has codes is left colliding
+    by finish_collisions / extend_collisions; here it takes the nearest code of level L-2 whose row has a free cell and the nearest
+    free last-level code there.  Rows 0 .. n_frozen-1 of idx never change; resid_prev / resid_last hold the rows of the new items
+    only (all items when n_frozen == 0): the residuals entering levels L-2 and L-1.  Mutates idx (its last two columns, movers only);
+    returns dict(moved, unresolved, super_buckets, largest_super_bucket)."""
+    levels = list(model.rq.vq_layers)
+    n, L = idx.shape
+    if L < 2:
+        raise ValueError("--spill moves an item one level above the last: a one-level model has none")
+    cb_prev = levels[-2].embedding.weight.detach().contiguous()
+    cb_last = levels[-1].embedding.weight.detach().contiguous()
+    dev = idx.device
+    shared = ops.collision_groups(idx, ks, want_groups="device")
+    if L == 2:                                             # one super-bucket of all items
+        members = torch.arange(n, dtype=torch.int64, device=dev)
+        offsets = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        supers, largest = (1, n) if n else (0, 0)
+        if not n:
+            offsets = offsets[:1]
+    else:
+        found = ops.collision_groups(idx[:, :L - 2].contiguous(), ks[:-2], want_groups="device")
+        members, offsets = found["members"], found["offsets"]
+        supers, largest = found["n_groups"], found["max_count"] if found["n_groups"] else 0
+    moved, unresolved = ops.spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, ks,
+                                               (shared["members"], shared["offsets"]), (members, offsets))
+    return {"moved": moved, "unresolved": unresolved, "super_buckets": supers, "largest_super_bucket": largest}
+
+
+def _spill_and_log(model, idx, n_frozen, resid_prev, resid_last, ks, stats):
+    """--spill behind --finish nearest_free / --extend: runs spill_collisions, fills the four statistics, logs."""
+    stats.update(spill_moved=0, spill_unresolved=0, spill_super_buckets=0, largest_super_bucket=0)
+    try:
+        done = spill_collisions(model, idx, n_frozen, resid_prev, resid_last, ks)
+    except ops._lib.LcrecError as exc:
+        if getattr(exc, "code", None) != ops._lib.EUNSUPPORTED:
+            raise
+        log.warning("--spill: skipped, the earlier pass's result is kept: %s", exc)
+        return
+    stats.update(spill_moved=done["moved"], spill_unresolved=done["unresolved"], spill_super_buckets=done["super_buckets"],
+                 largest_super_bucket=done["largest_super_bucket"])
+    log.info("--spill: %d items moved to a free cell of a sibling bucket, %d unresolved (%d super-buckets listed, largest %d items)",
+             done["moved"], done["unresolved"], done["super_buckets"], done["largest_super_bucket"])
+    if done["unresolved"]:
+        log.warning("--spill: %d items still collide: the largest super-bucket (items sharing all codes but the last two) holds %d "
+                    "items, the last two levels have %d x %d = %d cells", done["unresolved"], done["largest_super_bucket"],
+                    ks[-2], ks[-1], ks[-2] * ks[-1])
+
+
+def _refuse_one_level(args):
+    if len(args.num_emb_list) < 2:
+        raise ValueError("--spill moves an item one level above the last: this checkpoint's model has one level "
+                         f"(num_emb_list={list(args.num_emb_list)})")
+
+
 def _colliding(rows):
     """items that share their tuple with an earlier one, on the host (the N == N0 path launches nothing)"""
     return int(rows.shape[0] - np.unique(rows, axis=0).shape[0]) if rows.shape[0] else 0
 
 
-def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_path=None, verbose=True, trust_checkpoint=False):
+def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_path=None, verbose=True, trust_checkpoint=False,
+                      spill=False):
     """--extend: the data file holds the whole catalogue, its first N0 rows are the items of `base_file` (keys "0" .. "N0-1") and
     rows N0 .. N-1 are new.  The output holds all N items; the first N0 entries carry exactly the base file's tuples (and, for a
     base written by this project or by the reference, the output's first len(base) - 1 bytes are the base file's without its
@@ -323,9 +389,12 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
 
     The Sinkhorn conflict rounds are NOT run here: they re-assign within a group of colliding items and know nothing of codes held
     outside it, so beside a frozen catalogue most of their work would be undone again.  The distance rule alone decides.
-    --finish is ignored for the same reason.  N == N0 launches nothing and rewrites the base."""
+    --finish is ignored for the same reason.  N == N0 launches nothing and rewrites the base.
+    spill: the new items that extend_collisions leaves unresolved go through spill_collisions."""
     ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
     args = ckpt["args"]
+    if spill:
+        _refuse_one_level(args)
     data = EmbDataset(data_path or args.data_path, mmap=str(device).startswith("cuda"))
     model = build_model_from_args(args, data.dim)
     model.load_state_dict(ckpt["state_dict"])
@@ -337,6 +406,8 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
                          "catalogue, the base's items first")
     stats = {"items": n, "base_items": n0, "new_items": n - n0, "extend_moved": 0, "extend_unresolved": 0, "buckets": 0,
              "largest_bucket": 0, "neartie_items": 0, "neartie_tau": ops.NEARTIE_TAU}
+    if spill:
+        stats.update(spill_moved=0, spill_unresolved=0, spill_super_buckets=0, largest_super_bucket=0)
     if n == n0:
         final = base
         stats["base_colliding"] = _colliding(base)
@@ -346,7 +417,7 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
         dev = torch.device(device)
         model = model.to(dev).eval()
         audit = {}
-        idx_new, resid_new, ks = assign_all(model, data.to_device(dev, rows=(n0, n)), audit=audit)
+        idx_new, resid_new, ks, *prev = assign_all(model, data.to_device(dev, rows=(n0, n)), audit=audit, want_prev=spill)
         stats["neartie_items"] = int((audit["neartie"] != 0).sum())
         base_dev = torch.from_numpy(base).to(dev)
         stats["base_colliding"] = n0 - ops.collision_groups(base_dev, ks, want_groups=False)["unique"] if n0 else 0
@@ -361,6 +432,8 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
         if done["unresolved"]:
             log.warning("--extend: %d new items still collide: the largest bucket (items sharing all codes but the last) holds %d "
                         "items, the last level has %d codes", done["unresolved"], done["largest_bucket"], ks[-1])
+        if spill:
+            _spill_and_log(model, idx, n0, prev[0], resid_new, ks, stats)
         _warn_if_reference_would_truncate(first_pass, idx)
         after = ops.collision_groups(idx, ks, want_groups=False)
         stats["collision_rate"] = (n - after["unique"]) / n
@@ -512,18 +585,30 @@ def sharded_assign(ctx, data, assign_fn, device):
 
 
 def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=True, ctx=None, trust_checkpoint=False,
-             recheck=False, finish="none", extend=None):
+             recheck=False, finish="none", extend=None, spill=False):
     """Whole flow of generate_indices.py:51-145.  Returns a dict of the statistics it prints.
     recheck: re-evaluate the near-tie items of pass 1 in the reference's CPU operation order (recheck_neartie).
     finish: "none" (the reference's bytes) or "nearest_free" (finish_collisions after the rounds; beyond the reference).
 
     extend: path of an existing `.index.json` whose items are the first rows of the data file: their tuples are kept and only
         the new rows are indexed, around them (generate_extended, which says why neither the conflict rounds nor `finish` run).
+    spill: after finish="nearest_free" or `extend`, the items that pass leaves unresolved move to a sibling bucket
+        (spill_collisions; beyond the reference).  Refused with ValueError before the checkpoint is opened: without one of those two
+        passes, with `recheck` (the level L-2 residuals it patches are not kept) and under torchrun; and as soon as the checkpoint's
+        arguments are read, before the data or the device are touched, for a one-level model.
 
     Under torchrun (ctx = dist.init_from_env()) pass 1 is item-sharded over the ranks and each conflict round's
     groups are sharded too (resolve_collisions); rank 0 writes the file."""
     from . import dist as ldist
     ctx = ctx or ldist.current()
+    if spill:
+        if extend is None and finish != "nearest_free":
+            raise ValueError("--spill runs over what --finish nearest_free or --extend leave unresolved: give one of them")
+        if recheck:
+            raise ValueError("--spill with --recheck_neartie is not supported: the residuals of level L-2 that the re-evaluation "
+                             "patches are not kept")
+        if ctx.enabled:
+            raise ValueError("--spill under torchrun is not supported: run it in a single process")
     if extend is not None:
         if recheck:
             raise ValueError("--extend with --recheck_neartie is not supported: the re-evaluation works on the reference's 64-row "
@@ -531,13 +616,15 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         if ctx.enabled:
             raise ValueError("--extend under torchrun is not supported: run it in a single process")
         return generate_extended(ckpt_path, output_file, extend, device=device, data_path=data_path, verbose=verbose,
-                                 trust_checkpoint=trust_checkpoint)
+                                 trust_checkpoint=trust_checkpoint, spill=spill)
     lead = ctx.rank == 0
     verbose = verbose and lead
     if finish not in FINISH_MODES:
         raise ValueError(f"finish={finish!r}: one of {FINISH_MODES}")
     ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
     args = ckpt["args"]
+    if spill:
+        _refuse_one_level(args)
     data = EmbDataset(data_path or args.data_path, mmap=ctx.enabled or str(device).startswith("cuda"))
     model = build_model_from_args(args, data.dim)
     model.load_state_dict(ckpt["state_dict"])
@@ -545,7 +632,14 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
     if verbose:
         print(model)
     audit = {}
-    idx, resid_last, ks = sharded_assign(ctx, data, lambda x: assign_all(model, x, audit=audit), device)
+    prev = []                                              # spill: the residual entering level L-2 (one process: nothing to gather)
+
+    def assign(x):
+        out = assign_all(model, x, audit=audit, want_prev=spill)
+        prev.extend(out[3:])
+        return out[:3]
+
+    idx, resid_last, ks = sharded_assign(ctx, data, assign, device)
     first_pass = idx.clone()
     # near-tie audit of pass 1: items whose two best codes at some level are closer than the rounding noise of
     # vq.py:71-73 -- the only ones a CPU run of the reference could index differently (ops.NEARTIE_TAU)
@@ -579,6 +673,9 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
                 log.warning("--finish nearest_free: %d items still collide: the largest bucket (items sharing all codes but the "
                             "last) holds %d items, the last level has %d codes", finished["unresolved"],
                             finished["largest_bucket"], ks[-1])
+    spilled = {}
+    if spill:
+        _spill_and_log(model, idx, 0, prev[0], resid_last, ks, spilled)
     _warn_if_reference_would_truncate(first_pass, idx)
     final = ops.collision_groups(idx, ks, want_groups=False)
     n = idx.shape[0]
@@ -586,6 +683,8 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
              "rounds": len(history), "groups_per_round": history, "neartie_items": neartie_items,
              "neartie_tau": ops.NEARTIE_TAU, "rechecked_items": rechecked[0], "recheck_changed": rechecked[1],
              "finish": finish, "finish_moved": finished["moved"], "finish_unresolved": finished["unresolved"]}
+    if spill:
+        stats.update(spilled)
     if lead:
         log.info("near-tie items in pass 1: %d of %d (top-2 code gap <= %.3g x distance magnitude at some level); only "
                  "these could receive a different tuple from a CPU run of the reference", neartie_items, n, ops.NEARTIE_TAU)
@@ -622,6 +721,11 @@ def parse_args(argv=None):
                          "keep their tuples byte for byte; only the rows after them are indexed, each new item keeping its tuple "
                          "unless it is taken and then moving to the nearest free last-level code (goes beyond the reference).  The "
                          "conflict rounds are not run and --finish is ignored; not with --recheck_neartie or torchrun")
+    ap.add_argument("--spill", action="store_true",
+                    help="after --finish nearest_free or --extend: an item that pass leaves colliding, because its bucket holds more "
+                         "items than the last level has codes, takes the next-nearest code one level up and the nearest free "
+                         "last-level code there (goes beyond the reference; the last two tokens of those items change).  Not with "
+                         "--recheck_neartie or torchrun; needs at least two levels")
     return ap.parse_args(argv)
 
 
@@ -632,7 +736,8 @@ def main(argv=None):
     out = os.path.join(a.output_dir, f"{a.dataset}.index.json")
     try:
         return generate(a.ckpt_path, out, device=a.device, data_path=a.data_path, ctx=ctx,
-                        trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish, extend=a.extend)
+                        trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish, extend=a.extend,
+                        spill=a.spill)
     finally:
         ldist.shutdown(ctx)
 

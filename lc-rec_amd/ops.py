@@ -830,6 +830,56 @@ def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets)
     return moved, unresolved
 
 
+def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, ks, tuple_groups, super_groups):
+    """Spill to a sibling bucket (lcrec_spill_nearest_free of include/lcrec.h, which states the rule): every item that still
+    shares its tuple after finish_nearest_free / extend_nearest_free -- its bucket has more items than the last level has codes --
+    takes the nearest code of level L-2 whose row has a free cell in its super-bucket (the items sharing idx[:, :L-2]) and the
+    nearest free last-level code there.  Items 0 .. n_frozen-1 never change.
+
+    idx int64 [n, L], L >= 2, is updated IN PLACE (columns L-2 and L-1 of the items that move); resid_prev / resid_last float32
+    [n - n_frozen, e] are the residuals entering levels L-2 / L-1 of the NEW items (row i - n_frozen for item i); cb_prev
+    [ks[L-2], e], cb_last [ks[L-1], e]; tuple_groups / super_groups are (members, offsets) pairs of int64 device tensors in
+    collision_groups' "device" layout: the groups of the full idx, and of idx[:, :L-2].  Returns (moved, unresolved)."""
+    lib = _lib.load()
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2 and idx.is_contiguous()):
+        raise _lib.LcrecError("idx must be a contiguous int64 [n, L] device tensor (it is updated in place)")
+    n, L = idx.shape
+    n_frozen = int(n_frozen)
+    if not 0 <= n_frozen <= n:
+        raise _lib.LcrecError(f"n_frozen={n_frozen} does not go with idx {(n, L)} (0 .. {n})")
+    resid_prev, resid_last = _dev(resid_prev, "resid_prev"), _dev(resid_last, "resid_last")
+    cb_prev, cb_last = _dev(cb_prev, "cb_prev"), _dev(cb_last, "cb_last")
+    tables = []
+    for what, pair in (("tuple_groups", tuple_groups), ("super_groups", super_groups)):
+        if not (isinstance(pair, (tuple, list)) and len(pair) == 2):
+            raise _lib.LcrecError(f"{what} must be a (members, offsets) pair")
+        for name, t in zip(("members", "offsets"), pair):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
+                raise _lib.LcrecError(f"{what}: {name} must be an int64 [*] device tensor")
+        tables.append((pair[0].contiguous(), pair[1].contiguous()))
+    e = cb_last.shape[1] if cb_last.dim() == 2 else -1
+    for name, t in (("resid_prev", resid_prev), ("resid_last", resid_last)):
+        if t.dim() != 2 or t.shape[0] != n - n_frozen or t.shape[1] != e:
+            raise _lib.LcrecError(f"{name} {tuple(t.shape)} does not go with idx {(n, L)}, n_frozen={n_frozen} and cb_last "
+                                  f"{tuple(cb_last.shape)}: one row per new item")
+    if L < 2:
+        raise _lib.LcrecError(f"spill_nearest_free: L={L}: the pass moves an item one level above the last, it needs two levels")
+    if len(ks) != L or cb_prev.dim() != 2 or tuple(cb_prev.shape) != (int(ks[-2]), e) or int(ks[-1]) != cb_last.shape[0]:
+        raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}], cb_prev {tuple(cb_prev.shape)} and cb_last "
+                              f"{tuple(cb_last.shape)}")
+    (tmem, toff), (smem, soff) = tables
+    dev = idx.device
+    counters = torch.empty(2, dtype=torch.int64, device=dev)
+    with _on(dev):
+        ws = _workspace(lib.lcrec_spill_nearest_free_workspace(n), dev)
+        rc = lib.lcrec_spill_nearest_free(_ptr(idx), n, n_frozen, L, _ints(ks), _ptr(resid_prev), _ptr(resid_last), e, _ptr(cb_prev),
+                                          _ptr(cb_last), _ptr(tmem), _ptr(toff), max(toff.numel() - 1, 0), _ptr(smem), _ptr(soff),
+                                          max(soff.numel() - 1, 0), _ptr(counters), _ptr(ws), ws.numel(), _stream_ptr())
+    _lib.check(rc, "lcrec_spill_nearest_free")
+    moved, unresolved = counters.tolist()
+    return moved, unresolved
+
+
 def index_json_text(idx_rows, first_item=0):
     """bytes of the `.index.json` entries of items first_item.. for a HOST int64 [n, L] array
     (generate_indices.py:83-92,138-145; see lcrec_index_json_format in include/lcrec.h)."""

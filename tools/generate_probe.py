@@ -4,6 +4,7 @@ pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing
 
     python tools/generate_probe.py [--items 1000000] [--in_dim 768] [--levels 4] [--codes 256]
     python tools/generate_probe.py --extend_new 10000,100000   # then --extend: the finished tuples as base, that many new items
+    python tools/generate_probe.py --spill [--extend_new 100000]  # then --spill over what the finishing pass (and --extend) leave
 """
 import argparse
 import os
@@ -18,7 +19,16 @@ import lcrec_amd  # noqa: E402
 from lcrec_amd import generate_indices as gen, ops  # noqa: E402
 
 
-def extend_probe(model, x_new, base_file, n0, timed):
+def spill_line(what, done, t, tr, after):
+    """One line for a timed gen.spill_collisions call and its trace."""
+    k = lambda name: tr.get(name, (0, 0.0))
+    return (f"{what}: {t * 1e3:.2f} ms (collision_groups {k('collision_groups')[1]:.2f} ms/{k('collision_groups')[0]}, spill_keepers "
+            f"{k('spill_keepers')[1]:.3f}, spill_nearest_free {k('spill_nearest_free')[1]:.3f} by the trace brackets)   super-buckets "
+            f"{done['super_buckets']}, largest {done['largest_super_bucket']} items, moved {done['moved']}, unresolved "
+            f"{done['unresolved']}, collision rate afterwards {after['collision_rate']:.6f}")
+
+
+def extend_probe(model, x_new, base_file, n0, timed, spill=False):
     """The steps of generate_indices.generate_extended on a base file of n0 items and the rows x_new, each timed on its own; the
     yardstick (a full flow over all N items) is the caller's.  Returns the lines to print."""
     dev = x_new.device
@@ -26,7 +36,7 @@ def extend_probe(model, x_new, base_file, n0, timed):
     base, t_read = timed(lambda: gen.load_index_json(base_file, ks))
     base_dev, t_up = timed(lambda: torch.from_numpy(base).to(dev))
     ops.trace_enable(True)
-    (idx_new, resid_new, ks), t_pass1 = timed(lambda: gen.assign_all(model, x_new))
+    (idx_new, resid_new, ks, *prev), t_pass1 = timed(lambda: gen.assign_all(model, x_new, want_prev=spill))
     tr1 = ops.trace_collect()
     idx = torch.cat([base_dev, idx_new])
     done, t_ext = timed(lambda: gen.extend_collisions(model, idx, n0, resid_new, ks))
@@ -35,12 +45,20 @@ def extend_probe(model, x_new, base_file, n0, timed):
     after = ops.collision_groups(idx, ks, want_groups=False)
     assert bool((idx[:n0] == base_dev).all())
     k = lambda tr, name: tr.get(name, (0, 0.0))[1]
+    more = []
+    if spill:
+        ops.trace_enable(True)
+        sp, t_sp = timed(lambda: gen.spill_collisions(model, idx, n0, prev[0], resid_new, ks))
+        tr3 = ops.trace_collect()
+        ops.trace_enable(False)
+        assert bool((idx[:n0] == base_dev).all())
+        more = ["  " + spill_line("--spill behind it", sp, t_sp, tr3, ops.collision_groups(idx, ks, want_groups=False))]
     return [f"--extend, {n0} base + {x_new.shape[0]} new items: read + parse {t_read * 1e3:.1f} ms, upload {t_up * 1e3:.2f} ms, "
             f"pass 1 (new rows) {t_pass1 * 1e3:.1f} ms (kernel brackets {sum(v[1] for v in tr1.values()):.1f}), buckets + kernel "
             f"{t_ext * 1e3:.2f} ms (collision_groups {k(tr2, 'collision_groups'):.2f}, extend_nearest_free "
             f"{k(tr2, 'extend_nearest_free'):.2f} by the trace brackets)",
             f"  buckets {done['buckets']}, largest {done['largest_bucket']} items, moved {done['moved']}, unresolved "
-            f"{done['unresolved']}, collision rate afterwards {after['collision_rate']:.6f}"]
+            f"{done['unresolved']}, collision rate afterwards {after['collision_rate']:.6f}"] + more
 
 
 def main():
@@ -52,6 +70,8 @@ def main():
     ap.add_argument("--out", type=str, default="/tmp/probe.index.json")
     ap.add_argument("--extend_new", type=str, default="", help="comma-separated counts of new items: time --extend's steps for each, "
                     "with the run's finished tuples as the base file")
+    ap.add_argument("--spill", action="store_true", help="time --spill behind the finishing pass (and behind each --extend run); the "
+                    "base file of the --extend runs is then the spilled one")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.manual_seed(2024)
@@ -100,15 +120,17 @@ def main():
                     continue
         return " ".join(out) or "clocks unreadable"
 
-    w_idx, w_resid, w_ks = gen.assign_all(model, x[:300_000])   # warm-up: every kernel form and both helper streams used once
+    w_idx, w_resid, w_ks, *w_prev = gen.assign_all(model, x[:300_000], want_prev=a.spill)   # warm-up: every kernel form and both helper streams used once
     gen.resolve_collisions(model, w_idx, w_resid, w_ks)
     gen.finish_collisions(model, w_idx, w_resid, w_ks)
+    if a.spill:
+        gen.spill_collisions(model, w_idx, 0, w_prev[0], w_resid, w_ks)
     # Pass 1, first time at full size.  What the round-1 version of this probe timed here -- and sometimes saw take 185 ms
     # instead of 62 -- includes every first-time allocation at the 1 M-item sizes (idx 32 MB, latents 128 MB, the
     # [L][n][e] residual stack 512 MB, its clone): the allocator statistics around the call say whether it went to the device
     # for memory, and the traced repeats below give kernel time against wall time once the sizes are cached.
     a0 = alloc_stats()
-    (idx, resid_last, ks), t_pass1 = timed(lambda: gen.assign_all(model, x))
+    (idx, resid_last, ks, *resid_prev), t_pass1 = timed(lambda: gen.assign_all(model, x, want_prev=a.spill))
     a1 = alloc_stats()
     print(f"pass 1, first call at full size: {t_pass1 * 1e3:.1f} ms; allocator: "
           + ", ".join(f"{k} +{a1[k] - a0[k]}" for k in a0) + f"; {clocks()}")
@@ -141,13 +163,21 @@ def main():
     ftrace = ops.trace_collect()
     ops.trace_enable(False)
     finished = ops.collision_groups(idx, ks, want_groups=False)
+    spill_lines = []
+    if a.spill:
+        ops.trace_enable(True)
+        sp, t_spill = timed(lambda: gen.spill_collisions(model, idx, 0, resid_prev[0], resid_last, ks))
+        strace = ops.trace_collect()
+        ops.trace_enable(False)
+        spill_lines = [spill_line("spill", sp, t_spill, strace, ops.collision_groups(idx, ks, want_groups=False)),
+                       f"  yardsticks of this run: conflict rounds {t_rounds * 1e3:.1f} ms, finish nearest_free {t_finish * 1e3:.2f} ms"]
     _, t_json = timed(lambda: gen.dump_index_json(idx, a.out))
     size = os.path.getsize(a.out)
     extend_lines = []
     for count in [int(c) for c in a.extend_new.split(",") if c]:
         x_new = torch.randn((count, a.in_dim), generator=g, device=dev)
-        extend_probe(model, x_new[:min(count, 4096)], a.out, a.items, timed)       # warm-up of the small-launch forms
-        extend_lines += extend_probe(model, x_new, a.out, a.items, timed)
+        extend_probe(model, x_new[:min(count, 4096)], a.out, a.items, timed, a.spill)       # warm-up of the small-launch forms
+        extend_lines += extend_probe(model, x_new, a.out, a.items, timed, a.spill)
         # the yardstick: what a user does today, the whole flow again over all N items (without the file's text)
         x_all = torch.cat([x, x_new])
         def full():
@@ -168,6 +198,8 @@ def main():
           f"largest {fin['largest_bucket']} items, moved {fin['moved']}, unresolved {fin['unresolved']}")
     print("  kernels: " + ", ".join(f"{k} {v[1]:.2f} ms/{v[0]}" for k, v in sorted(ftrace.items(), key=lambda kv: -kv[1][1])))
     print(f"  collision rate {final['collision_rate']:.6f} -> {finished['collision_rate']:.6f}")
+    for line in spill_lines:
+        print(line)
     print(f".index.json ({size / 1e6:.0f} MB)     {t_json * 1e3:9.1f} ms   {a.items / t_json / 1e6:7.2f} M items/s (D2H + text + write)")
     for line in extend_lines:
         print(line)

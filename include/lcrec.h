@@ -296,14 +296,19 @@ int lcrec_sinkhorn_assign(const float *resid, int64_t n, int e, const float *cod
  *   xq        device [n][e] or NULL: x_q sum, += x_res (starts from 0 unless xq_accumulate)
  *   resid_out device [n][e] or NULL: residual after the level (may alias resid_in)
  *   sse_out   device double[1] or NULL; workspace must then hold 8 KB
- *   ticket    NULL, or see "ticket arguments" (finishes sse_out inside the launch) */
+ *   ticket    NULL, or see "ticket arguments" (finishes sse_out inside the launch)
+ * A code outside [0, K): below 0 counts as 0, K and above as K - 1, decided on the int64 value (a batch-sized
+ * lcrec_sinkhorn_assign that gives up fills its column with -1).  lcrec_code_stats and lcrec_code_stats_levels take the
+ * same rule, so the statistics are those of the squared error this call computed. */
 int lcrec_rq_apply_level(const float *resid_in, int64_t n, int e, const float *codebook, int K,
                          const int64_t *idx, int64_t idx_stride, float *xq, int xq_accumulate,
                          float *resid_out, double *sse_out, void *workspace, size_t workspace_bytes,
                          unsigned int *ticket, void *stream);
 
 /* Per-code count and sum of the residuals assigned to it:
- *   count[k] = #{i : idx[i*idx_stride] == k},  sum[k][:] = sum_i resid[i][:]  (item order, fp32).
+ *   count[k] = #{i : code(i) == k},  sum[k][:] = sum_i resid[i][:]  (item order, fp32),
+ *   code(i) = idx[i*idx_stride] brought into [0, K-1] by the rule of lcrec_rq_apply_level: below 0 counts as 0, K and
+ *   above as K - 1, decided on the int64 value -- for every n, whichever kernel the size selects.
  * Replaces the scatter_add_/index_add_ block of index_improve/models/vq.py:151-167 and is the
  * segmented reduce behind the codebook gradient autograd derives from vq.py:90-92
  * (dL/dC[k] = w * (count[k]*C[k] - sum[k])).  Bit-identical to the CPU order. */
@@ -316,7 +321,7 @@ int lcrec_code_stats(const int64_t *idx, int64_t idx_stride, const float *resid,
  *   K        HOST [L];  count / sum: HOST arrays of L device pointers ([K[l]], [K[l]][e])
  *   codebooks / grad_out: both NULL, or HOST arrays of L device pointers: grad_out[l] =
  *            (scale * (count*C_l - sum)) * weight, see lcrec_codebook_grad
- * Same bits as the per-level calls. */
+ * Same bits as the per-level calls, codes outside [0, K[l]) included (the rule of lcrec_rq_apply_level). */
 int lcrec_code_stats_levels(const int64_t *idx, const float *const *resid, int64_t n, int e, const int *K, int L,
                             float *const *count, float *const *sum, const float *const *codebooks, float *const *grad_out,
                             float scale, float weight, void *stream);
@@ -784,6 +789,46 @@ typedef struct {
     int xcd_order;            /* workgroup b takes strip (b % 8) * (grid / 8) + b / 8, not strip b (grid a multiple of 8) */
 } lcrec_bn_plan;
 int lcrec_debug_bn_plan(int call, int64_t n, int features, int aligned, lcrec_bn_plan *out);
+
+/* The reduction and gradient tail of a training step: the launch each call below picks for its size and alignment;
+ * lcrec_debug_step_tail_plan reports it, and the launchers launch by the same function.  Host only: nothing is launched.
+ *   call        LCREC_TAIL_*
+ *   n_or_count  rows n (relu_bias_backward, quantizer_input_grad_bias, rq_apply_level, code_stats*), or elements `count`
+ *               (recon_loss_grad, grad_norm_clip); >= 1
+ *   width       features (relu_bias_backward), e (quantizer_input_grad_bias, rq_apply_level, code_stats*); unused for the two
+ *               flat reductions
+ *   aligned     whether every array of the call sits on 16 bytes (read by the two flat reductions only)
+ *   out->K      IN, the two code_stats calls only: the codebook size (code_stats_levels: the largest of the levels') */
+enum { LCREC_TAIL_RELU_BIAS_BACKWARD = 0, LCREC_TAIL_RECON_LOSS_GRAD, LCREC_TAIL_GRAD_NORM_CLIP, LCREC_TAIL_QUANTIZER_INPUT_GRAD_BIAS,
+       LCREC_TAIL_RQ_APPLY_LEVEL, LCREC_TAIL_CODE_STATS, LCREC_TAIL_CODE_STATS_LEVELS };
+enum {
+    LCREC_TAILK_STRIP = 0,          /* relu_bias_backward_kernel<cols>: one 1024-thread workgroup per strip of columns */
+    LCREC_TAILK_REDUCE,             /* recon_loss_grad_kernel / sumsq_kernel: fp64 partial per 1024-thread workgroup */
+    LCREC_TAILK_QGB_ONE,            /* quantizer_input_grad_bias_kernel: one workgroup (e 16 / 32 / 64, n * e <= 65536) */
+    LCREC_TAILK_QG_TWO,             /* quantizer_input_grad_kernel, then the strip kernel over its output */
+    LCREC_TAILK_APPLY_LEVEL,        /* apply_level_kernel */
+    LCREC_TAILK_CS_SORTED,          /* code_stats_sorted_kernel: counting sort in LDS (n <= 8192, K <= 1024) */
+    LCREC_TAILK_CS_STREAMING,       /* code_stats_kernel: every thread scans all items */
+    LCREC_TAILK_CS_LEVELS,          /* code_stats_levels_kernel: the sorted form of all levels in one launch, gridDim.y = L */
+    LCREC_TAILK_CS_PER_LEVEL        /* code_stats_levels falls back to lcrec_code_stats (+ lcrec_codebook_grad) level by level */
+};
+typedef struct {
+    int K;                    /* IN (see above); 0 otherwise */
+    int family;               /* LCREC_TAILK_* */
+    int grid;                 /* workgroups of the (first) launch; gridDim.x.  CS_PER_LEVEL: 0, see LCREC_TAIL_CODE_STATS */
+    int grid_sse;             /* rq_apply_level given sse_out: the partial sums' grouping follows the grid, at most 256; else 0 */
+    int cols;                 /* STRIP: strip width in columns (8, 16 or 32); else 0 */
+    int xcd_order;            /* STRIP: workgroup b takes strip (b % 8) * (grid / 8) + b / 8 (grid a multiple of 8) */
+    int vec16;                /* REDUCE: the 16-byte loop runs (aligned); APPLY_LEVEL and the CS forms: always 16-byte rows */
+    int second_launch;        /* a launch follows the first: REDUCE and APPLY_LEVEL's sse when the call is given no ticket (the
+                               * finishing kernel); QG_TWO and CS_PER_LEVEL always */
+    int64_t tail;             /* elements outside the main loop.  REDUCE: read by scalars, count % 4 with vec16, else all `count`;
+                               * STRIP: rows past the last whole block of 8 x (1024 / cols) rows, taken one row per lane and
+                               * trip (a row group whose eighth row is still below n takes them in one more unrolled trip);
+                               * QGB_ONE: rows past the last whole block of 4 x (1024 / e) rows, whose missing rows are clamped
+                               * loads; else 0 */
+} lcrec_step_tail_plan;
+int lcrec_debug_step_tail_plan(int call, int64_t n_or_count, int width, int aligned, lcrec_step_tail_plan *out);
 
 #ifdef __cplusplus
 }

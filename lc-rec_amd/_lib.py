@@ -132,6 +132,7 @@ _SIGNATURES = {
                                              ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_float,
                                              _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "lcrec_debug_bn_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
+    "lcrec_debug_step_tail_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
 }
 
 
@@ -167,6 +168,12 @@ class BnPlan(ctypes.Structure):
     """lcrec_bn_plan of include/lcrec.h"""
     _fields_ = [("float4", ctypes.c_int), ("cols", ctypes.c_int), ("rows_per_lane", ctypes.c_int), ("cached", ctypes.c_int), ("grid", ctypes.c_int),
                 ("xcd_order", ctypes.c_int)]
+
+
+class StepTailPlan(ctypes.Structure):
+    """lcrec_step_tail_plan of include/lcrec.h"""
+    _fields_ = [("K", ctypes.c_int), ("family", ctypes.c_int), ("grid", ctypes.c_int), ("grid_sse", ctypes.c_int), ("cols", ctypes.c_int),
+                ("xcd_order", ctypes.c_int), ("vec16", ctypes.c_int), ("second_launch", ctypes.c_int), ("tail", ctypes.c_int64)]
 
 
 class TraceEntry(ctypes.Structure):

@@ -531,6 +531,11 @@ LCREC_API int lcrec_debug_bn_plan(int call, int64_t n, int features, int aligned
     return debug_bn_plan(call, n, features, aligned, out);
 }
 
+LCREC_API int lcrec_debug_step_tail_plan(int call, int64_t n_or_count, int width, int aligned, lcrec_step_tail_plan *out)
+{
+    return debug_step_tail_plan(call, n_or_count, width, aligned, out);
+}
+
 LCREC_API int lcrec_bn_relu_apply(const float *t, int64_t n, int features, const float *gamma, const float *beta, const float *mean,
                                   const float *rstd, int relu, float *y, void *stream)
 {

@@ -249,6 +249,10 @@ int bn_relu_backward(const float *gy, const float *t, const float *y, int64_t n,
                      const float *fold_shift, hipStream_t stream);
 int bn_stats(const float *t, int64_t n, int F, float *mean_out, float *m2_out, hipStream_t stream);
 int debug_bn_plan(int call, int64_t n, int F, int aligned, lcrec_bn_plan *out);
+// the plan of a step-tail launch (include/lcrec.h, lcrec_debug_step_tail_plan): the launchers launch by these two and the debug
+// entry reports them.  vq_tail_plan (vq_train.hip): rq_apply_level and the two code_stats calls; returns false for an e the call refuses
+int debug_step_tail_plan(int call, int64_t n, int width, int aligned, lcrec_step_tail_plan *out);
+bool vq_tail_plan(int call, int64_t n, int e, int K, lcrec_step_tail_plan *out);
 int bn_merge_stats(const float *rows, int world, int F, float eps, float momentum, float *mean_out, float *rstd_out,
                    float *running_mean, float *running_var, hipStream_t stream);
 int bn_relu_apply(const float *t, int64_t n, int F, const float *gamma, const float *beta, const float *mean, const float *rstd,

@@ -671,7 +671,7 @@ __device__ __forceinline__ bool publish_and_check_last(double *partial, double s
 __global__ __launch_bounds__(RED_THREADS) void recon_loss_grad_kernel(const float *__restrict__ out, const float *__restrict__ x,
                                                                        int64_t count, int64_t count_total, int l1,
                                                                        float *__restrict__ g, double *partial, unsigned *ticket,
-                                                                       float *loss)
+                                                                       float *loss, int vec)
 {
     __shared__ double sm[RED_THREADS / 64];
     __shared__ int last_sh;
@@ -684,8 +684,8 @@ __global__ __launch_bounds__(RED_THREADS) void recon_loss_grad_kernel(const floa
         return d * scale;
     };
     // 16-byte accesses when the three arrays allow it (a lane's four elements in index order, so the workgroup's sum takes the
-    // elements in a fixed order either way); the ragged end and unaligned callers by scalars
-    const bool vec = (((uintptr_t)out | (uintptr_t)x | (uintptr_t)g) & 15) == 0;
+    // elements in a fixed order either way); the ragged end and unaligned callers by scalars.  vec: the launcher's
+    // aligned16({out, x, g}), the bit its plan reports
     const int64_t quads = vec ? count / 4 : 0;
     for (int64_t q = (int64_t)blockIdx.x * RED_THREADS + threadIdx.x; q < quads; q += (int64_t)gridDim.x * RED_THREADS) {
         const float4 o = reinterpret_cast<const float4 *>(out)[q], t = reinterpret_cast<const float4 *>(x)[q];
@@ -725,12 +725,12 @@ __device__ __forceinline__ void norm_and_coef(double sumsq, float max_norm, floa
 
 // 16-byte loads (the flat gradient buffer is 256-byte aligned; a ragged tail is read by scalars): 35 MB at 768-d in ~7 us
 __global__ __launch_bounds__(RED_THREADS) void sumsq_kernel(const float *__restrict__ g, int64_t count, double *partial, unsigned *ticket,
-                                                             float max_norm, float *norm_out)
+                                                             float max_norm, float *norm_out, int vec)
 {
     __shared__ double sm[RED_THREADS / 64];
     __shared__ int last_sh;
     double acc = 0.0;
-    const int64_t count4 = ((reinterpret_cast<uintptr_t>(g) & 15) == 0) ? count / 4 : 0;
+    const int64_t count4 = vec ? count / 4 : 0;                  // vec: g on 16 bytes (the launcher's plan)
     const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
     for (int64_t i = (int64_t)blockIdx.x * RED_THREADS + threadIdx.x; i < count4; i += (int64_t)gridDim.x * RED_THREADS) {
         const f32x4 v = g4[i];
@@ -1263,6 +1263,70 @@ static void launch_bn_backward(const lcrec_bn_plan &p, hipStream_t stream, const
         });
 }
 
+static int red_blocks(int64_t count, int per_thread = 16)
+{
+    int64_t b = (count + (int64_t)RED_THREADS * per_thread - 1) / ((int64_t)RED_THREADS * per_thread);
+    return (int)(b < 1 ? 1 : (b > RED_MAX_BLOCKS ? RED_MAX_BLOCKS : b));
+}
+
+// workgroups of quantizer_input_grad_kernel (four elements per thread, at most 2048)
+static int qg_grid(int64_t n, int e)
+{
+    const int64_t blocks = (n * e + 256 * 4 - 1) / (256 * 4);
+    return (int)(blocks > 2048 ? 2048 : blocks);
+}
+
+// ---- the plan of a step-tail launch of this file (include/lcrec.h, lcrec_step_tail_plan): relu_bias_backward, the two flat
+// reductions and quantizer_input_grad_bias launch by it and lcrec_debug_step_tail_plan() reports it; neither restates the other.
+// (rq_apply_level and the code_stats calls: vq_tail_plan, vq_train.hip.)
+static lcrec_step_tail_plan step_tail_plan(int call, int64_t n, int width, bool aligned)
+{
+    lcrec_step_tail_plan p = {};
+    if (call == LCREC_TAIL_RELU_BIAS_BACKWARD) {
+        p.family = LCREC_TAILK_STRIP;
+        p.cols = strip_cols(width);
+        p.grid = (width + p.cols - 1) / p.cols;
+        p.xcd_order = p.cols < 32 && (p.grid & 7) == 0;          // strip_of_block()
+        p.tail = n % ((int64_t)CR_UNROLL * (CR_THREADS / p.cols));
+    } else if (call == LCREC_TAIL_RECON_LOSS_GRAD || call == LCREC_TAIL_GRAD_NORM_CLIP) {
+        p.family = LCREC_TAILK_REDUCE;
+        // the loss: one 16-byte access per lane and array: a batch's 786 k elements on 192 CUs, not 48
+        p.grid = red_blocks(n, call == LCREC_TAIL_RECON_LOSS_GRAD ? 4 : 16);
+        p.vec16 = aligned;
+        p.tail = aligned ? n % 4 : n;
+        p.second_launch = 1;
+    } else {
+        if ((width == 16 || width == 32 || width == 64) && n * width <= 65536) {
+            p.family = LCREC_TAILK_QGB_ONE;
+            p.grid = 1;
+            p.tail = n % (4 * (QGB_THREADS / width));
+        } else {                                                  // other shapes: the two launches this call stands for
+            p.family = LCREC_TAILK_QG_TWO;
+            p.grid = qg_grid(n, width);
+            p.second_launch = 1;
+        }
+    }
+    return p;
+}
+
+int debug_step_tail_plan(int call, int64_t n, int width, int aligned, lcrec_step_tail_plan *out)
+{
+    if (!out) return fail(LCREC_EINVAL, "debug_step_tail_plan: NULL pointer");
+    if (call < LCREC_TAIL_RELU_BIAS_BACKWARD || call > LCREC_TAIL_CODE_STATS_LEVELS) return fail(LCREC_EINVAL, "debug_step_tail_plan: no such call (%d)", call);
+    if (n < 1) return fail(LCREC_EINVAL, "debug_step_tail_plan: n_or_count=%lld", (long long)n);
+    const bool flat = call == LCREC_TAIL_RECON_LOSS_GRAD || call == LCREC_TAIL_GRAD_NORM_CLIP;
+    if (!flat && width < 1) return fail(LCREC_EINVAL, "debug_step_tail_plan: width=%d", width);
+    if (call == LCREC_TAIL_RELU_BIAS_BACKWARD && n > (1 << 20)) return fail(LCREC_EUNSUPPORTED, "debug_step_tail_plan: relu_bias_backward is sized for training batches (n=%lld)", (long long)n);
+    if (call >= LCREC_TAIL_RQ_APPLY_LEVEL) {
+        const int K = out->K;
+        if (call == LCREC_TAIL_RQ_APPLY_LEVEL ? (width % 4 != 0) : K < 1) return fail(LCREC_EINVAL, "debug_step_tail_plan: bad e=%d or out->K=%d", width, K);
+        if (!vq_tail_plan(call, n, width, K, out)) return fail(LCREC_EUNSUPPORTED, "debug_step_tail_plan: code_stats: e_dim=%d (supported: 16, 32, 64)", width);
+        return LCREC_OK;
+    }
+    *out = step_tail_plan(call, n, width, aligned != 0);
+    return LCREC_OK;
+}
+
 int debug_bn_plan(int call, int64_t n, int F, int aligned, lcrec_bn_plan *out)
 {
     if (!out) return fail(LCREC_EINVAL, "debug_bn_plan: NULL pointer");
@@ -1363,18 +1427,12 @@ int relu_bias_backward(const float *gy, const float *y, int64_t n, int F, int re
     if (!gy || (relu && !y)) return fail(LCREC_EINVAL, "relu_bias_backward: NULL pointer");
     if (n > (1 << 20) || F < 1) return fail(LCREC_EUNSUPPORTED, "relu_bias_backward: sized for training batches (n=%lld)", (long long)n);
     TraceScope trace(K_RELU_BIAS_BWD, stream);
-    const int cols = strip_cols(F);
-    with_strip(cols, [&](auto c) {
-        hipLaunchKernelGGL(relu_bias_backward_kernel<decltype(c)::value>, dim3((unsigned)((F + cols - 1) / cols)), dim3(CR_THREADS), 0, stream, gy, y,
+    const lcrec_step_tail_plan p = step_tail_plan(LCREC_TAIL_RELU_BIAS_BACKWARD, n, F, true);
+    with_strip(p.cols, [&](auto c) {
+        hipLaunchKernelGGL(relu_bias_backward_kernel<decltype(c)::value>, dim3((unsigned)p.grid), dim3(CR_THREADS), 0, stream, gy, y,
                            n, F, relu, g_out, dbias);
     });
     return check_launch("relu_bias_backward_kernel");
-}
-
-static int red_blocks(int64_t count, int per_thread = 16)
-{
-    int64_t b = (count + (int64_t)RED_THREADS * per_thread - 1) / ((int64_t)RED_THREADS * per_thread);
-    return (int)(b < 1 ? 1 : (b > RED_MAX_BLOCKS ? RED_MAX_BLOCKS : b));
 }
 
 size_t train_reduce_workspace() { return RED_MAX_BLOCKS * sizeof(double); }
@@ -1387,10 +1445,11 @@ int recon_loss_grad(const float *out, const float *x, int64_t count, int64_t cou
     if (!out || !x || !loss) return fail(LCREC_EINVAL, "recon_loss_grad: NULL pointer");
     if (count < 1) return fail(LCREC_EINVAL, "recon_loss_grad: empty input");
     if (!workspace || workspace_bytes < train_reduce_workspace()) return fail(LCREC_EWORKSPACE, "recon_loss_grad: workspace too small");
-    const int blocks = red_blocks(count, 4);          // one 16-byte access per lane and array: a batch's 786 k elements on 192 CUs, not 48
+    const lcrec_step_tail_plan p = step_tail_plan(LCREC_TAIL_RECON_LOSS_GRAD, count, 0, aligned16({out, x, g}));
+    const int blocks = p.grid;
     TraceScope trace(K_LOSS, stream);
     hipLaunchKernelGGL(recon_loss_grad_kernel, dim3(blocks), dim3(RED_THREADS), 0, stream, out, x, count, count_total, l1, g, (double *)workspace,
-                       ticket, loss);
+                       ticket, loss, p.vec16);
     if (!ticket)
         hipLaunchKernelGGL(recon_loss_finish_kernel, dim3(1), dim3(RED_THREADS), 0, stream, (const double *)workspace, blocks, count_total, loss);
     return check_launch("recon_loss_grad_kernel");
@@ -1402,9 +1461,11 @@ int grad_norm_clip(const float *g, int64_t count, float max_norm, float *norm_ou
     if (!g || !norm_out) return fail(LCREC_EINVAL, "grad_norm_clip: NULL pointer");
     if (count < 1) return fail(LCREC_EINVAL, "grad_norm_clip: empty input");
     if (!workspace || workspace_bytes < train_reduce_workspace()) return fail(LCREC_EWORKSPACE, "grad_norm_clip: workspace too small");
-    const int blocks = red_blocks(count);
+    const lcrec_step_tail_plan p = step_tail_plan(LCREC_TAIL_GRAD_NORM_CLIP, count, 0, aligned16({g}));
+    const int blocks = p.grid;
     TraceScope trace(K_GRAD_NORM, stream);
-    hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(RED_THREADS), 0, stream, g, count, (double *)workspace, ticket, max_norm, norm_out);
+    hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(RED_THREADS), 0, stream, g, count, (double *)workspace, ticket, max_norm, norm_out,
+                       p.vec16);
     if (!ticket)
         hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(RED_THREADS), 0, stream, (const double *)workspace, blocks, max_norm, norm_out);
     return check_launch("grad_norm kernels");
@@ -1427,8 +1488,7 @@ int quantizer_input_grad(const float *z, const float *cb0, const int64_t *idx, i
     if (n == 0) return LCREC_OK;
     if (!z || !cb0 || !idx || !g_xq || !out) return fail(LCREC_EINVAL, "quantizer_input_grad: NULL pointer");
     if (n < 0 || e < 1) return fail(LCREC_EINVAL, "quantizer_input_grad: bad shape");
-    int64_t blocks = (n * e + 256 * 4 - 1) / (256 * 4);
-    if (blocks > 2048) blocks = 2048;
+    const int blocks = qg_grid(n, e);
     TraceScope trace(K_APPLY_LEVEL, stream);
     hipLaunchKernelGGL(quantizer_input_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, z, cb0, idx, idx_stride, n, e, coef, weight,
                        g_xq, out);
@@ -1442,7 +1502,7 @@ int quantizer_input_grad_bias(const float *z, const float *cb0, const int64_t *i
     if (n == 0) return LCREC_OK;
     if (!z || !cb0 || !idx || !g_xq || !out) return fail(LCREC_EINVAL, "quantizer_input_grad_bias: NULL pointer");
     if (n < 0 || e < 1) return fail(LCREC_EINVAL, "quantizer_input_grad_bias: bad shape");
-    if ((e == 16 || e == 32 || e == 64) && n * e <= 65536) {
+    if (step_tail_plan(LCREC_TAIL_QUANTIZER_INPUT_GRAD_BIAS, n, e, true).family == LCREC_TAILK_QGB_ONE) {
         TraceScope trace(K_APPLY_LEVEL, stream);
         hipLaunchKernelGGL(quantizer_input_grad_bias_kernel, dim3(1), dim3(QGB_THREADS), 0, stream, z, cb0, idx, idx_stride, (int)n, e, coef,
                            weight, g_xq, out, dbias);

@@ -543,6 +543,11 @@ __global__ __launch_bounds__(THREADS) void sk_small_kernel(const float *__restri
     }
 }
 
+// The one rule for a code outside [0, K) in the calls that take a given assignment (lcrec_rq_apply_level, lcrec_code_stats,
+// lcrec_code_stats_levels; include/lcrec.h): below 0 counts as 0, K and above as K - 1 -- decided on the int64 value, before
+// it is narrowed.  (A batch-sized Sinkhorn solve that gives up fills its column with -1.)
+__device__ __forceinline__ int clamp_code(int64_t j, int K) { return (int)(j < 0 ? 0 : (j >= K ? K - 1 : j)); }
+
 // ------------------------------------------------------------------------------------------
 // Apply a given assignment to one level (vq.py:87-95 + rq.py:47-48): gather, SSE, STE, residual.
 // One wave-quarter per item: thread handles 4 consecutive dims.
@@ -560,8 +565,7 @@ __global__ __launch_bounds__(256) void apply_level_kernel(const float *__restric
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
         const int64_t i = q / per;
         const int k4 = (int)(q % per) * 4;
-        int64_t j = idx[i * idx_stride];
-        j = j < 0 ? 0 : (j >= K ? K - 1 : j);
+        const int64_t j = clamp_code(idx[i * idx_stride], K);
         const f32x4 c = *reinterpret_cast<const f32x4 *>(cb + j * e + k4);
         const f32x4 r = *reinterpret_cast<const f32x4 *>(r_in + i * e + k4);
         f32x4 xo = {0.f, 0.f, 0.f, 0.f}, ro;
@@ -636,7 +640,7 @@ __global__ __launch_bounds__(256) void code_stats_kernel(const int64_t *__restri
     for (int64_t i0 = 0; i0 < n; i0 += CS_CHUNK) {
         const int m = (int)((n - i0 < CS_CHUNK) ? n - i0 : CS_CHUNK);
         __syncthreads();
-        for (int q = tid; q < m; q += 256) sidx[q] = (int)idx[(i0 + q) * idx_stride];
+        for (int q = tid; q < m; q += 256) sidx[q] = clamp_code(idx[(i0 + q) * idx_stride], K);
         for (int q = tid; q < m * E; q += 256) sres[q / E][q % E] = resid[i0 * E + q];
         __syncthreads();
         for (int t = 0; t < m; ++t) {
@@ -1828,9 +1832,9 @@ int apply_level(const float *r_in, int64_t n, int e, const float *cb, int K, con
     if (!r_in || !cb || !idx) return fail(LCREC_EINVAL, "rq_apply_level: NULL pointer");
     if (e % 4 || e <= 0 || K < 1 || n < 0) return fail(LCREC_EINVAL, "rq_apply_level: bad shape");
     if (n == 0) return LCREC_OK;
-    int64_t blocks = (n * (e / 4) + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    if (sse_out && blocks > TICKET_MAX_WORKGROUPS) blocks = TICKET_MAX_WORKGROUPS;   // (both forms: the sum's grouping follows the grid)
+    lcrec_step_tail_plan plan;
+    vq_tail_plan(LCREC_TAIL_RQ_APPLY_LEVEL, n, e, K, &plan);
+    const int blocks = sse_out ? plan.grid_sse : plan.grid;
     double *partial = nullptr;
     if (sse_out) {
         if (!workspace || workspace_bytes < 1024 * sizeof(double))
@@ -1840,7 +1844,7 @@ int apply_level(const float *r_in, int64_t n, int e, const float *cb, int K, con
     TraceScope trace(K_APPLY_LEVEL, stream);
     hipLaunchKernelGGL(apply_level_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, r_in, n, e, cb, K, idx, idx_stride, xq,
                        xq_accumulate, r_out, partial, sse_out ? ticket : nullptr, sse_out);
-    if (sse_out && !ticket) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, stream, partial, (int)blocks, sse_out);
+    if (sse_out && !ticket) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, stream, partial, blocks, sse_out);
     return check_launch("apply_level_kernel");
 }
 
@@ -1874,13 +1878,13 @@ __device__ __forceinline__ void code_stats_sorted_body(const int64_t *__restrict
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int i = i0 + u * CSS_THREADS + tid;
-            kk[u] = i < n ? (int)idx[(int64_t)i * idx_stride] : 0;
+            kk[u] = i < n ? clamp_code(idx[(int64_t)i * idx_stride], K) : 0;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int i = i0 + u * CSS_THREADS + tid;
             if (i < n) {
-                const int k = kk[u] < 0 ? 0 : (kk[u] >= K ? K - 1 : kk[u]);
+                const int k = kk[u];
                 skey[i] = (unsigned short)k;
                 atomicAdd(&cursor[k], 1);    // integer histogram: the totals do not depend on arrival order
             }
@@ -1989,22 +1993,62 @@ __global__ __launch_bounds__(CSS_THREADS) void code_stats_levels_kernel(CsLevels
                               g.weight);
 }
 
+// The launch of rq_apply_level and of the two code_stats calls for a size (include/lcrec.h, lcrec_step_tail_plan): the three
+// launchers launch by it, lcrec_debug_step_tail_plan reports it.  false: an e the code_stats kernels have no instantiation for.
+bool vq_tail_plan(int call, int64_t n, int e, int K, lcrec_step_tail_plan *out)
+{
+    lcrec_step_tail_plan p = {};
+    p.K = K;
+    p.vec16 = 1;
+    const bool e_ok = e == 16 || e == 32 || e == 64;
+    if (call == LCREC_TAIL_RQ_APPLY_LEVEL) {
+        p.K = 0;
+        p.family = LCREC_TAILK_APPLY_LEVEL;
+        int64_t blocks = (n * (e / 4) + 255) / 256;
+        if (blocks > 1024) blocks = 1024;
+        p.grid = (int)blocks;
+        p.grid_sse = (int)(blocks > TICKET_MAX_WORKGROUPS ? TICKET_MAX_WORKGROUPS : blocks);   // (with and without a ticket: the sum's grouping follows the grid)
+        p.second_launch = 1;
+    } else if (call == LCREC_TAIL_CODE_STATS) {
+        if (n > 0 && n <= CSS_MAX_N && K <= CSS_MAX_K && e_ok) {
+            p.family = LCREC_TAILK_CS_SORTED;
+            p.grid = (K * e + CSS_THREADS - 1) / CSS_THREADS;
+        } else {
+            if (!e_ok) return false;
+            p.family = LCREC_TAILK_CS_STREAMING;
+            p.grid = (K + 256 / e - 1) / (256 / e);
+        }
+    } else {
+        if (n <= CSS_MAX_N && K <= CSS_MAX_K && e_ok) {
+            p.family = LCREC_TAILK_CS_LEVELS;
+            p.grid = (K * e + CSS_THREADS - 1) / CSS_THREADS;
+        } else {
+            p.family = LCREC_TAILK_CS_PER_LEVEL;            // sizes beyond the one-workgroup sort
+            p.second_launch = 1;
+        }
+    }
+    *out = p;
+    return true;
+}
+
 int code_stats(const int64_t *idx, int64_t idx_stride, const float *resid, int64_t n, int e, int K, float *count,
                float *sum, hipStream_t stream)
 {
     if ((n > 0 && (!idx || !resid)) || !count || !sum) return fail(LCREC_EINVAL, "code_stats: NULL pointer");
     if (n < 0 || K < 1) return fail(LCREC_EINVAL, "code_stats: bad shape");
     TraceScope trace(K_CODE_STATS, stream);
-    if (n > 0 && n <= CSS_MAX_N && K <= CSS_MAX_K && (e == 16 || e == 32 || e == 64)) {
-        if (e == 16) hipLaunchKernelGGL(code_stats_sorted_kernel<16>, dim3((unsigned)((K * e + CSS_THREADS - 1) / CSS_THREADS)), dim3(CSS_THREADS), 0, stream, idx, idx_stride, resid, (int)n, K, count, sum);
-        else if (e == 32) hipLaunchKernelGGL(code_stats_sorted_kernel<32>, dim3((unsigned)((K * e + CSS_THREADS - 1) / CSS_THREADS)), dim3(CSS_THREADS), 0, stream, idx, idx_stride, resid, (int)n, K, count, sum);
-        else hipLaunchKernelGGL(code_stats_sorted_kernel<64>, dim3((unsigned)((K * e + CSS_THREADS - 1) / CSS_THREADS)), dim3(CSS_THREADS), 0, stream, idx, idx_stride, resid, (int)n, K, count, sum);
+    lcrec_step_tail_plan plan;
+    if (!vq_tail_plan(LCREC_TAIL_CODE_STATS, n, e, K, &plan)) return fail(LCREC_EUNSUPPORTED, "code_stats: e_dim=%d (supported: 16, 32, 64)", e);
+    const dim3 grid((unsigned)plan.grid);
+    if (plan.family == LCREC_TAILK_CS_SORTED) {
+        if (e == 16) hipLaunchKernelGGL(code_stats_sorted_kernel<16>, grid, dim3(CSS_THREADS), 0, stream, idx, idx_stride, resid, (int)n, K, count, sum);
+        else if (e == 32) hipLaunchKernelGGL(code_stats_sorted_kernel<32>, grid, dim3(CSS_THREADS), 0, stream, idx, idx_stride, resid, (int)n, K, count, sum);
+        else hipLaunchKernelGGL(code_stats_sorted_kernel<64>, grid, dim3(CSS_THREADS), 0, stream, idx, idx_stride, resid, (int)n, K, count, sum);
         return check_launch("code_stats_sorted_kernel");
     }
-    if (e == 16) hipLaunchKernelGGL(code_stats_kernel<16>, dim3((K + 15) / 16), dim3(256), 0, stream, idx, idx_stride, resid, n, K, count, sum);
-    else if (e == 32) hipLaunchKernelGGL(code_stats_kernel<32>, dim3((K + 7) / 8), dim3(256), 0, stream, idx, idx_stride, resid, n, K, count, sum);
-    else if (e == 64) hipLaunchKernelGGL(code_stats_kernel<64>, dim3((K + 3) / 4), dim3(256), 0, stream, idx, idx_stride, resid, n, K, count, sum);
-    else return fail(LCREC_EUNSUPPORTED, "code_stats: e_dim=%d (supported: 16, 32, 64)", e);
+    if (e == 16) hipLaunchKernelGGL(code_stats_kernel<16>, grid, dim3(256), 0, stream, idx, idx_stride, resid, n, K, count, sum);
+    else if (e == 32) hipLaunchKernelGGL(code_stats_kernel<32>, grid, dim3(256), 0, stream, idx, idx_stride, resid, n, K, count, sum);
+    else hipLaunchKernelGGL(code_stats_kernel<64>, grid, dim3(256), 0, stream, idx, idx_stride, resid, n, K, count, sum);
     return check_launch("code_stats_kernel");
 }
 
@@ -2015,14 +2059,14 @@ int code_stats_levels(const int64_t *idx, const float *const *resid, int64_t n, 
     if (L < 1 || L > LCREC_MAX_LEVELS || n < 1) return fail(LCREC_EINVAL, "code_stats_levels: bad L=%d or n=%lld", L, (long long)n);
     if ((cb == nullptr) != (grad == nullptr)) return fail(LCREC_EINVAL, "code_stats_levels: codebooks and grad_out go together");
     int kmax = 0;
-    bool fused = n <= CSS_MAX_N && (e == 16 || e == 32 || e == 64);
     for (int l = 0; l < L; ++l) {
         if (K[l] < 1 || !resid[l] || !count[l] || !sum[l] || (cb && (!cb[l] || !grad[l])))
             return fail(LCREC_EINVAL, "code_stats_levels: level %d: bad K or NULL pointer", l);
         kmax = K[l] > kmax ? K[l] : kmax;
-        fused = fused && K[l] <= CSS_MAX_K;
     }
-    if (!fused) {                                   // sizes beyond the one-workgroup sort: level by level
+    lcrec_step_tail_plan plan;
+    vq_tail_plan(LCREC_TAIL_CODE_STATS_LEVELS, n, e, kmax, &plan);       // (an e it does not take: level by level, where code_stats refuses it)
+    if (plan.family != LCREC_TAILK_CS_LEVELS) {                                   // sizes beyond the one-workgroup sort: level by level
         for (int l = 0; l < L; ++l) {
             int rc = code_stats(idx + l, L, resid[l], n, e, K[l], count[l], sum[l], stream);
             if (!rc && cb) rc = codebook_grad(count[l], sum[l], cb[l], K[l], e, scale, weight, grad[l], stream);
@@ -2037,7 +2081,7 @@ int code_stats_levels(const int64_t *idx, const float *const *resid, int64_t n, 
         g.cb[l] = cb ? cb[l] : nullptr; g.grad[l] = grad ? grad[l] : nullptr;
     }
     TraceScope trace(K_CODE_STATS, stream);
-    const dim3 grid((unsigned)((kmax * e + CSS_THREADS - 1) / CSS_THREADS), (unsigned)L);
+    const dim3 grid((unsigned)plan.grid, (unsigned)L);
     if (e == 16) hipLaunchKernelGGL(code_stats_levels_kernel<16>, grid, dim3(CSS_THREADS), 0, stream, g);
     else if (e == 32) hipLaunchKernelGGL(code_stats_levels_kernel<32>, grid, dim3(CSS_THREADS), 0, stream, g);
     else hipLaunchKernelGGL(code_stats_levels_kernel<64>, grid, dim3(CSS_THREADS), 0, stream, g);

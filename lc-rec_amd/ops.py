@@ -1004,6 +1004,24 @@ def bn_plan(call, n, F, aligned=True):
     return {name: int(getattr(plan, name)) for name, _ in _lib.BnPlan._fields_}
 
 
+TAIL_CALLS = ("relu_bias_backward", "recon_loss_grad", "grad_norm_clip", "quantizer_input_grad_bias", "rq_apply_level", "code_stats",
+              "code_stats_levels")                                   # LCREC_TAIL_* of include/lcrec.h, in order
+TAIL_FAMILIES = ("strip", "reduce", "qgb_one", "qg_two", "apply_level", "cs_sorted", "cs_streaming", "cs_levels", "cs_per_level")   # LCREC_TAILK_*
+
+
+def step_tail_plan(call, n_or_count, width=0, aligned=True, K=0):
+    """The launch the step-tail call `call` (one of TAIL_CALLS) picks for its size (include/lcrec.h, lcrec_debug_step_tail_plan),
+    as a dict of the fields of lcrec_step_tail_plan with `family` as its name in TAIL_FAMILIES.  K: the codebook size, for the two
+    code_stats calls.  Host only: no GPU is needed."""
+    plan = _lib.StepTailPlan()
+    plan.K = int(K)
+    rc = _lib.load().lcrec_debug_step_tail_plan(TAIL_CALLS.index(call), int(n_or_count), int(width), int(bool(aligned)), ctypes.addressof(plan))
+    _lib.check(rc, "lcrec_debug_step_tail_plan")
+    out = {name: int(getattr(plan, name)) for name, _ in _lib.StepTailPlan._fields_}
+    out["family"] = TAIL_FAMILIES[out["family"]]
+    return out
+
+
 def bn_merge_stats(rows, eps, momentum=0.0, running_mean=None, running_var=None):
     """(mean, rstd) of the union of the ranks' rows from rows [world, 2F+1] = (n_r, mean_r, m2_r); updates the running
     statistics in place when given (lcrec_bn_merge_stats)."""

@@ -830,6 +830,53 @@ typedef struct {
 } lcrec_step_tail_plan;
 int lcrec_debug_step_tail_plan(int call, int64_t n_or_count, int width, int aligned, lcrec_step_tail_plan *out);
 
+/* The launches of lcrec_linear_backward, lcrec_linear_backward_weights and lcrec_linear_bn_forward (csrc/gemm_f32.hip): each
+ * entry point decides its launches with one pure host function; the launch code launches by it and the debug exports below
+ * report it.  Host only: nothing is launched, no device is needed.  One lcrec_gemm_launch per kernel launch. */
+enum { LCREC_GEMMK_TILE_BODY = 0,   /* linear_tile_body: linear_fwd_kernel / linear_train_fwd_kernel / linear_dw_grouped_kernel */
+       LCREC_GEMMK_32x64,           /* linear_s16_kernel */
+       LCREC_GEMMK_REDUCER };       /* splitk_reduce_kernel / splitk_reduce_grouped_kernel */
+enum { LCREC_GEMMR_DX = 0, LCREC_GEMMR_DW, LCREC_GEMMR_REDUCE, LCREC_GEMMR_FORWARD };
+typedef struct {
+    const char *label;        /* the trace label the launch is counted under (a reducer runs inside its product's bracket) */
+    int role;                 /* LCREC_GEMMR_* */
+    int family;               /* LCREC_GEMMK_* */
+    int tile_rows, tile_cols; /* the workgroup tile (reducer: 0) */
+    int fast;                 /* buffer-load staging (K % 32 == 0 or k-major operands), not the guarded loads */
+    int a_kmajor, w_kmajor;   /* the TA / TB template switches */
+    int pro;                  /* 0; 1: scale / shift / clamp on the row-major A operand; 2: on the k-major W operand */
+    int stats;                /* batch statistics in the epilogue */
+    int register_buffered;    /* the tile body's DB form (ring of four register sets, k_tile_rb); the 32x64 kernel: always 1 */
+    int64_t m;                /* the product's output is [m][n], contracted over k */
+    int n, k;
+    int k_tiles;              /* ceil(k / 32) */
+    int runs;                 /* S: K-runs (gridDim.y); reducer: the partial products it adds */
+    int k_tiles_per_run;      /* K-tiles of every run but the last */
+    int k_tiles_last_run;
+    int last_k_valid;         /* valid k of the last K-tile (32: not ragged) */
+    int tiles, virtual_tiles; /* output tiles, and the numbering's extent (row panels padded to the 8 XCDs: the rest are holes) */
+    int workgroups;           /* grid size, all K-runs included (reducer: ceil(total4 / 256)) */
+    int wg_start;             /* grouped launches: the problem's first workgroup in the shared grid */
+    int last_panel_rows;      /* valid rows of the last row panel */
+    int last_tile_cols;       /* valid columns of the last column tile */
+    int vector_stores;        /* n % 4 == 0: 16-byte stores */
+    int chunk_row_tiles;      /* stats: row tiles per merge chunk (CH); else 0 */
+    int chunks;               /* stats: merge chunks, ceil(row tiles / CH); else 0 */
+    int64_t total4;           /* reducer: float4 sums */
+} lcrec_gemm_launch;
+/* out[0 .. capacity), capacity >= 3: the dX launch (want_gx), the dW launch and its reducer (want_gw, S > 1), in launch order.
+ * Returns the count or a negative code for a shape lcrec_linear_backward refuses. */
+int lcrec_debug_linear_backward_plan(int64_t n, int in_dim, int out_dim, int want_gx, int want_gw, lcrec_gemm_launch *out, int capacity);
+/* out[p] for problem p < count, every one a part of ONE launch of grid_out[0] workgroups, then one record per problem with
+ * S > 1, in problem order: its part of the grouped reducer's launch of grid_out[1] workgroups (0: not launched).  capacity >=
+ * 2 * count.  Of the problems only sizes, `splits` and whether x_scale / x_shift are given are read.  Returns the number of
+ * records or a negative code. */
+int lcrec_debug_linear_backward_weights_plan(const lcrec_dw_problem *problems, int count, lcrec_gemm_launch *out, int capacity,
+                                             int *grid_out);
+/* The one launch of lcrec_linear_bn_forward with an input fold (pro) and / or statistics (stats).  Returns 1, 0 when neither is
+ * asked for (the call is lcrec_linear_forward's then), or a negative code for a refused shape. */
+int lcrec_debug_linear_bn_forward_plan(int64_t n, int in_dim, int out_dim, int pro, int stats, lcrec_gemm_launch *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,10 @@ _SIGNATURES = {
                                              _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "lcrec_debug_bn_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
     "lcrec_debug_step_tail_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
+    "lcrec_debug_linear_backward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                                        ctypes.c_int]),
+    "lcrec_debug_linear_backward_weights_plan": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "lcrec_debug_linear_bn_forward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
 }
 
 
@@ -174,6 +178,18 @@ class StepTailPlan(ctypes.Structure):
     """lcrec_step_tail_plan of include/lcrec.h"""
     _fields_ = [("K", ctypes.c_int), ("family", ctypes.c_int), ("grid", ctypes.c_int), ("grid_sse", ctypes.c_int), ("cols", ctypes.c_int),
                 ("xcd_order", ctypes.c_int), ("vec16", ctypes.c_int), ("second_launch", ctypes.c_int), ("tail", ctypes.c_int64)]
+
+
+class GemmLaunch(ctypes.Structure):
+    """lcrec_gemm_launch of include/lcrec.h"""
+    _fields_ = [("label", ctypes.c_char_p), ("role", ctypes.c_int), ("family", ctypes.c_int), ("tile_rows", ctypes.c_int),
+                ("tile_cols", ctypes.c_int), ("fast", ctypes.c_int), ("a_kmajor", ctypes.c_int), ("w_kmajor", ctypes.c_int),
+                ("pro", ctypes.c_int), ("stats", ctypes.c_int), ("register_buffered", ctypes.c_int), ("m", ctypes.c_int64),
+                ("n", ctypes.c_int), ("k", ctypes.c_int), ("k_tiles", ctypes.c_int), ("runs", ctypes.c_int),
+                ("k_tiles_per_run", ctypes.c_int), ("k_tiles_last_run", ctypes.c_int), ("last_k_valid", ctypes.c_int),
+                ("tiles", ctypes.c_int), ("virtual_tiles", ctypes.c_int), ("workgroups", ctypes.c_int), ("wg_start", ctypes.c_int),
+                ("last_panel_rows", ctypes.c_int), ("last_tile_cols", ctypes.c_int), ("vector_stores", ctypes.c_int),
+                ("chunk_row_tiles", ctypes.c_int), ("chunks", ctypes.c_int), ("total4", ctypes.c_int64)]
 
 
 class TraceEntry(ctypes.Structure):

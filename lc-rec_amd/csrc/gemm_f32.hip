@@ -96,6 +96,12 @@ constexpr int LDK = 36;  // padded LDS row length in floats
 #define LCREC_GEMM_RING 4   // register sets of the 64 x 64 kernel's global prefetch ring (see linear_tile_body)
 #endif
 
+// Two facts about a tile shape that the launch plan (lcrec_debug_*_plan, below) reports from the functions the kernel is built
+// with: whether its FAST form runs the register-buffered K-tile (DB in linear_tile_body), and how many row tiles' statistics
+// records fit one chunk of the merge (CH there: three records of BN columns each, in the first K-tile buffer).
+constexpr bool tile_register_buffered(int waves_m, int tm, int tn) { return tm * tn == 1 || (tm * tn == 2 && waves_m == 2); }
+constexpr int stats_chunk_tiles(int bm, int bn) { return (bm + bn) * LDK / (3 * bn); }
+
 template <int ROWS>
 struct StageRegs {
     static constexpr int ITERS = (ROWS * 4 + 255) / 256;
@@ -267,7 +273,7 @@ __device__ __forceinline__ void linear_tile_body(
     // (k_tile_rb below).  History of this path at 1024 x 2048 -> 1024, us per launch: 62 (one buffer, loads behind a branch)
     // -> 49 (prefetch distance 2, second LDS buffer) -> 38.7 (this form; the MFMA pipe alone needs 27.3): what the in-kernel
     // stamps (tools/rb_stamp_probe.py) and leave-one-out builds showed on the way is noted at each piece.
-    constexpr bool DB = FAST && (TM * TN == 1 || (TM * TN == 2 && WAVES_M == 2));
+    constexpr bool DB = FAST && tile_register_buffered(WAVES_M, TM, TN);
     static_assert((PRO == 0 && !STATS) || DB, "the training-step extras live in the register-buffered K-tile");
     constexpr int BUF = (BM + BN) * LDK;
     __shared__ __attribute__((aligned(16))) float smem[BUF * (DB ? 2 : 1)];
@@ -766,7 +772,7 @@ __device__ __forceinline__ void linear_tile_body(
             // bits whichever tile comes last.  The acquire in ticket_is_last + the barrier above make plain loads of the records
             // valid; all 256 threads fetch a chunk of them into LDS side by side (one memory round trip, not one per tile), then
             // one thread per column walks the chunk in order.  Two passes (mean, then M2 about it), as lcrec_bn_merge_stats.
-            constexpr int CH = BUF / (3 * BN);            // row tiles per chunk (the first K-tile buffer: the staging patches are done)
+            constexpr int CH = stats_chunk_tiles(BM, BN);  // row tiles per chunk (the first K-tile buffer: the staging patches are done)
             float *rec_l = smem;
             const bool mine = tid < BN && n0 + tid < N;
             const int col = n0 + tid;
@@ -1700,6 +1706,13 @@ extern "C" struct lcrec_debug_forward_launch {
     // goes through the hand-over to the next tile's K loop instead of through finish())
     int steady_iterations, list_min, list_max, empty_workgroups, single_tile_workgroups, ragged_handed_over;
 };
+// The same record extended at its end (lcrec_debug_linear_forward_plan_ext).  The first export keeps writing records of the
+// first size: a caller built against it owns a buffer of those.
+extern "C" struct lcrec_debug_forward_launch_ext {
+    lcrec_debug_forward_launch base;
+    int fast;                  // buffer-load staging (the two ping-pong kernels and the 32 x 64 kernel have no other)
+    int register_buffered;     // generic kernel: the DB form of linear_tile_body (k_tile_rb); 32 x 64 kernel: 1; ping-pong: 0
+};
 namespace lcrec {
 
 // ---- Launch side: which kernel a shape gets.  Top to bottom: knobs, tile table, choosers, grid helper, launches, entry
@@ -1730,6 +1743,8 @@ template <int WAVES_M_, int WAVES_N_, int TM_, int TN_, KernelId LABEL_>        
 struct Tile {
     static constexpr int WAVES_M = WAVES_M_, WAVES_N = WAVES_N_, TM = TM_, TN = TN_, BM = WAVES_M_ * TM_ * 32, BN = WAVES_N_ * TN_ * 32;
     static constexpr KernelId LABEL = LABEL_;
+    static constexpr bool RB = tile_register_buffered(WAVES_M_, TM_, TN_);            // the register-buffered K-tile when FAST
+    static constexpr int STATS_CHUNK = stats_chunk_tiles(BM, BN);
 };
 // calls f with the row of `shape` as a constant: the one place a runtime shape becomes template arguments
 template <class F>
@@ -1828,15 +1843,96 @@ static int tile_grid(TileGrid &g, const char *who, int64_t M, int N, int bm, int
     return LCREC_OK;
 }
 
-// ---- launches
-static int launch_s16(const float *A, const float *W, const float *b, const float *sc, const float *sh, int relu, float *C, int64_t M,
-                      int N, int K, bool kmajor_w, hipStream_t stream)
+// ---- one launch of the generic kernels, the 32 x 64 kernel or a split-K reducer as a pure decision (no HIP call): which
+// instantiation, which grid, how K is cut.  The entry points below build these (backward_steps, dw_group_steps,
+// train_fwd_step), the launch_* functions launch what they say, and describe_step() turns them into the lcrec_gemm_launch
+// records of the debug exports; neither side restates the other.
+struct GemmStep {
+    int role, family;           // LCREC_GEMMR_* / LCREC_GEMMK_*
+    KernelId label;
+    TileShape shape;            // tile body only
+    bool fast, ta, tb;          // tb is also linear_s16_kernel's template switch
+    int pro;
+    bool stats;
+    int64_t M;                  // the output is [M][N], contracted over K
+    int N, K;
+    int splits;                 // K-runs, >= 1 (gridDim.y of a plain launch); reducer: the partial products it adds
+    int per;                    // the kernel's kt_per_split argument: K-tiles per run, 1 << 30 for one run
+    TileGrid g;                 // reducer: grid = workgroups, the blocks are 0
+    unsigned wg_start;          // grouped launches: first workgroup of the problem
+    int64_t total4;             // reducer: float4 sums
+};
+
+static int tile_step(GemmStep &s, const char *who, int role, TileShape shape, bool fast, bool ta, bool tb, int pro, bool stats, int64_t M,
+                     int N, int K, int splits)
 {
-    TileGrid g;
-    if (int rc = tile_grid(g, "linear (32 x 64 tiles)", M, N, S16_BM, S16_BN, false)) return rc;
-    TraceScope trace(K_LINEAR_32x64, stream);
-    const auto kernel = kmajor_w ? linear_s16_kernel<true> : linear_s16_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, stream, A, W, b, sc, sh, C, M, N, K, relu, g.bn_blocks);
+    s = GemmStep{};
+    s.role = role; s.family = LCREC_GEMMK_TILE_BODY; s.shape = shape;
+    s.label = with_tile(shape, [](auto tile) { return decltype(tile)::LABEL; });
+    s.fast = fast; s.ta = ta; s.tb = tb; s.pro = pro; s.stats = stats;
+    s.M = M; s.N = N; s.K = K;
+    const int nk = (K + BK - 1) / BK;
+    s.splits = splits > 1 ? splits : 1;
+    s.per = splits > 1 ? (nk + splits - 1) / splits : 1 << 30;
+    const TileDims d = tile_dims(shape);
+    return tile_grid(s.g, who, M, N, d.bm, d.bn, XCD_ORDER);
+}
+
+static int s16_step(GemmStep &s, int role, bool kmajor_w, int64_t M, int N, int K)
+{
+    s = GemmStep{};
+    s.role = role; s.family = LCREC_GEMMK_32x64; s.label = K_LINEAR_32x64; s.fast = true; s.tb = kmajor_w;
+    s.M = M; s.N = N; s.K = K; s.splits = 1; s.per = 1 << 30;
+    return tile_grid(s.g, "linear (32 x 64 tiles)", M, N, S16_BM, S16_BN, false);
+}
+
+// the ordered sum of `product`'s K-runs; it runs inside the product's trace bracket, hence under its label
+static void reduce_step(GemmStep &s, const GemmStep &product)
+{
+    s = GemmStep{};
+    s.role = LCREC_GEMMR_REDUCE; s.family = LCREC_GEMMK_REDUCER; s.label = product.label;
+    s.M = product.M; s.N = product.N; s.K = product.K; s.splits = product.splits;
+    s.total4 = product.M * (int64_t)product.N / 4;
+    s.g.grid = (unsigned)((s.total4 + 255) / 256);
+}
+
+static void describe_step(const GemmStep &s, lcrec_gemm_launch &o)
+{
+    memset(&o, 0, sizeof o);
+    o.label = kKernelNames[s.label];
+    o.role = s.role; o.family = s.family;
+    o.m = s.M; o.n = s.N; o.k = s.K;
+    o.runs = s.splits;
+    o.workgroups = (int)s.g.grid * (s.family == LCREC_GEMMK_REDUCER ? 1 : s.splits);
+    o.wg_start = (int)s.wg_start;
+    o.vector_stores = s.N % 4 == 0;
+    if (s.family == LCREC_GEMMK_REDUCER) { o.total4 = s.total4; return; }
+    const TileDims d = s.family == LCREC_GEMMK_32x64 ? TileDims{S16_BM, S16_BN} : tile_dims(s.shape);
+    o.tile_rows = d.bm; o.tile_cols = d.bn;
+    o.fast = s.fast; o.a_kmajor = s.ta; o.w_kmajor = s.tb; o.pro = s.pro; o.stats = s.stats;
+    o.register_buffered = s.family == LCREC_GEMMK_32x64 || (s.fast && with_tile(s.shape, [](auto tile) { return decltype(tile)::RB; }));
+    // the runs as the kernel cuts them: run r takes K-tiles [r * per, min((r + 1) * per, all))
+    o.k_tiles = (s.K + BK - 1) / BK;
+    o.k_tiles_per_run = s.per < o.k_tiles ? s.per : o.k_tiles;
+    o.k_tiles_last_run = o.k_tiles - (s.splits - 1) * o.k_tiles_per_run;
+    o.last_k_valid = s.K - (o.k_tiles - 1) * BK;
+    o.tiles = (int)(s.g.bm_blocks * s.g.bn_blocks);
+    o.virtual_tiles = (int)s.g.grid;
+    o.last_panel_rows = (int)(s.M - (s.g.bm_blocks - 1) * d.bm);
+    o.last_tile_cols = s.N - (s.g.bn_blocks - 1) * d.bn;
+    if (s.stats) {
+        o.chunk_row_tiles = with_tile(s.shape, [](auto tile) { return decltype(tile)::STATS_CHUNK; });
+        o.chunks = (int)((s.g.bm_blocks + o.chunk_row_tiles - 1) / o.chunk_row_tiles);
+    }
+}
+
+// ---- launches
+static int launch_s16(const GemmStep &s, const float *A, const float *W, const float *b, const float *sc, const float *sh, int relu,
+                      float *C, hipStream_t stream)
+{
+    TraceScope trace(s.label, stream);
+    const auto kernel = s.tb ? linear_s16_kernel<true> : linear_s16_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(s.g.grid), dim3(256), 0, stream, A, W, b, sc, sh, C, s.M, s.N, s.K, relu, s.g.bn_blocks);
     return check_launch("linear_s16_kernel");
 }
 
@@ -1897,6 +1993,12 @@ static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *
     return check_launch("linear_fwd_pp2_kernel");
 }
 
+// K % 32 == 0 (every layer of the run.sh architecture): the row-major instantiation whose staging path has no VALU
+static bool forward_fast(int in_dim, int tile_rows)
+{
+    return knobs().fast && in_dim % BK == 0 && (int64_t)in_dim * 4 * (tile_rows + 64) < (1ll << 31);
+}
+
 template <class T>
 static int launch_linear(T, const float *x, int64_t n, int in_dim, const float *W, const float *b, const float *sc, const float *sh,
                          int relu, int out_dim, float *y, hipStream_t stream)
@@ -1904,8 +2006,7 @@ static int launch_linear(T, const float *x, int64_t n, int in_dim, const float *
     TileGrid g;
     if (int rc = tile_grid(g, "linear_forward", n, out_dim, T::BM, T::BN, XCD_ORDER)) return rc;
     TraceScope trace(T::LABEL, stream);
-    // K % 32 == 0 (every layer of the run.sh architecture): the instantiation whose staging path has no VALU
-    const bool fast = knobs().fast && in_dim % BK == 0 && (int64_t)in_dim * 4 * (T::BM + 64) < (1ll << 31);
+    const bool fast = forward_fast(in_dim, T::BM);
     const auto kernel = fast ? linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true> : linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, false>;
     hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu, g.bn_blocks,
                        (int)g.bm_blocks, XCD_ORDER, 1 << 30, (int64_t)0);
@@ -1915,37 +2016,43 @@ static int launch_linear(T, const float *x, int64_t n, int in_dim, const float *
 // C[M][N] = A * B with A given [M][K] (TA false) or [K][M] (TA true) and B given [K][N] (always k-major here):
 // the two backward products of a Linear layer.  `splits` > 1 cuts K into that many runs of K-tiles whose partial
 // products go to `partial` [splits][M][N].
-template <bool TA, class T>
-static int launch_kmajor(T, const float *A, const float *B, int64_t M, int N, int K, float *C, int splits, float *partial,
+// `s` is a product step: its splits > 1 cut K into that many runs of K-tiles whose partial products go to `partial`
+// [splits][M][N]; `reduce` (then given) adds them into C in the same trace bracket.
+static int launch_kmajor(const GemmStep &s, const GemmStep *reduce, const float *A, const float *B, float *C, float *partial,
                          hipStream_t stream)
 {
-    TileGrid g;
-    if (int rc = tile_grid(g, "linear_backward", M, N, T::BM, T::BN, XCD_ORDER)) return rc;
-    const int nk = (K + BK - 1) / BK;
-    const int per = splits > 1 ? (nk + splits - 1) / splits : 1 << 30;
-    TraceScope trace(T::LABEL, stream);
-    hipLaunchKernelGGL((linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, TA, true>), dim3(g.grid, (unsigned)(splits > 1 ? splits : 1)),
-                       dim3(256), 0, stream, A, B, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
-                       splits > 1 ? partial : C, M, N, K, 0, g.bn_blocks, (int)g.bm_blocks, XCD_ORDER, per, splits > 1 ? M * (int64_t)N : (int64_t)0);
-    if (splits > 1) {
-        const int64_t total4 = M * (int64_t)N / 4;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, partial, splits, total4, C);
-    }
+    TraceScope trace(s.label, stream);
+    with_tile(s.shape, [&](auto tile) {
+        using T = decltype(tile);
+        const auto kernel = s.ta ? linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, true, true>
+                                 : linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, false, true>;
+        hipLaunchKernelGGL(kernel, dim3(s.g.grid, (unsigned)s.splits), dim3(256), 0, stream, A, B, (const float *)nullptr,
+                           (const float *)nullptr, (const float *)nullptr, s.splits > 1 ? partial : C, s.M, s.N, s.K, 0, s.g.bn_blocks,
+                           (int)s.g.bm_blocks, XCD_ORDER, s.per, s.splits > 1 ? s.M * (int64_t)s.N : (int64_t)0);
+        return 0;
+    });
+    if (reduce)
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(reduce->g.grid), dim3(256), 0, stream, partial, reduce->splits, reduce->total4, C);
     return check_launch("linear_fwd_kernel (k-major operands)");
 }
 
-template <class T>
-static int launch_train_fwd(T, const float *x, int64_t n, int in_dim, const float *W, const float *b, int out_dim, float *t,
-                            bool pro, bool stats, const TileExtras &ex, hipStream_t stream)
+static int launch_train_fwd(const GemmStep &s, const float *x, const float *W, const float *b, float *t, const TileExtras &ex,
+                            hipStream_t stream)
 {
-    TileGrid g;
-    if (int rc = tile_grid(g, "linear_bn_forward", n, out_dim, T::BM, T::BN, XCD_ORDER)) return rc;
-    TraceScope trace(T::LABEL, stream);
-    const auto kernel = pro && stats ? linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 1, true>
-                        : pro        ? linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 1, false>
-                                     : linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 0, true>;
-    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, stream, x, W, b, t, n, out_dim, in_dim, g.bn_blocks, (int)g.bm_blocks, XCD_ORDER, ex);
-    return check_launch("linear_train_fwd_kernel");
+    return with_tile(s.shape, [&](auto tile) -> int {
+        using T = decltype(tile);
+        if constexpr (!T::RB) {                   // never planned: no training kernel is built for these
+            return fail(LCREC_EUNSUPPORTED, "linear_bn_forward: no kernel for %d x %d tiles", T::BM, T::BN);
+        } else {
+            TraceScope trace(s.label, stream);
+            const auto kernel = s.pro && s.stats ? linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 1, true>
+                                : s.pro          ? linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 1, false>
+                                                 : linear_train_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, 0, true>;
+            hipLaunchKernelGGL(kernel, dim3(s.g.grid), dim3(256), 0, stream, x, W, b, t, s.M, s.N, s.K, s.g.bn_blocks, (int)s.g.bm_blocks,
+                               XCD_ORDER, ex);
+            return check_launch("linear_train_fwd_kernel");
+        }
+    });
 }
 
 // ---- entry points
@@ -2002,9 +2109,11 @@ int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const 
         int rc;
         if (s.kind == FWD_PP)
             rc = launch_linear_pp(xs, s.rows, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, ys, stream);
-        else if (s.kind == FWD_S16)
-            rc = launch_s16(xs, W, b, bn_scale, bn_shift, relu, ys, s.rows, out_dim, in_dim, false, stream);
-        else
+        else if (s.kind == FWD_S16) {
+            GemmStep step;
+            rc = s16_step(step, LCREC_GEMMR_FORWARD, false, s.rows, out_dim, in_dim);
+            if (!rc) rc = launch_s16(step, xs, W, b, bn_scale, bn_shift, relu, ys, stream);
+        } else
             rc = with_tile(s.shape, [&](auto tile) { return launch_linear(tile, xs, s.rows, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, ys, stream); });
         if (rc) return rc;
     }
@@ -2015,7 +2124,7 @@ int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const 
 // launched and no HIP call is made.  Rows, label and form come from forward_steps(), pp_form() and pp_workgroups(), the
 // functions the launch path runs.  The tile lists of a persistent launch are walked here as linear_fwd_pp3_kernel's
 // tile_of() / next_tile() walk them (device code: restated, with the same arguments the launch passes).
-static int linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcrec_debug_forward_launch *out, int capacity)
+static int linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcrec_debug_forward_launch_ext *out, int capacity)
 {
     if (n == 0) return 0;
     // (plain codes: a question about a launch does not touch the thread's last-error text)
@@ -2026,8 +2135,8 @@ static int linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcre
     const int count = forward_steps(n, in_dim, out_dim, steps);
     for (int i = 0; i < count; ++i) {
         const FwdStep &s = steps[i];
-        lcrec_debug_forward_launch &o = out[i];
-        memset(&o, 0, sizeof o);
+        memset(&out[i], 0, sizeof out[i]);
+        lcrec_debug_forward_launch &o = out[i].base;
         o.row0 = s.row0;
         o.rows = s.rows;
         const TileDims d = s.kind == FWD_PP ? TileDims{256, 128} : s.kind == FWD_S16 ? TileDims{S16_BM, S16_BN} : tile_dims(s.shape);
@@ -2044,6 +2153,8 @@ static int linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcre
         o.virtual_tiles = (int)g.grid;
         o.workgroups = (int)g.grid;
         o.last_panel_rows = (int)(s.rows - (g.bm_blocks - 1) * d.bm);
+        out[i].fast = s.kind != FWD_TILE || forward_fast(in_dim, d.bm);
+        out[i].register_buffered = s.kind == FWD_S16 || (s.kind == FWD_TILE && out[i].fast && with_tile(s.shape, [](auto tile) { return decltype(tile)::RB; }));
         if (s.kind != FWD_PP) continue;
         o.form = pp_form(in_dim, out_dim);
         o.workgroups = (int)pp_workgroups((PpForm)o.form, g.grid, cus);
@@ -2100,39 +2211,78 @@ size_t linear_backward_workspace(int64_t n, int in_dim, int out_dim)
     return s > 1 ? (size_t)s * out_dim * in_dim * sizeof(float) : 0;
 }
 
+// What lcrec_linear_backward launches for a shape (n > 0), as pure steps in launch order: the dX product (want_gx), the dW
+// product and the ordered sum of its K-runs (want_gw, S > 1).  Shapes the entry point refuses come back as its code, the
+// last-error text set.  linear_backward() launches exactly these; lcrec_debug_linear_backward_plan() reports them.
+constexpr int BWD_MAX_STEPS = 3;
+static int backward_steps(int64_t n, int in_dim, int out_dim, bool want_gx, bool want_gw, GemmStep *steps, int *count)
+{
+    *count = 0;
+    if (n < 0 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_backward: bad shape");
+    if (in_dim % 4 != 0 || out_dim % 4 != 0)
+        return fail(LCREC_EUNSUPPORTED, "linear_backward: in_dim=%d / out_dim=%d must be multiples of 4", in_dim, out_dim);
+    const int64_t widest = in_dim > out_dim ? in_dim : out_dim;
+    if ((n + 64) * widest * 4 >= (1ll << 31) || (int64_t)out_dim * in_dim * 4 >= (1ll << 31))
+        return fail(LCREC_EUNSUPPORTED, "linear_backward: operands of %lld x %lld floats exceed the 2 GiB a buffer descriptor spans "
+                                        "(a training batch is expected here)", (long long)n, (long long)widest);
+    if (want_gx) {
+        // dX [n][in] = dY [n][out] * W [out][in]: A row-major (K = out), B = W as it is stored
+        if (out_dim % BK != 0) return fail(LCREC_EUNSUPPORTED, "linear_backward: out_dim=%d is not a multiple of 32", out_dim);
+        GemmStep &s = steps[(*count)++];
+        int rc = use_s16_tiles(n, in_dim, out_dim)             // an under-filled launch: the 32 x 64 tiles
+                     ? s16_step(s, LCREC_GEMMR_DX, true, n, in_dim, out_dim)
+                     : tile_step(s, "linear_backward", LCREC_GEMMR_DX, forward_tile_shape(n, in_dim), true, false, true, 0, false, n, in_dim, out_dim, 1);
+        if (rc) return rc;
+    }
+    if (want_gw) {
+        // dW [out][in] = dY^T * X: A = dY [n][out] and B = X [n][in], both as they are stored (K = n, any length)
+        GemmStep &s = steps[(*count)++];
+        if (int rc = tile_step(s, "linear_backward", LCREC_GEMMR_DW, forward_tile_shape(out_dim, in_dim), true, true, true, 0, false, out_dim,
+                               in_dim, (int)n, linear_backward_splits(n, in_dim, out_dim)))
+            return rc;
+        if (s.splits > 1) {
+            reduce_step(steps[*count], s);
+            ++*count;
+        }
+    }
+    return LCREC_OK;
+}
+
 int linear_backward(const float *gy, const float *x, const float *W, int64_t n, int in_dim, int out_dim, float *gx, float *gw,
                     void *workspace, size_t workspace_bytes, hipStream_t stream)
 {
     if (n == 0) return LCREC_OK;
     if (!gy || (gx && !W) || (gw && !x)) return fail(LCREC_EINVAL, "linear_backward: NULL pointer");
-    if (n < 0 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_backward: bad shape");
-    if (in_dim % 4 != 0 || out_dim % 4 != 0)
-        return fail(LCREC_EUNSUPPORTED, "linear_backward: in_dim=%d / out_dim=%d must be multiples of 4", in_dim, out_dim);
     if (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)W) & 15) return fail(LCREC_EINVAL, "linear_backward: operands must be 16-byte aligned");
-    const int64_t widest = in_dim > out_dim ? in_dim : out_dim;
-    if ((n + 64) * widest * 4 >= (1ll << 31) || (int64_t)out_dim * in_dim * 4 >= (1ll << 31))
-        return fail(LCREC_EUNSUPPORTED, "linear_backward: operands of %lld x %lld floats exceed the 2 GiB a buffer descriptor spans "
-                                        "(a training batch is expected here)", (long long)n, (long long)widest);
-    if (gx) {
-        // dX [n][in] = dY [n][out] * W [out][in]: A row-major (K = out), B = W as it is stored
-        if (out_dim % BK != 0) return fail(LCREC_EUNSUPPORTED, "linear_backward: out_dim=%d is not a multiple of 32", out_dim);
-        int rc = use_s16_tiles(n, in_dim, out_dim)             // an under-filled launch: the 32 x 64 tiles
-                     ? launch_s16(gy, W, nullptr, nullptr, nullptr, 0, gx, n, in_dim, out_dim, true, stream)
-                     : with_tile(forward_tile_shape(n, in_dim), [&](auto tile) { return launch_kmajor<false>(tile, gy, W, n, in_dim, out_dim, gx, 1, nullptr, stream); });
-        if (rc) return rc;
-    }
-    if (gw) {
-        // dW [out][in] = dY^T * X: A = dY [n][out] and B = X [n][in], both as they are stored (K = n, any length)
-        const int splits = linear_backward_splits(n, in_dim, out_dim);
-        const size_t need = linear_backward_workspace(n, in_dim, out_dim);
-        if (splits > 1 && (!workspace || workspace_bytes < need))
-            return fail(LCREC_EWORKSPACE, "linear_backward: workspace %zu B < required %zu B", workspace_bytes, need);
-        int rc = with_tile(forward_tile_shape(out_dim, in_dim), [&](auto tile) {
-            return launch_kmajor<true>(tile, gy, x, out_dim, in_dim, (int)n, gw, splits, reinterpret_cast<float *>(workspace), stream);
-        });
+    GemmStep steps[BWD_MAX_STEPS];
+    int count = 0;
+    if (int rc = backward_steps(n, in_dim, out_dim, gx != nullptr, gw != nullptr, steps, &count)) return rc;
+    for (int i = 0; i < count; ++i) {
+        const GemmStep &s = steps[i];
+        int rc = LCREC_OK;
+        if (s.role == LCREC_GEMMR_DX) {
+            rc = s.family == LCREC_GEMMK_32x64 ? launch_s16(s, gy, W, nullptr, nullptr, nullptr, 0, gx, stream)
+                                               : launch_kmajor(s, nullptr, gy, W, gx, nullptr, stream);
+        } else if (s.role == LCREC_GEMMR_DW) {
+            const size_t need = s.splits > 1 ? (size_t)s.splits * out_dim * in_dim * sizeof(float) : 0;
+            if (need && (!workspace || workspace_bytes < need))
+                return fail(LCREC_EWORKSPACE, "linear_backward: workspace %zu B < required %zu B", workspace_bytes, need);
+            rc = launch_kmajor(s, s.splits > 1 ? &steps[i + 1] : nullptr, gy, x, gw, reinterpret_cast<float *>(workspace), stream);
+        }                                                      // (a reduce step is launched with its product)
         if (rc) return rc;
     }
     return LCREC_OK;
+}
+
+static int linear_backward_plan(int64_t n, int in_dim, int out_dim, int want_gx, int want_gw, lcrec_gemm_launch *out, int capacity)
+{
+    if (!out || capacity < BWD_MAX_STEPS) return fail(LCREC_EINVAL, "linear_backward_plan: room for %d launches is needed", BWD_MAX_STEPS);
+    if (n == 0) return 0;
+    GemmStep steps[BWD_MAX_STEPS];
+    int count = 0;
+    if (int rc = backward_steps(n, in_dim, out_dim, want_gx != 0, want_gw != 0, steps, &count)) return rc;
+    for (int i = 0; i < count; ++i) describe_step(steps[i], out[i]);
+    return count;
 }
 
 // ---- grouped weight gradients (lcrec_linear_backward_weights): same S and run lengths per problem as linear_backward,
@@ -2159,69 +2309,127 @@ size_t linear_backward_weights_workspace(const lcrec_dw_problem *pr, int count)
     return total;
 }
 
+// What lcrec_linear_backward_weights launches, as pure steps: products[p] is problem p's share of the ONE grouped launch
+// (64 x 64 tiles, both operands k-major, PRO 2 for the whole launch as soon as one problem folds its input: a problem without
+// a fold runs it with scale 1, shift 0, clamp -inf), wg_start its first workgroup; reduces[j] the share of the j-th problem
+// with S > 1 in the grouped reducer.  grids: the two launches' workgroups.  Reads sizes, fold presence and `splits` only.
+struct DwGroupSteps {
+    GemmStep products[DW_GROUP_MAX], reduces[DW_GROUP_MAX];
+    int reduce_of[DW_GROUP_MAX];       // problem p's entry in reduces, or -1
+    int reduce_count;
+    unsigned grid_products, grid_reduce;
+};
+static int dw_group_steps(const lcrec_dw_problem *pr, int count, DwGroupSteps &d)
+{
+    if (!pr || count < 1 || count > DW_GROUP_MAX)
+        return fail(LCREC_EINVAL, "linear_backward_weights: %d problems (1..%d supported)", count, DW_GROUP_MAX);
+    bool any_pro = false;
+    for (int i = 0; i < count; ++i) any_pro = any_pro || pr[i].x_scale != nullptr;
+    d.reduce_count = 0;
+    d.grid_products = d.grid_reduce = 0;
+    for (int i = 0; i < count; ++i) {
+        const lcrec_dw_problem &q = pr[i];
+        if (q.n <= 0 || q.in_dim <= 0 || q.out_dim <= 0 || q.in_dim % 4 || q.out_dim % 4)
+            return fail(LCREC_EUNSUPPORTED, "linear_backward_weights: problem %d: n=%lld in=%d out=%d (positive, widths multiples of 4)", i,
+                        (long long)q.n, q.in_dim, q.out_dim);
+        const int64_t widest = q.in_dim > q.out_dim ? q.in_dim : q.out_dim;
+        if ((q.n + 64) * widest * 4 >= (1ll << 31) || (int64_t)q.out_dim * q.in_dim * 4 >= (1ll << 31))
+            return fail(LCREC_EUNSUPPORTED, "linear_backward_weights: problem %d exceeds the 2 GiB a buffer descriptor spans", i);
+        if ((q.x_scale == nullptr) != (q.x_shift == nullptr)) return fail(LCREC_EINVAL, "linear_backward_weights: problem %d: x_scale and x_shift go together", i);
+        GemmStep &s = d.products[i];                                       // 64 x 64 tiles for every problem
+        if (int rc = tile_step(s, "linear_backward_weights", LCREC_GEMMR_DW, TILE_64x64, true, true, true, any_pro ? 2 : 0, false, q.out_dim,
+                               q.in_dim, (int)q.n, dw_problem_splits(q)))
+            return rc;
+        s.wg_start = d.grid_products;
+        d.grid_products += s.g.grid * (unsigned)s.splits;
+        d.reduce_of[i] = -1;
+        if (s.splits > 1) {
+            GemmStep &r = d.reduces[d.reduce_count];
+            reduce_step(r, s);
+            r.wg_start = d.grid_reduce;
+            d.grid_reduce += r.g.grid;
+            d.reduce_of[i] = d.reduce_count++;
+        }
+    }
+    return LCREC_OK;
+}
+
 int linear_backward_weights(const lcrec_dw_problem *pr, int count, void *workspace, size_t workspace_bytes, hipStream_t stream)
 {
     if (count == 0) return LCREC_OK;
-    if (!pr || count < 0 || count > DW_GROUP_MAX)
-        return fail(LCREC_EINVAL, "linear_backward_weights: %d problems (1..%d supported)", count, DW_GROUP_MAX);
+    DwGroupSteps d;
+    if (int rc = dw_group_steps(pr, count, d)) return rc;
     const size_t need = linear_backward_weights_workspace(pr, count);
     if (workspace_bytes < need || (!workspace && need))
         return fail(LCREC_EWORKSPACE, "linear_backward_weights: workspace %zu B < required %zu B", workspace_bytes, need);
     DwGroup g = {};
     DwReduce r = {};
     char *ws = reinterpret_cast<char *>(workspace);
-    unsigned wg = 0, rwg = 0;
-    bool any_pro = false;
     for (int i = 0; i < count; ++i) {
         const lcrec_dw_problem &q = pr[i];
+        const GemmStep &s = d.products[i];
         if (!q.gy || !q.x || !q.gw) return fail(LCREC_EINVAL, "linear_backward_weights: NULL pointer in problem %d", i);
-        if (q.n <= 0 || q.in_dim <= 0 || q.out_dim <= 0 || q.in_dim % 4 || q.out_dim % 4)
-            return fail(LCREC_EUNSUPPORTED, "linear_backward_weights: problem %d: n=%lld in=%d out=%d (positive, widths multiples of 4)", i,
-                        (long long)q.n, q.in_dim, q.out_dim);
         if (((uintptr_t)q.gy | (uintptr_t)q.x | (uintptr_t)q.gw) & 15)
             return fail(LCREC_EINVAL, "linear_backward_weights: operands must be 16-byte aligned");
-        const int64_t widest = q.in_dim > q.out_dim ? q.in_dim : q.out_dim;
-        if ((q.n + 64) * widest * 4 >= (1ll << 31) || (int64_t)q.out_dim * q.in_dim * 4 >= (1ll << 31))
-            return fail(LCREC_EUNSUPPORTED, "linear_backward_weights: problem %d exceeds the 2 GiB a buffer descriptor spans", i);
-        const int splits = dw_problem_splits(q);
-        const int nk = (int)((q.n + BK - 1) / BK);
-        TileGrid tg;                                                      // 64 x 64 tiles for every problem
-        if (int rc = tile_grid(tg, "linear_backward_weights", q.out_dim, q.in_dim, 64, 64, XCD_ORDER)) return rc;
-        g.A[i] = q.gy; g.B[i] = q.x;
-        if ((q.x_scale == nullptr) != (q.x_shift == nullptr)) return fail(LCREC_EINVAL, "linear_backward_weights: problem %d: x_scale and x_shift go together", i);
         if (((uintptr_t)q.x_scale | (uintptr_t)q.x_shift) & 15) return fail(LCREC_EINVAL, "linear_backward_weights: x_scale / x_shift must be 16-byte aligned");
+        g.A[i] = q.gy; g.B[i] = q.x;
         g.xs[i] = q.x_scale; g.xh[i] = q.x_shift;
         g.lo[i] = (q.x_scale && q.x_relu) ? 0.0f : -__builtin_inff();
-        any_pro = any_pro || q.x_scale != nullptr;
-        g.M[i] = q.out_dim; g.N[i] = q.in_dim; g.K[i] = (int)q.n;
-        g.bn_blocks[i] = tg.bn_blocks; g.bm_blocks[i] = (int)tg.bm_blocks; g.tiles[i] = (int)tg.grid;
-        g.kt_per_split[i] = splits > 1 ? (nk + splits - 1) / splits : 1 << 30;
-        g.wg_start[i] = wg;
-        wg += tg.grid * (unsigned)(splits > 1 ? splits : 1);
-        if (splits > 1) {
+        g.M[i] = (int)s.M; g.N[i] = s.N; g.K[i] = s.K;
+        g.bn_blocks[i] = s.g.bn_blocks; g.bm_blocks[i] = (int)s.g.bm_blocks; g.tiles[i] = (int)s.g.grid;
+        g.kt_per_split[i] = s.per;
+        g.wg_start[i] = s.wg_start;
+        if (d.reduce_of[i] >= 0) {
+            const int j = d.reduce_of[i];
+            const GemmStep &rs = d.reduces[j];
             float *partial = reinterpret_cast<float *>(ws);
             ws += align_up(dw_problem_workspace(q), 256);
             g.C[i] = partial;
-            const int j = r.count++;
-            r.partial[j] = partial; r.out[j] = q.gw; r.splits[j] = splits;
-            r.total4[j] = (unsigned)((int64_t)q.out_dim * q.in_dim / 4);
-            r.wg_start[j] = rwg;
-            rwg += (r.total4[j] + 255) / 256;
+            r.partial[j] = partial; r.out[j] = q.gw; r.splits[j] = rs.splits;
+            r.total4[j] = (unsigned)rs.total4;
+            r.wg_start[j] = rs.wg_start;
         } else {
             g.C[i] = q.gw;
         }
     }
     g.count = count;
-    g.wg_start[count] = wg;
-    r.wg_start[r.count] = rwg;
+    g.wg_start[count] = d.grid_products;
+    r.count = d.reduce_count;
+    r.wg_start[r.count] = d.grid_reduce;
     TraceScope trace(K_LINEAR_64x64, stream);
-    hipLaunchKernelGGL(any_pro ? linear_dw_grouped_kernel<true> : linear_dw_grouped_kernel<false>, dim3(wg), dim3(256), 0, stream, g);
-    if (r.count) hipLaunchKernelGGL(splitk_reduce_grouped_kernel, dim3(rwg), dim3(256), 0, stream, r);
+    hipLaunchKernelGGL(d.products[0].pro ? linear_dw_grouped_kernel<true> : linear_dw_grouped_kernel<false>, dim3(d.grid_products), dim3(256), 0,
+                       stream, g);
+    if (r.count) hipLaunchKernelGGL(splitk_reduce_grouped_kernel, dim3(d.grid_reduce), dim3(256), 0, stream, r);
     return check_launch("linear_dw_grouped_kernel");
+}
+
+static int linear_backward_weights_plan(const lcrec_dw_problem *pr, int count, lcrec_gemm_launch *out, int capacity, int *grid_out)
+{
+    if (!out || !grid_out || capacity < 2 * count) return fail(LCREC_EINVAL, "linear_backward_weights_plan: room for %d records is needed", 2 * count);
+    DwGroupSteps d;
+    if (int rc = dw_group_steps(pr, count, d)) return rc;
+    for (int i = 0; i < count; ++i) describe_step(d.products[i], out[i]);
+    for (int j = 0; j < d.reduce_count; ++j) describe_step(d.reduces[j], out[count + j]);
+    grid_out[0] = (int)d.grid_products;
+    grid_out[1] = (int)d.grid_reduce;
+    return count + d.reduce_count;
 }
 
 // ---- lcrec_linear_bn_forward: the training step's Linear with its input's BatchNorm + ReLU folded into the operand staging
 // and its output's batch statistics taken in the epilogue (TileExtras)
+// The one launch of lcrec_linear_bn_forward with a fold (pro) and / or statistics, as a pure step; the shapes the entry point
+// refuses come back as its code.  linear_bn_forward() launches it, lcrec_debug_linear_bn_forward_plan() reports it.
+static int train_fwd_step(int64_t n, int in_dim, int out_dim, bool pro, bool stats, GemmStep &s)
+{
+    if (in_dim % BK != 0 || out_dim % 4 != 0)
+        return fail(LCREC_EUNSUPPORTED, "linear_bn_forward: in_dim=%d must be a multiple of 32, out_dim=%d of 4", in_dim, out_dim);
+    if (((n + 127) / 128) * ((out_dim + 127) / 128) >= 512 || (int64_t)in_dim * 4 * (n + 128) >= (1ll << 31) || out_dim > 64 * 64)
+        return fail(LCREC_EUNSUPPORTED, "linear_bn_forward: sized for training batches (n=%lld, out_dim=%d)", (long long)n, out_dim);
+    if (stats && n < 2) return fail(LCREC_EINVAL, "linear_bn_forward: training-mode BatchNorm needs more than 1 row (n=%lld)", (long long)n);
+    return tile_step(s, "linear_bn_forward", LCREC_GEMMR_FORWARD, train_tile_shape(n, out_dim), true, false, false, pro ? 1 : 0, stats, n,
+                     out_dim, in_dim, 1);
+}
+
 size_t linear_bn_forward_workspace(int64_t n, int out_dim)
 {
     const int bm = tile_dims(train_tile_shape(n, out_dim)).bm;
@@ -2235,18 +2443,15 @@ int linear_bn_forward(const float *x, int64_t n, int in_dim, const float *in_sca
                       unsigned *tickets, hipStream_t stream)
 {
     if (!x || !W || !t_out) return fail(LCREC_EINVAL, "linear_bn_forward: NULL pointer");
-    if (n < 1 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_bn_forward: bad shape");
     if ((in_scale == nullptr) != (in_shift == nullptr)) return fail(LCREC_EINVAL, "linear_bn_forward: in_scale and in_shift go together");
     const bool pro = in_scale != nullptr, stats = want_stats != 0;
+    if (n < 1 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_bn_forward: bad shape");
     if (!pro && !stats) return linear_forward(x, n, in_dim, W, b, nullptr, nullptr, 0, out_dim, t_out, stream);
-    if (in_dim % BK != 0 || out_dim % 4 != 0)
-        return fail(LCREC_EUNSUPPORTED, "linear_bn_forward: in_dim=%d must be a multiple of 32, out_dim=%d of 4", in_dim, out_dim);
+    GemmStep step;
+    if (int rc = train_fwd_step(n, in_dim, out_dim, pro, stats, step)) return rc;
     if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)in_scale | (uintptr_t)in_shift) & 15)
         return fail(LCREC_EINVAL, "linear_bn_forward: operands must be 16-byte aligned");
-    if (((n + 127) / 128) * ((out_dim + 127) / 128) >= 512 || (int64_t)in_dim * 4 * (n + 128) >= (1ll << 31) || out_dim > 64 * 64)
-        return fail(LCREC_EUNSUPPORTED, "linear_bn_forward: sized for training batches (n=%lld, out_dim=%d)", (long long)n, out_dim);
     if (stats) {
-        if (n < 2) return fail(LCREC_EINVAL, "linear_bn_forward: training-mode BatchNorm needs more than 1 row (n=%lld)", (long long)n);
         if (!mean_out || !rstd_out || !scale_out || !shift_out || !tickets) return fail(LCREC_EINVAL, "linear_bn_forward: NULL statistics output or tickets");
         if (!workspace || workspace_bytes < linear_bn_forward_workspace(n, out_dim))
             return fail(LCREC_EWORKSPACE, "linear_bn_forward: workspace %zu B < required %zu B", workspace_bytes, linear_bn_forward_workspace(n, out_dim));
@@ -2257,12 +2462,18 @@ int linear_bn_forward(const float *x, int64_t n, int in_dim, const float *in_sca
     ex.gamma = gamma; ex.beta = beta; ex.eps = eps; ex.momentum = momentum;
     ex.running_mean = running_mean; ex.running_var = running_var;
     ex.mean_out = mean_out; ex.rstd_out = rstd_out; ex.scale_out = scale_out; ex.shift_out = shift_out;
-    return with_tile(train_tile_shape(n, out_dim), [&](auto tile) -> int {
-        if constexpr (decltype(tile)::BM == 128 && decltype(tile)::BN > 32)       // never chosen: no training kernel is built for these
-            return fail(LCREC_EUNSUPPORTED, "linear_bn_forward: no kernel for %d x %d tiles", decltype(tile)::BM, decltype(tile)::BN);
-        else
-            return launch_train_fwd(tile, x, n, in_dim, W, b, out_dim, t_out, pro, stats, ex, stream);
-    });
+    return launch_train_fwd(step, x, W, b, t_out, ex, stream);
+}
+
+static int linear_bn_forward_plan(int64_t n, int in_dim, int out_dim, int pro, int stats, lcrec_gemm_launch *out)
+{
+    if (!out) return fail(LCREC_EINVAL, "linear_bn_forward_plan: NULL output");
+    if (n < 1 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_bn_forward: bad shape");
+    if (!pro && !stats) return 0;
+    GemmStep step;
+    if (int rc = train_fwd_step(n, in_dim, out_dim, pro != 0, stats != 0, step)) return rc;
+    describe_step(step, *out);
+    return 1;
 }
 
 }  // namespace lcrec
@@ -2273,7 +2484,32 @@ int linear_bn_forward(const float *x, int64_t n, int in_dim, const float *in_sca
 extern "C" __attribute__((visibility("default"))) int lcrec_debug_linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus,
                                                                                         lcrec_debug_forward_launch *out, int capacity)
 {
+    if (!out || capacity < lcrec::FWD_MAX_STEPS) return LCREC_EINVAL;
+    lcrec_debug_forward_launch_ext ext[lcrec::FWD_MAX_STEPS];
+    const int count = lcrec::linear_forward_plan(n, in_dim, out_dim, cus, ext, lcrec::FWD_MAX_STEPS);
+    for (int i = 0; i < count; ++i) out[i] = ext[i].base;
+    return count;
+}
+// The same with the extended records (tests/gemm_pp_cases.py holds the matching ctypes struct).
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_linear_forward_plan_ext(int64_t n, int in_dim, int out_dim, int cus,
+                                                                                            lcrec_debug_forward_launch_ext *out, int capacity)
+{
     return lcrec::linear_forward_plan(n, in_dim, out_dim, cus, out, capacity);
+}
+
+// Debug exports (include/lcrec.h): the launches of the other three GEMM entry points, from the step functions they launch by.
+LCREC_API int lcrec_debug_linear_backward_plan(int64_t n, int in_dim, int out_dim, int want_gx, int want_gw, lcrec_gemm_launch *out, int capacity)
+{
+    return lcrec::linear_backward_plan(n, in_dim, out_dim, want_gx, want_gw, out, capacity);
+}
+LCREC_API int lcrec_debug_linear_backward_weights_plan(const lcrec_dw_problem *problems, int count, lcrec_gemm_launch *out, int capacity,
+                                                       int *grid_out)
+{
+    return lcrec::linear_backward_weights_plan(problems, count, out, capacity, grid_out);
+}
+LCREC_API int lcrec_debug_linear_bn_forward_plan(int64_t n, int in_dim, int out_dim, int pro, int stats, lcrec_gemm_launch *out)
+{
+    return lcrec::linear_bn_forward_plan(n, in_dim, out_dim, pro, stats, out);
 }
 
 #ifdef LCREC_GEMM_STAMP

@@ -312,6 +312,64 @@ def linear_backward_splits(n, in_dim, out_dim):
     return int(_lib.load().lcrec_linear_backward_splits(n, in_dim, out_dim))
 
 
+GEMM_ROLES = ("dx", "dw", "reduce", "forward")                 # LCREC_GEMMR_* of include/lcrec.h, in order
+GEMM_FAMILIES = ("tile_body", "32x64", "reducer")              # LCREC_GEMMK_*
+
+
+def _gemm_launches(buf, count):
+    out = []
+    for i in range(count):
+        d = {name: getattr(buf[i], name) for name, _ in _lib.GemmLaunch._fields_}
+        d["label"] = d["label"].decode()
+        d["role"] = GEMM_ROLES[d["role"]]
+        d["family"] = GEMM_FAMILIES[d["family"]]
+        out.append(d)
+    return out
+
+
+def linear_backward_plan(n, in_dim, out_dim, need_gx=True, need_gw=True):
+    """The launches of linear_backward for these sizes, in order (include/lcrec.h, lcrec_debug_linear_backward_plan): a list of
+    dicts of the fields of lcrec_gemm_launch, `role` and `family` as their names in GEMM_ROLES / GEMM_FAMILIES.  Host only: no
+    GPU is needed.  Raises LcrecError for a shape the entry point refuses."""
+    buf = (_lib.GemmLaunch * 3)()
+    count = _lib.load().lcrec_debug_linear_backward_plan(int(n), int(in_dim), int(out_dim), int(bool(need_gx)), int(bool(need_gw)),
+                                                         ctypes.addressof(buf), 3)
+    if count < 0:
+        _lib.check(count, "lcrec_debug_linear_backward_plan")
+    return _gemm_launches(buf, count)
+
+
+def linear_backward_weights_plan(problems):
+    """What linear_backward_weights launches for `problems`, a list of (n, in_dim, out_dim, folded, splits): (products, reducers,
+    (grid of the grouped launch, grid of the grouped reducer)) -- products[p] is problem p's share of the one launch, reducers the
+    shares of the problems with more than one K-run, in problem order.  Host only (lcrec_debug_linear_backward_weights_plan)."""
+    count = len(problems)
+    arr = (_lib.DwProblem * max(count, 1))()
+    for i, (n, in_dim, out_dim, folded, splits) in enumerate(problems):
+        flag = 16 if folded else None                          # only whether a fold is given is read
+        arr[i] = _lib.DwProblem(None, None, None, int(n), int(in_dim), int(out_dim), flag, flag, int(bool(folded)), int(splits))
+    buf = (_lib.GemmLaunch * max(2 * count, 1))()
+    grids = (ctypes.c_int * 2)()
+    got = _lib.load().lcrec_debug_linear_backward_weights_plan(ctypes.cast(arr, ctypes.c_void_p), count, ctypes.addressof(buf), 2 * count,
+                                                               grids)
+    if got < 0:
+        _lib.check(got, "lcrec_debug_linear_backward_weights_plan")
+    launches = _gemm_launches(buf, got)
+    return launches[:count], launches[count:], (int(grids[0]), int(grids[1]))
+
+
+def linear_bn_forward_plan(n, in_dim, out_dim, pro, stats):
+    """The launch of linear_bn_forward with an input fold (pro) and / or batch statistics (stats), as a dict of the fields of
+    lcrec_gemm_launch; None when neither is asked for (the call is linear_forward's).  Host only
+    (lcrec_debug_linear_bn_forward_plan)."""
+    buf = (_lib.GemmLaunch * 1)()
+    got = _lib.load().lcrec_debug_linear_bn_forward_plan(int(n), int(in_dim), int(out_dim), int(bool(pro)), int(bool(stats)),
+                                                         ctypes.addressof(buf))
+    if got < 0:
+        _lib.check(got, "lcrec_debug_linear_bn_forward_plan")
+    return _gemm_launches(buf, got)[0] if got else None
+
+
 def flatten_codebooks(codebooks):
     """List of [K_l, e] tensors -> (flat fp32 tensor, [K_l]) in the layout lcrec_rq_assign expects."""
     ks = [int(c.shape[0]) for c in codebooks]

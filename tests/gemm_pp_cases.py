@@ -16,19 +16,19 @@ TILE_M, TILE_N, GROUP_M = 256, 128, 128
 
 
 class ForwardLaunch(ctypes.Structure):
-    """lcrec_debug_forward_launch of csrc/gemm_f32.hip"""
+    """lcrec_debug_forward_launch_ext of csrc/gemm_f32.hip: lcrec_debug_forward_launch with `fast` and `register_buffered` at its end"""
     _fields_ = [("row0", ctypes.c_int64), ("rows", ctypes.c_int64), ("label", ctypes.c_char_p), ("form", ctypes.c_int),
                 ("tile_rows", ctypes.c_int), ("tile_cols", ctypes.c_int), ("k_tiles", ctypes.c_int), ("tiles", ctypes.c_int),
                 ("virtual_tiles", ctypes.c_int), ("workgroups", ctypes.c_int), ("last_panel_rows", ctypes.c_int),
                 ("steady_iterations", ctypes.c_int), ("list_min", ctypes.c_int), ("list_max", ctypes.c_int),
                 ("empty_workgroups", ctypes.c_int), ("single_tile_workgroups", ctypes.c_int),
-                ("ragged_handed_over", ctypes.c_int)]
+                ("ragged_handed_over", ctypes.c_int), ("fast", ctypes.c_int), ("register_buffered", ctypes.c_int)]
 
 
 def plan(lib, n, k, out, cus):
     """The launches lcrec_linear_forward makes for [n][k] -> [n][out] on `cus` compute units: a list of dicts (the fields of
     ForwardLaunch, label decoded).  Host code of the library: no GPU is needed."""
-    fn = lib.lcrec_debug_linear_forward_plan
+    fn = lib.lcrec_debug_linear_forward_plan_ext
     fn.restype = ctypes.c_int
     fn.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ForwardLaunch), ctypes.c_int]
     buf = (ForwardLaunch * 4)()

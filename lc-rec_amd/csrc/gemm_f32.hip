@@ -54,6 +54,17 @@ __device__ unsigned long long g_marks[8][4];      // kernel entry, prologue done
             g_stamps[wave][2 * u + half][slot] = t_;                                               \
         }                                                                                          \
     } while (0)
+// persistent ping-pong kernel: the phase number runs on across the workgroup's tiles (stamp_u0 = K-tiles of the tiles before
+// this one), so the first 64 phases of its list stay: with 24 K-tiles per tile, phases 46..47 are the first tile's TAIL1 and
+// 48..63 the second tile's HEAD -- the hand-over, pieces included
+#define LCREC_STAMP3(slot)                                                                         \
+    do {                                                                                           \
+        if (blockIdx.x == 8 && lane == 0 && 2 * (stamp_u0 + u) + half < 64) {                      \
+            unsigned long long t_;                                                                 \
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
+            g_stamps[wave][2 * (stamp_u0 + u) + half][slot] = t_;                                  \
+        }                                                                                          \
+    } while (0)
 // generic (non ping-pong) kernel: workgroup with tile number 9, lane 0 of each wave, first 64 K-tiles, 6 points per K-tile
 __device__ unsigned long long g_gen_stamps[4][64][6];
 #define LCREC_GSTAMP(slot)                                                                         \
@@ -75,6 +86,7 @@ __device__ unsigned long long g_gen_stamps[4][64][6];
     } while (0)
 #else
 #define LCREC_STAMP(slot) do { } while (0)
+#define LCREC_STAMP3(slot) do { } while (0)
 #define LCREC_MARK(slot) do { } while (0)
 #define LCREC_GSTAMP(slot) do { } while (0)
 #define LCREC_GMARK(slot) do { } while (0)
@@ -1176,17 +1188,27 @@ __global__ __launch_bounds__(512) void linear_fwd_pp2_kernel(
 //     roles: patch writes in the compute role, two reads + two stores in the staging role.
 // Measured on MI355X (131 072 rows, TFLOP/s, this / linear_fwd_pp2_kernel): 768->2048 143 / 140, 2048->1024 151 / 150,
 // 1024->512 146 / 144, 512->256 138 / 134; C3 end to end 16.49 M vs 16.30 M items/s.
+// The hand-over since then (profiles/pp3_handover_*.txt; builds interleaved on one machine): ReLU, bias and BN
+// are template arguments (the run-time `relu` cost every accumulator
+// element v_cmp + s_or_b64 vcc + v_cndmask ahead of the tile's first MFMA: HEAD0 ran 3.3 k ticks over a steady K-tile, now
+// 0.5 k), the previous tile's output descriptor is built once, where the tile is handed over, and a piece's store offsets
+// beside its patch writes, so a send block holds no scalar arithmetic and no VALU: 148.4 / 152.8 / 148.3 / 139.1 against the
+// parent's 145.2 / 151.0 / 146.3 / 136.7 in the same job, C3 -1.0 % per pass.  The STEADY loop is the parent's, both roles,
+// wait operands included, in all eight instantiations.  Tried on top and dropped, both slower end to end although each
+// shortens the stretch it aims at: next_tile() inside K-tile 9's compute phase, and the epilogue arithmetic dealt between
+// HEAD0's first four MFMAs (the TAIL1 half of that idea was not built).  Of the ~13 k cycles a tile still costs outside
+// STEADY about a third is located (TAIL +1.0 k ticks per K-tile, HEAD0 +0.6 k, pieces +0.3 k each); the rest is not.
 // Same arithmetic as every other kernel here: one fma chain per output over k ascending, epilogue after it.
 // K = 384 is 12 K-tiles: HEAD and TAIL take them all and the STEADY loop is empty; it runs (K / 32 - 12) / 2 times per tile.
 // tests/gemm_pp_cases.py lists the smallest shape that reaches each path (one tile per workgroup, hand-over, ragged panels, ...).
 // ------------------------------------------------------------------------------------------
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
-template <bool HAS_BN>
+template <bool HAS_BN, bool RELU, bool HAS_BIAS>
 __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
     const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
     const float *__restrict__ bn_scale, const float *__restrict__ bn_shift, float *__restrict__ C,
-    int64_t M, int N, int K, int relu, int bn_blocks, int bm_blocks, int total_virtual, int xcd_order)
+    int64_t M, int N, int K, int bn_blocks, int bm_blocks, int total_virtual, int xcd_order)
 {
     constexpr int GM = 128, BN = 128, LDT = LDK;
     // parts of a tile's K loop: HEAD0 = K-tile 0, HEAD_S0 + p = K-tile 1 + p carrying epilogue piece p (8 pieces: the
@@ -1234,11 +1256,14 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
         return total_virtual;
     };
 
-    int64_t cur_m0 = 0, nxt_m0 = 0, prv_m0 = 0;
-    int cur_n0 = 0, nxt_n0 = 0, prv_n0 = 0, cur_ar = 0, nxt_ar = 0, prv_ar = 0, cur_wr = 0, nxt_wr = 0;
+    int64_t cur_m0 = 0, nxt_m0 = 0;
+    int cur_n0 = 0, nxt_n0 = 0, cur_ar = 0, nxt_ar = 0, cur_wr = 0, nxt_wr = 0;
     int t = blockIdx.x;
     if (!tile_of(t, cur_m0, cur_n0, cur_ar, cur_wr)) t = next_tile(t, cur_m0, cur_n0, cur_ar, cur_wr);
     if (t >= total_virtual) return;
+#ifdef LCREC_GEMM_STAMP
+    int stamp_u0 = 0;
+#endif
     int has_next = 0, have_prev = 0;
 
     const int t_g = ((gt >> 2) * K + (gt & 3) * 8) * 4;
@@ -1250,6 +1275,7 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
     // operand descriptors of the current and the next tile, rebuilt once per tile
     __amdgpu_buffer_rsrc_t cur_a = tile_rsrc(A, cur_m0, M, GM, K), cur_w = tile_rsrc(W, cur_n0 + grp * 64, N, 64, K);
     __amdgpu_buffer_rsrc_t nxt_a = cur_a, nxt_w = cur_w;
+    __amdgpu_buffer_rsrc_t prv_c = cur_a;       // the previous tile's output descriptor: built at the hand-over, read by K-tiles 1..9
 
     f32x4 ra[2][2], rw[2];
     auto load_a = [&](__amdgpu_buffer_rsrc_t r, int kt) __attribute__((always_inline)) {
@@ -1281,23 +1307,30 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int col = n0 + wn * 64 + j * 32 + (lane & 31);
-            e.b[j] = bias ? bias[col] : 0.f;
+            e.b[j] = HAS_BIAS ? bias[col] : 0.f;
             e.sc[j] = HAS_BN ? bn_scale[col] : 1.f;
             e.sh[j] = HAS_BN ? bn_shift[col] : 0.f;
+        }
+    };
+    // The switches are template arguments: per element an add (of 0.0f without a bias, as the oracle adds it: -0.0f becomes
+    // +0.0f), the fma if BN, and the ReLU -- as run-time arguments every element also paid an s_or_b64 of the uniform `relu`
+    // into VCC, a VALU -> SALU -> VALU round trip (v_cmp, s_or, v_cndmask: 256 serialised instructions per wave and tile).
+    // With RELU a constant the compiler folds compare + select against 0.0f into one v_max_f32; NaN and -0.0f both leave it
+    // as +0.0f like the oracle's (t > 0) ? t : 0 (tests/test_gpu_gemm_pp_handover.py, the special-value row).
+    auto epi_sub = [&](f32x16 &dst, const f32x16 &src, const EpiConst &e, int j) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = src[r] + e.b[j];
+            if (HAS_BN) v = __builtin_fmaf(v, e.sc[j], e.sh[j]);
+            if (RELU) v = (v > 0.f) ? v : 0.f;
+            dst[r] = v;
         }
     };
     auto epi_math = [&](f32x16 (&dst)[2][2], const f32x16 (&src)[2][2], const EpiConst &e) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = src[i][j][r] + e.b[j];
-                    if (HAS_BN) v = __builtin_fmaf(v, e.sc[j], e.sh[j]);
-                    if (relu) v = (v > 0.f) ? v : 0.f;
-                    dst[i][j][r] = v;
-                }
+            for (int j = 0; j < 2; ++j) epi_sub(dst[i][j], src[i][j], e, j);
     };
     // one 32 x 32 sub-tile of a post-processed accumulator set -> C, through this wave's LDS patch
     // The epilogue pieces run in the STAGING role, where every VALU instruction waits for a gap in the partner's MFMA
@@ -1322,11 +1355,34 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
         LCREC_PATCH_W(4); LCREC_PATCH_W(5); LCREC_PATCH_W(6); LCREC_PATCH_W(7);
 #undef LCREC_PATCH_W
     };
-    auto epi_send = [&](auto i_c, auto j_c, auto hf_c, int64_t t_m0, int t_n0, int rows) __attribute__((always_inline)) {
-        constexpr int i = decltype(i_c)::value, j = decltype(j_c)::value, hf = decltype(hf_c)::value;
+    // The output tile's descriptor (base = the group's first row of the tile, extent = its valid rows) is built once per
+    // tile, where the tile is handed over (c_tile_rsrc, at the end of the tile loop's body).  Built inside HEAD0's compute
+    // phase instead it cost the staging role its counted vmcnt waits -- one vmcnt(0) ahead of all twelve ds_write2_b32, in
+    // STEADY too, in every instantiation with a bias or BN; the reason was not found.
+    // The SGPR offsets of a piece's two stores -- the wave's offset in the tile
+    // (once per launch) plus a multiple of eight output rows (a step, once per launch) -- are computed by epi_aim in the
+    // compute role, beside the piece's patch writes.  So a send block is two LDS reads, two stores and their waits: no
+    // scalar arithmetic, no VALU.  (Re-derived in each of the eight send blocks, descriptor and offsets were ~22 scalar
+    // instructions, two branches and a v_readlane_b32 of a spilled SGPR.  The empty asm keeps the compiler from hoisting
+    // all sixteen offsets out of the tile loop, where it spills half of them to VGPR lanes and reads them back in the send
+    // blocks.)  A wave alternates strictly between aiming a piece and sending it, so one pair of offsets is enough.
+    auto c_tile_rsrc = [&](int64_t t_m0, int t_n0, int rows) __attribute__((always_inline)) {
         const int extent = rows > 0 ? ((rows - 1) * N + BN) * 4 : 0;
-        const __amdgpu_buffer_rsrc_t c_rsrc =
-            __builtin_amdgcn_make_buffer_rsrc(C + t_m0 * (int64_t)N + t_n0, 0, extent, 0x00020000);
+        return __builtin_amdgcn_make_buffer_rsrc(C + t_m0 * (int64_t)N + t_n0, 0, extent, 0x00020000);
+    };
+    const int c_soff0 = __builtin_amdgcn_readfirstlane(((wm * 64) * N + wn * 64) * 4);
+    const int c_step8 = N * 32;                // bytes from one output row to the eighth after it
+    int c_so0 = 0, c_so1 = 0;
+    auto epi_aim = [&](auto i_c, auto j_c, auto hf_c) __attribute__((always_inline)) {
+        constexpr int i = decltype(i_c)::value, j = decltype(j_c)::value, hf = decltype(hf_c)::value;
+        int o0 = c_soff0 + (4 * i + 2 * hf) * c_step8 + j * 32 * 4;   // row wm * 64 + i * 32 + 16 hf, column wn * 64 + j * 32
+        int o1 = o0 + c_step8;                                        // eight rows further down
+        asm volatile("" : "+s"(o0), "+s"(o1));
+        c_so0 = o0;
+        c_so1 = o1;
+    };
+    auto epi_send = [&](auto hf_c, __amdgpu_buffer_rsrc_t c_rsrc) __attribute__((always_inline)) {
+        constexpr int hf = decltype(hf_c)::value;
         f32x4 q[2];
         asm volatile("s_waitcnt lgkmcnt(0)\n\t"
                      "ds_read_b128 %0, %2 offset:%3\n\t"
@@ -1337,8 +1393,7 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
                      : "memory");
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            const int soff = ((wm * 64 + i * 32 + 8 * (2 * hf + p)) * N + wn * 64 + j * 32) * 4;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, q[p]), c_rsrc, c_voff, soff, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, q[p]), c_rsrc, c_voff, p == 0 ? c_so0 : c_so1, 0);
             // A 16-byte buffer store reads its data VGPRs a few cycles AFTER issue.  The compiler inserts the required
             // wait state before an instruction that overwrites them -- except when the store has an SGPR offset (LLVM
             // assumes that form is safe; on gfx950 it is not: the next VALU write, e.g. the v_cndmask of a branch
@@ -1346,9 +1401,10 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
             asm volatile("s_nop 3" ::: "memory");
         }
     };
-    auto epi_store = [&](const f32x16 &v, auto i_c, auto j_c, auto hf_c, int64_t t_m0, int t_n0, int rows) __attribute__((always_inline)) {
+    auto epi_store = [&](const f32x16 &v, auto i_c, auto j_c, auto hf_c, __amdgpu_buffer_rsrc_t c_rsrc) __attribute__((always_inline)) {
         epi_patch(v, hf_c);
-        epi_send(i_c, j_c, hf_c, t_m0, t_n0, rows);
+        epi_aim(i_c, j_c, hf_c);
+        epi_send(hf_c, c_rsrc);
     };
 
     // ---- prologue of the workgroup's first tile: W[0] (both halves) and A0[0] into LDS; group 1 keeps (A1[0], upper W[1])
@@ -1372,7 +1428,7 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
     auto phase = [&](auto par_c, auto half_c, auto mode_c, int u) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_c)::value, half = decltype(half_c)::value, MODE = decltype(mode_c)::value;
         if (grp == half) {
-            LCREC_STAMP(0);
+            LCREC_STAMP3(0);
             const float *w_base = Ws0 + PAR * BN * LDT + w_off;
             f32x4 af[2][2], wf[2][2];
             auto frags = [&](int buf, int g) {
@@ -1434,6 +1490,7 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
                 if (have_prev) {
                     constexpr int s = (MODE - HEAD_S0) >> 1, hf = (MODE - HEAD_S0) & 1;
                     epi_patch(prev[s >> 1][s & 1], IntC<hf>{});
+                    epi_aim(IntC<(s >> 1)>{}, IntC<(s & 1)>{}, IntC<hf>{});
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1445,32 +1502,31 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
             mfma_group(af[0], wf[0]);                                   // k group 2
             reads_then_mfmas();
             __builtin_amdgcn_sched_barrier(0);
-            LCREC_STAMP(1);
+            LCREC_STAMP3(1);
             lds_barrier();                                            // after this wave's LAST LDS read of the tile
-            LCREC_STAMP(2);
+            LCREC_STAMP3(2);
             __builtin_amdgcn_s_setprio(3);
             mfma_group(af[1], wf[1]);                                   // k group 3
             __builtin_amdgcn_s_setprio(0);
-            LCREC_STAMP(3);
+            LCREC_STAMP3(3);
         } else {
-            LCREC_STAMP(0);
+            LCREC_STAMP3(0);
             store_a();
             store_w(PAR ^ 1);
             lds_drain();
-            LCREC_STAMP(1);
+            LCREC_STAMP3(1);
             // K-tiles 1..4 of a tile: one sub-tile of the previous tile's output per staging phase
             // the piece this wave wrote to its patch in its last compute phase: this K-tile's for group 0 (half == 1
             // phases), the previous K-tile's for group 1 (whose staging phase comes first in a K-tile)
             constexpr int PIECE = MODE - HEAD_S0 - (half == 0 ? 1 : 0);
             if constexpr (MODE >= HEAD_S0 && MODE <= HEAD_S8 && PIECE >= 0 && PIECE < 8) {
                 if (have_prev) {
-                    constexpr int s = PIECE >> 1, hf = PIECE & 1;
-                    epi_send(IntC<(s >> 1)>{}, IntC<(s & 1)>{}, IntC<hf>{}, prv_m0, prv_n0, prv_ar);
+                    epi_send(IntC<(PIECE & 1)>{}, prv_c);
                 }
             }
-            LCREC_STAMP(3);
+            LCREC_STAMP3(3);
             lds_barrier();
-            LCREC_STAMP(2);
+            LCREC_STAMP3(2);
         }
     };
     auto pair = [&](auto par_c, auto mode_c, int u) __attribute__((always_inline)) {
@@ -1479,14 +1535,11 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
     };
     auto finish = [&]() __attribute__((always_inline)) {     // the workgroup's last tile: nothing left to hide behind
         epi_math(acc, acc, ec);
-        epi_store(acc[0][0], IntC<0>{}, IntC<0>{}, IntC<0>{}, cur_m0, cur_n0, cur_ar);
-        epi_store(acc[0][0], IntC<0>{}, IntC<0>{}, IntC<1>{}, cur_m0, cur_n0, cur_ar);
-        epi_store(acc[0][1], IntC<0>{}, IntC<1>{}, IntC<0>{}, cur_m0, cur_n0, cur_ar);
-        epi_store(acc[0][1], IntC<0>{}, IntC<1>{}, IntC<1>{}, cur_m0, cur_n0, cur_ar);
-        epi_store(acc[1][0], IntC<1>{}, IntC<0>{}, IntC<0>{}, cur_m0, cur_n0, cur_ar);
-        epi_store(acc[1][0], IntC<1>{}, IntC<0>{}, IntC<1>{}, cur_m0, cur_n0, cur_ar);
-        epi_store(acc[1][1], IntC<1>{}, IntC<1>{}, IntC<0>{}, cur_m0, cur_n0, cur_ar);
-        epi_store(acc[1][1], IntC<1>{}, IntC<1>{}, IntC<1>{}, cur_m0, cur_n0, cur_ar);
+        const __amdgpu_buffer_rsrc_t cur_c = c_tile_rsrc(cur_m0, cur_n0, cur_ar);
+        static_for<8>([&](auto p_c) {
+            constexpr int s = decltype(p_c)::value >> 1, hf = decltype(p_c)::value & 1;
+            epi_store(acc[s >> 1][s & 1], IntC<(s >> 1)>{}, IntC<(s & 1)>{}, IntC<hf>{}, cur_c);
+        });
     };
 
     for (;;) {
@@ -1511,10 +1564,13 @@ __global__ __launch_bounds__(512) void linear_fwd_pp3_kernel(
         pair(IntC<0>{}, IntC<TAIL0>{}, nk - 2);
         pair(IntC<1>{}, IntC<TAIL1>{}, nk - 1);
         if (!has_next) { finish(); break; }
-        prv_m0 = cur_m0; prv_n0 = cur_n0; prv_ar = cur_ar;
+        prv_c = c_tile_rsrc(cur_m0, cur_n0, cur_ar);
         cur_m0 = nxt_m0; cur_n0 = nxt_n0; cur_ar = nxt_ar; cur_wr = nxt_wr; cur_a = nxt_a; cur_w = nxt_w;
         t = tn;
         have_prev = 1;
+#ifdef LCREC_GEMM_STAMP
+        stamp_u0 += nk;
+#endif
     }
 }
 
@@ -1973,16 +2029,25 @@ static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
             return v;
         }();
-        static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp3_kernel<false>),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-        static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp3_kernel<true>),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-        if (attr0 != hipSuccess || attr1 != hipSuccess)
-            return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds3, hipGetErrorString(attr0 != hipSuccess ? attr0 : attr1));
+        // the epilogue switches are template arguments: one instantiation per (BN, ReLU, bias), index bn * 4 + relu * 2 + bias
+        using Pp3Kernel = void (*)(const float *, const float *, const float *, const float *, const float *, float *, int64_t, int, int,
+                                   int, int, int, int);
+        static const Pp3Kernel kernels[8] = {
+            linear_fwd_pp3_kernel<false, false, false>, linear_fwd_pp3_kernel<false, false, true>,
+            linear_fwd_pp3_kernel<false, true, false>,  linear_fwd_pp3_kernel<false, true, true>,
+            linear_fwd_pp3_kernel<true, false, false>,  linear_fwd_pp3_kernel<true, false, true>,
+            linear_fwd_pp3_kernel<true, true, false>,   linear_fwd_pp3_kernel<true, true, true>};
+        static const hipError_t attr = [] {
+            for (Pp3Kernel k : kernels)
+                if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3))
+                    return e;
+            return hipSuccess;
+        }();
+        if (attr != hipSuccess) return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds3, hipGetErrorString(attr));
         const int total = (int)g.grid;                   // virtual tiles (the XCD-aware numbering has holes)
         const dim3 grid(pp_workgroups(PP_PERSISTENT, g.grid, cus));
-        hipLaunchKernelGGL(sc ? linear_fwd_pp3_kernel<true> : linear_fwd_pp3_kernel<false>, grid, dim3(512), lds3, stream, x, W, b, sc, sh, y,
-                           n, out_dim, in_dim, relu, g.bn_blocks, (int)g.bm_blocks, total, XCD_ORDER);
+        hipLaunchKernelGGL(kernels[(sc ? 4 : 0) + (relu ? 2 : 0) + (b ? 1 : 0)], grid, dim3(512), lds3, stream, x, W, b, sc, sh, y, n, out_dim,
+                           in_dim, g.bn_blocks, (int)g.bm_blocks, total, XCD_ORDER);
     } else {
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp2_kernel),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);

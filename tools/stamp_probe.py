@@ -7,6 +7,17 @@
 Stamps (s_memtime, shader cycles) of workgroup 8, lane 0 of every wave, first 64 phases:
   compute role: 0 = phase entry, 1 = before the mid-phase barrier, 2 = after it, 3 = all 64 MFMAs issued
   staging role: 0 = phase entry, 1 = LDS writes done (before the barrier), 2 = after the barrier
+
+Which phases those are.  The per-tile kernel (linear_fwd_pp2_kernel) stamps the 64 first phases of the workgroup's tile.  The
+persistent kernel (linear_fwd_pp3_kernel, LCREC_STAMP3) numbers its phases on across the tiles of the workgroup's list and
+keeps the first 64 of the LIST: at the default PROBE_K=2048 (64 K-tiles = 128 phases per tile) that is the first half of the
+workgroup's FIRST tile -- no pieces of a previous tile in its HEAD -- where this probe used to show the last tile written.
+
+    PROBE_K=768 PROBE_N=2048 LCREC_LIB_PATH=... python tools/stamp_probe.py --handover
+
+prints the hand-over instead (profiles/pp3_handover_stamps.txt): with 24 K-tiles = 48 phases per tile, phases 44..47 are
+TAIL0 / TAIL1 of the first tile, 48..49 HEAD0 of the second and 50..63 its piece phases; per phase the entry-to-entry
+length of waves 0 and 4, and per part of the tile the length of a K-tile (two phases) against a STEADY one.
 """
 import ctypes
 import os
@@ -17,6 +28,29 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lcrec_amd import _lib, ops  # noqa: E402
+
+
+def handover(s, k):
+    """Phase lengths around the hand-over from the first to the second tile of the workgroup's list (persistent kernel)."""
+    assert k == 768, "--handover reads the phase numbers of 24 K-tiles per tile: PROBE_K=768"
+    ent = s[:, :, 0]                       # phase entry of every wave
+    length = np.diff(ent, axis=1)          # phase p -> p + 1
+    print("phase lengths (entry to entry), waves 0 (group 0) and 4 (group 1); C = computes, S = stages")
+    for p in range(20, 63):
+        print(f"{p:3d}  w0 {'C' if p % 2 == 0 else 'S'} {int(length[0, p]):6d}   w4 {'C' if p % 2 == 1 else 'S'} {int(length[4, p]):6d}")
+
+    def per_ktile(lo, hi, wave):
+        return (ent[wave, hi] - ent[wave, lo]) / ((hi - lo) / 2)
+    print("per K-tile (two phases), wave 0 / wave 4:")
+    for name, lo, hi in (("STEADY  K-tiles 10..21 of tile 1", 20, 44), ("TAIL    K-tiles 22..23 of tile 1", 44, 48),
+                         ("HEAD0   K-tile 0 of tile 2      ", 48, 50), ("PIECES  K-tiles 1..6 of tile 2  ", 50, 62)):
+        print(f"  {name}: {per_ktile(lo, hi, 0):8.0f} {per_ktile(lo, hi, 4):8.0f}")
+    print("tile 1 phases 2..19 (HEAD without pieces, first tile): %.0f %.0f per K-tile" % (per_ktile(2, 20, 0), per_ktile(2, 20, 4)))
+    for wave, phases in ((0, (44, 46, 48, 50, 52, 54)), (4, (45, 47, 49, 51, 53, 55))):
+        for p in phases:
+            v = s[wave, p]
+            print(f"compute phase {p} wave {wave}: entry->barrier {int(v[1] - v[0])}  in barrier {int(v[2] - v[1])}  "
+                  f"barrier->64th MFMA {int(v[3] - v[2])}")
 
 
 def main():
@@ -35,6 +69,8 @@ def main():
     rc = lib.lcrec_debug_gemm_stamps(ctypes.cast(buf, ctypes.c_void_p))
     assert rc == 0, rc
     s = np.frombuffer(buf, dtype=np.uint64).reshape(8, 64, 4).astype(np.int64)
+    if "--handover" in sys.argv[1:]:
+        return handover(s, k)
     t0 = s[:, 8, 0].min()
     print("phase | wave0 (group 0)                       | wave4 (group 1)        [cycles since phase 8 entry]")
     for p in range(int(os.environ.get("PROBE_P0", "8")), 24):

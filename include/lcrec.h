@@ -830,12 +830,14 @@ typedef struct {
 } lcrec_step_tail_plan;
 int lcrec_debug_step_tail_plan(int call, int64_t n_or_count, int width, int aligned, lcrec_step_tail_plan *out);
 
-/* The launches of lcrec_linear_backward, lcrec_linear_backward_weights and lcrec_linear_bn_forward (csrc/gemm_f32.hip): each
- * entry point decides its launches with one pure host function; the launch code launches by it and the debug exports below
- * report it.  Host only: nothing is launched, no device is needed.  One lcrec_gemm_launch per kernel launch. */
+/* The launches of lcrec_linear_forward, lcrec_linear_backward, lcrec_linear_backward_weights and lcrec_linear_bn_forward
+ * (csrc/gemm_f32.hip): each entry point decides its launches with one pure host function; the launch code launches by it and the
+ * debug exports below report it.  Host only: nothing is launched, no device is needed.  One lcrec_gemm_launch per kernel launch.
+ * The debug plan records are not part of the versioned surface: fields are added at the end without a new LCREC_ABI_VERSION. */
 enum { LCREC_GEMMK_TILE_BODY = 0,   /* linear_tile_body: linear_fwd_kernel / linear_train_fwd_kernel / linear_dw_grouped_kernel */
        LCREC_GEMMK_32x64,           /* linear_s16_kernel */
-       LCREC_GEMMK_REDUCER };       /* splitk_reduce_kernel / splitk_reduce_grouped_kernel */
+       LCREC_GEMMK_REDUCER,         /* splitk_reduce_kernel / splitk_reduce_grouped_kernel */
+       LCREC_GEMMK_PP };            /* the ping-pong kernels: linear_fwd_pp2_kernel / linear_fwd_pp3_kernel (`form`) */
 enum { LCREC_GEMMR_DX = 0, LCREC_GEMMR_DW, LCREC_GEMMR_REDUCE, LCREC_GEMMR_FORWARD };
 typedef struct {
     const char *label;        /* the trace label the launch is counted under (a reducer runs inside its product's bracket) */
@@ -863,7 +865,21 @@ typedef struct {
     int chunk_row_tiles;      /* stats: row tiles per merge chunk (CH); else 0 */
     int chunks;               /* stats: merge chunks, ceil(row tiles / CH); else 0 */
     int64_t total4;           /* reducer: float4 sums */
+    /* lcrec_linear_forward only (else 0) */
+    int64_t row0;             /* the first row of the call this launch covers: rows row0 .. row0 + m */
+    int form;                 /* 0: not a ping-pong launch, 2: per-tile (linear_fwd_pp2_kernel), 3: persistent (linear_fwd_pp3_kernel) */
+    /* persistent form only (else 0) */
+    int steady_iterations;    /* STEADY iterations per tile */
+    int list_min, list_max;   /* shortest and longest tile list of a workgroup */
+    int empty_workgroups;     /* workgroups with no tile */
+    int single_tile_workgroups; /* ... and with exactly one */
+    int ragged_handed_over;   /* tiles of a ragged last row panel that are NOT the last of their list (their partial row count goes
+                               * through the hand-over to the next tile's K loop instead of through finish()) */
 } lcrec_gemm_launch;
+/* The launches lcrec_linear_forward makes for [n][in_dim] -> [n][out_dim] on a device of `cus` compute units, in order, into
+ * out[0 .. capacity), capacity >= 4.  Returns the count (0 for n = 0) or a negative code for a shape lcrec_linear_forward refuses;
+ * unlike the three below it then leaves lcrec_last_error() as it was. */
+int lcrec_debug_linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcrec_gemm_launch *out, int capacity);
 /* out[0 .. capacity), capacity >= 3: the dX launch (want_gx), the dW launch and its reducer (want_gw, S > 1), in launch order.
  * Returns the count or a negative code for a shape lcrec_linear_backward refuses. */
 int lcrec_debug_linear_backward_plan(int64_t n, int in_dim, int out_dim, int want_gx, int want_gw, lcrec_gemm_launch *out, int capacity);

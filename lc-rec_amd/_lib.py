@@ -133,6 +133,7 @@ _SIGNATURES = {
                                              _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "lcrec_debug_bn_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
     "lcrec_debug_step_tail_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
+    "lcrec_debug_linear_forward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "lcrec_debug_linear_backward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                                         ctypes.c_int]),
     "lcrec_debug_linear_backward_weights_plan": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -189,7 +190,9 @@ class GemmLaunch(ctypes.Structure):
                 ("k_tiles_per_run", ctypes.c_int), ("k_tiles_last_run", ctypes.c_int), ("last_k_valid", ctypes.c_int),
                 ("tiles", ctypes.c_int), ("virtual_tiles", ctypes.c_int), ("workgroups", ctypes.c_int), ("wg_start", ctypes.c_int),
                 ("last_panel_rows", ctypes.c_int), ("last_tile_cols", ctypes.c_int), ("vector_stores", ctypes.c_int),
-                ("chunk_row_tiles", ctypes.c_int), ("chunks", ctypes.c_int), ("total4", ctypes.c_int64)]
+                ("chunk_row_tiles", ctypes.c_int), ("chunks", ctypes.c_int), ("total4", ctypes.c_int64), ("row0", ctypes.c_int64),
+                ("form", ctypes.c_int), ("steady_iterations", ctypes.c_int), ("list_min", ctypes.c_int), ("list_max", ctypes.c_int),
+                ("empty_workgroups", ctypes.c_int), ("single_tile_workgroups", ctypes.c_int), ("ragged_handed_over", ctypes.c_int)]
 
 
 class TraceEntry(ctypes.Structure):

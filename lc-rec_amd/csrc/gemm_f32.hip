@@ -1746,33 +1746,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
     reinterpret_cast<f32x4 *>(out)[q] = acc;
 }
 
-// One launch of lcrec_debug_linear_forward_plan (below; a debug export, so the struct lives here and not in include/lcrec.h).
-}  // namespace lcrec
-extern "C" struct lcrec_debug_forward_launch {
-    int64_t row0, rows;        // the rows of the call this launch covers
-    const char *label;         // its name in the launch trace
-    int form;                  // 0: not a ping-pong launch, 2: per-tile (linear_fwd_pp2_kernel), 3: persistent (linear_fwd_pp3_kernel)
-    int tile_rows, tile_cols;  // the workgroup tile
-    int k_tiles;               // K-tiles of 32 per output tile
-    int tiles, virtual_tiles;  // real tiles, and the numbering's extent (row panels padded to the 8 XCDs: the rest are holes)
-    int workgroups;            // grid size
-    int last_panel_rows;       // valid rows of the last row panel (tile_rows: not ragged)
-    // persistent form only (else 0): STEADY iterations per tile; shortest and longest tile list; workgroups with no tile
-    // and with exactly one; tiles of a ragged last row panel that are NOT the last of their list (their partial row count
-    // goes through the hand-over to the next tile's K loop instead of through finish())
-    int steady_iterations, list_min, list_max, empty_workgroups, single_tile_workgroups, ragged_handed_over;
-};
-// The same record extended at its end (lcrec_debug_linear_forward_plan_ext).  The first export keeps writing records of the
-// first size: a caller built against it owns a buffer of those.
-extern "C" struct lcrec_debug_forward_launch_ext {
-    lcrec_debug_forward_launch base;
-    int fast;                  // buffer-load staging (the two ping-pong kernels and the 32 x 64 kernel have no other)
-    int register_buffered;     // generic kernel: the DB form of linear_tile_body (k_tile_rb); 32 x 64 kernel: 1; ping-pong: 0
-};
-namespace lcrec {
-
-// ---- Launch side: which kernel a shape gets.  Top to bottom: knobs, tile table, choosers, grid helper, launches, entry
-// points.  Every kernel gives the same bits for a given product; the one choice that changes bits is S, the K-runs of a
+// ---- Launch side: which kernel a shape gets.  Top to bottom: knobs, tile table, choosers, grid helper, the step (one launch as a
+// pure decision) with its builders and describe_step(), one launcher per kernel family, entry points -- each a step builder,
+// the call that launches its steps and the plan that describes them -- and the debug exports.
+// Every kernel gives the same bits for a given product; the one choice that changes bits is S, the K-runs of a
 // weight gradient (linear_backward_splits).  bench.py replays the forward rule (pp_fits, pp_head_rows,
 // forward_tile_shape) to attribute flops, and tests/test_gpu_kernels.py pins the trace labels at its boundaries.
 // Two knobs were retired on their measurements: LCREC_GEMM_TUNE=0 (XCD-aware tile order off; only the forward launches
@@ -1886,6 +1863,46 @@ static int64_t pp_head_rows(int64_t n, int out_dim)
     return 0;
 }
 
+// The two ping-pong kernels: which form, how many workgroups (decided in pp_step() and nowhere else).
+enum PpForm { PP_NONE = 0, PP_PER_TILE = 2, PP_PERSISTENT = 3 };      // linear_fwd_pp2_kernel / linear_fwd_pp3_kernel
+constexpr int PP_BM = 256, PP_BN = 128;
+// K-tiles of a tile that linear_fwd_pp3_kernel spends outside its STEADY loop: HEAD (0..9) and TAIL (the last two).  At the
+// smallest admitted K (12 K-tiles = 384) the STEADY loop is therefore empty; it runs (K / 32 - 12) / 2 times per tile.
+constexpr int PP3_HEAD_KTILES = 10, PP3_TAIL_KTILES = 2;
+// the persistent form where it applies (measured +1.2 % on C3, +0.5 .. +3.4 % per layer)
+static PpForm pp_form(int in_dim, int out_dim)
+{
+    return knobs().pp3 && in_dim % 64 == 0 && in_dim >= (PP3_HEAD_KTILES + PP3_TAIL_KTILES) * BK && out_dim % 128 == 0 &&
+                   (int64_t)out_dim * 4 * 128 < (1ll << 31)
+               ? PP_PERSISTENT : PP_PER_TILE;
+}
+// the persistent form's workgroup count: one per CU, the CU count rounded down to a multiple of 8 (that keeps a
+// workgroup's tiles on its own XCD), and never more than there are (virtual) tiles -- each workgroup walks total / grid of them
+static int pp3_usable_cus(int device_cus) { return device_cus > 8 ? device_cus / 8 * 8 : 8; }
+static unsigned pp_workgroups(PpForm form, unsigned virtual_tiles, int cus)
+{
+    if (form == PP_PER_TILE) return virtual_tiles;
+    const unsigned usable = (unsigned)pp3_usable_cus(cus);
+    return virtual_tiles < usable ? virtual_tiles : usable;
+}
+// the CU count of the current device, asked once per process and only when a persistent launch is first planned for it
+constexpr int DEVICE_CUS = 0;           // the `cus` of forward_steps() / pp_step() that stands for it
+static int device_cus()
+{
+    static const int cus = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
+        return v;
+    }();
+    return cus;
+}
+
+// K % 32 == 0 (every layer of the run.sh architecture): the row-major instantiation whose staging path has no VALU
+static bool forward_fast(int in_dim, int tile_rows)
+{
+    return knobs().fast && in_dim % BK == 0 && (int64_t)in_dim * 4 * (tile_rows + 64) < (1ll << 31);
+}
+
 // ---- the grid of an [M][N] output in bm x bn tiles.  xcd_padded: the row-panel count rounded up to the 8 XCDs, which the
 // XCD-aware tile numbering needs (it has holes, see linear_tile_body).  Fails when the grid does not fit a launch.
 struct TileGrid { int64_t bm_blocks; int bn_blocks; unsigned grid; };
@@ -1899,10 +1916,10 @@ static int tile_grid(TileGrid &g, const char *who, int64_t M, int N, int bm, int
     return LCREC_OK;
 }
 
-// ---- one launch of the generic kernels, the 32 x 64 kernel or a split-K reducer as a pure decision (no HIP call): which
-// instantiation, which grid, how K is cut.  The entry points below build these (backward_steps, dw_group_steps,
-// train_fwd_step), the launch_* functions launch what they say, and describe_step() turns them into the lcrec_gemm_launch
-// records of the debug exports; neither side restates the other.
+// ---- one launch of the generic kernels, the 32 x 64 kernel, a ping-pong kernel or a split-K reducer as a pure decision: which
+// instantiation, which grid, how K is cut.  The entry points below build these (forward_steps, backward_steps,
+// dw_group_steps, train_fwd_step), the launch_* functions launch what they say, and describe_step() turns them into the
+// lcrec_gemm_launch records of the debug exports; neither side restates the other.
 struct GemmStep {
     int role, family;           // LCREC_GEMMR_* / LCREC_GEMMK_*
     KernelId label;
@@ -1910,11 +1927,14 @@ struct GemmStep {
     bool fast, ta, tb;          // tb is also linear_s16_kernel's template switch
     int pro;
     bool stats;
+    int64_t row0;               // forward: the first row of the call this launch takes (its M rows are row0 .. row0 + M)
     int64_t M;                  // the output is [M][N], contracted over K
     int N, K;
     int splits;                 // K-runs, >= 1 (gridDim.y of a plain launch); reducer: the partial products it adds
     int per;                    // the kernel's kt_per_split argument: K-tiles per run, 1 << 30 for one run
-    TileGrid g;                 // reducer: grid = workgroups, the blocks are 0
+    TileGrid g;                 // reducer: grid = workgroups, the blocks are 0; ping-pong: grid = the virtual tiles
+    PpForm form;                // ping-pong only
+    unsigned workgroups;        // ping-pong only: the launch's grid (the others launch g.grid x splits)
     unsigned wg_start;          // grouped launches: first workgroup of the problem
     int64_t total4;             // reducer: float4 sums
 };
@@ -1942,6 +1962,18 @@ static int s16_step(GemmStep &s, int role, bool kmajor_w, int64_t M, int N, int 
     return tile_grid(s.g, "linear (32 x 64 tiles)", M, N, S16_BM, S16_BN, false);
 }
 
+// a ping-pong launch of lcrec_linear_forward on a device of `cus` compute units (DEVICE_CUS: the current one's)
+static int pp_step(GemmStep &s, int64_t M, int N, int K, int cus)
+{
+    s = GemmStep{};
+    s.role = LCREC_GEMMR_FORWARD; s.family = LCREC_GEMMK_PP; s.label = K_LINEAR_PP; s.fast = true;
+    s.M = M; s.N = N; s.K = K; s.splits = 1; s.per = 1 << 30;
+    if (int rc = tile_grid(s.g, "linear_forward", M, N, PP_BM, PP_BN, XCD_ORDER)) return rc;
+    s.form = pp_form(K, N);
+    s.workgroups = pp_workgroups(s.form, s.g.grid, s.form == PP_PERSISTENT && cus == DEVICE_CUS ? device_cus() : cus);
+    return LCREC_OK;
+}
+
 // the ordered sum of `product`'s K-runs; it runs inside the product's trace bracket, hence under its label
 static void reduce_step(GemmStep &s, const GemmStep &product)
 {
@@ -1952,21 +1984,47 @@ static void reduce_step(GemmStep &s, const GemmStep &product)
     s.g.grid = (unsigned)((s.total4 + 255) / 256);
 }
 
+// The tile lists of a persistent ping-pong launch, walked as linear_fwd_pp3_kernel's tile_of() / next_tile() walk them (device
+// code: restated, with the arguments the launch passes).  For describe_step() alone: a launch never runs it.
+static void describe_tile_lists(const GemmStep &s, lcrec_gemm_launch &o)
+{
+    o.steady_iterations = (o.k_tiles - PP3_HEAD_KTILES - PP3_TAIL_KTILES) / 2;
+    o.list_min = o.tiles;
+    for (int wg = 0; wg < o.workgroups; ++wg) {
+        int len = 0, ragged = 0;             // ragged: ragged-panel tiles in this list; last_ragged: is its last tile one
+        bool last_ragged = false;
+        for (int64_t t = wg; t < s.g.grid; t += o.workgroups) {
+            const int xcd = (int)(t & 7);
+            const int64_t j = t >> 3, panels = (s.g.bm_blocks - xcd + 7) >> 3;
+            if (j >= panels * s.g.bn_blocks) continue;                       // a hole
+            last_ragged = o.last_panel_rows < PP_BM && j / s.g.bn_blocks * 8 + xcd == s.g.bm_blocks - 1;
+            ragged += last_ragged;
+            ++len;
+        }
+        if (len < o.list_min) o.list_min = len;
+        if (len > o.list_max) o.list_max = len;
+        o.empty_workgroups += len == 0;
+        o.single_tile_workgroups += len == 1;
+        o.ragged_handed_over += ragged - (last_ragged ? 1 : 0);
+    }
+}
+
 static void describe_step(const GemmStep &s, lcrec_gemm_launch &o)
 {
     memset(&o, 0, sizeof o);
     o.label = kKernelNames[s.label];
     o.role = s.role; o.family = s.family;
-    o.m = s.M; o.n = s.N; o.k = s.K;
+    o.row0 = s.row0; o.m = s.M; o.n = s.N; o.k = s.K;
     o.runs = s.splits;
-    o.workgroups = (int)s.g.grid * (s.family == LCREC_GEMMK_REDUCER ? 1 : s.splits);
+    o.workgroups = s.family == LCREC_GEMMK_PP ? (int)s.workgroups : (int)s.g.grid * (s.family == LCREC_GEMMK_REDUCER ? 1 : s.splits);
     o.wg_start = (int)s.wg_start;
     o.vector_stores = s.N % 4 == 0;
     if (s.family == LCREC_GEMMK_REDUCER) { o.total4 = s.total4; return; }
-    const TileDims d = s.family == LCREC_GEMMK_32x64 ? TileDims{S16_BM, S16_BN} : tile_dims(s.shape);
+    const bool body = s.family == LCREC_GEMMK_TILE_BODY;
+    const TileDims d = body ? tile_dims(s.shape) : s.family == LCREC_GEMMK_PP ? TileDims{PP_BM, PP_BN} : TileDims{S16_BM, S16_BN};
     o.tile_rows = d.bm; o.tile_cols = d.bn;
     o.fast = s.fast; o.a_kmajor = s.ta; o.w_kmajor = s.tb; o.pro = s.pro; o.stats = s.stats;
-    o.register_buffered = s.family == LCREC_GEMMK_32x64 || (s.fast && with_tile(s.shape, [](auto tile) { return decltype(tile)::RB; }));
+    o.register_buffered = s.family == LCREC_GEMMK_32x64 || (body && s.fast && with_tile(s.shape, [](auto tile) { return decltype(tile)::RB; }));
     // the runs as the kernel cuts them: run r takes K-tiles [r * per, min((r + 1) * per, all))
     o.k_tiles = (s.K + BK - 1) / BK;
     o.k_tiles_per_run = s.per < o.k_tiles ? s.per : o.k_tiles;
@@ -1976,6 +2034,8 @@ static void describe_step(const GemmStep &s, lcrec_gemm_launch &o)
     o.virtual_tiles = (int)s.g.grid;
     o.last_panel_rows = (int)(s.M - (s.g.bm_blocks - 1) * d.bm);
     o.last_tile_cols = s.N - (s.g.bn_blocks - 1) * d.bn;
+    o.form = s.form;
+    if (s.form == PP_PERSISTENT) describe_tile_lists(s, o);
     if (s.stats) {
         o.chunk_row_tiles = with_tile(s.shape, [](auto tile) { return decltype(tile)::STATS_CHUNK; });
         o.chunks = (int)((s.g.bm_blocks + o.chunk_row_tiles - 1) / o.chunk_row_tiles);
@@ -1992,43 +2052,13 @@ static int launch_s16(const GemmStep &s, const float *A, const float *W, const f
     return check_launch("linear_s16_kernel");
 }
 
-// ---- the ping-pong launch as a pure decision: which form, how many workgroups.  launch_linear_pp() launches what these
-// say and lcrec_debug_linear_forward_plan() reports it; neither restates the other.
-enum PpForm { PP_PER_TILE = 2, PP_PERSISTENT = 3 };      // linear_fwd_pp2_kernel / linear_fwd_pp3_kernel
-// K-tiles of a tile that linear_fwd_pp3_kernel spends outside its STEADY loop: HEAD (0..9) and TAIL (the last two).  At the
-// smallest admitted K (12 K-tiles = 384) the STEADY loop is therefore empty; it runs (K / 32 - 12) / 2 times per tile.
-constexpr int PP3_HEAD_KTILES = 10, PP3_TAIL_KTILES = 2;
-// the persistent form where it applies (measured +1.2 % on C3, +0.5 .. +3.4 % per layer)
-static PpForm pp_form(int in_dim, int out_dim)
-{
-    return knobs().pp3 && in_dim % 64 == 0 && in_dim >= (PP3_HEAD_KTILES + PP3_TAIL_KTILES) * BK && out_dim % 128 == 0 &&
-                   (int64_t)out_dim * 4 * 128 < (1ll << 31)
-               ? PP_PERSISTENT : PP_PER_TILE;
-}
-// the persistent form's workgroup count: one per CU, the CU count rounded down to a multiple of 8 (that keeps a
-// workgroup's tiles on its own XCD), and never more than there are (virtual) tiles -- each workgroup walks total / grid of them
-static int pp3_usable_cus(int device_cus) { return device_cus > 8 ? device_cus / 8 * 8 : 8; }
-static unsigned pp_workgroups(PpForm form, unsigned virtual_tiles, int cus)
-{
-    if (form == PP_PER_TILE) return virtual_tiles;
-    const unsigned usable = (unsigned)pp3_usable_cus(cus);
-    return virtual_tiles < usable ? virtual_tiles : usable;
-}
-
-static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *W, const float *b, const float *sc,
-                            const float *sh, int relu, int out_dim, float *y, hipStream_t stream)
+static int launch_linear_pp(const GemmStep &s, const float *x, const float *W, const float *b, const float *sc, const float *sh,
+                            int relu, float *y, hipStream_t stream)
 {
     constexpr size_t lds2 = (size_t)(2 * 128 + 2 * 128) * (BK + 4) * sizeof(float);            // 73 728 B
     constexpr size_t lds3 = (size_t)(2 * 128 + 2 * 128 + 8 * 32) * LDK * sizeof(float);        // 110 592 B
-    TileGrid g;
-    if (int rc = tile_grid(g, "linear_forward", n, out_dim, 256, 128, XCD_ORDER)) return rc;
-    TraceScope trace(K_LINEAR_PP, stream);
-    if (pp_form(in_dim, out_dim) == PP_PERSISTENT) {
-        static const int cus = [] {
-            int dev = 0, v = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
-            return v;
-        }();
+    TraceScope trace(s.label, stream);
+    if (s.form == PP_PERSISTENT) {
         // the epilogue switches are template arguments: one instantiation per (BN, ReLU, bias), index bn * 4 + relu * 2 + bias
         using Pp3Kernel = void (*)(const float *, const float *, const float *, const float *, const float *, float *, int64_t, int, int,
                                    int, int, int, int);
@@ -2044,61 +2074,41 @@ static int launch_linear_pp(const float *x, int64_t n, int in_dim, const float *
             return hipSuccess;
         }();
         if (attr != hipSuccess) return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds3, hipGetErrorString(attr));
-        const int total = (int)g.grid;                   // virtual tiles (the XCD-aware numbering has holes)
-        const dim3 grid(pp_workgroups(PP_PERSISTENT, g.grid, cus));
-        hipLaunchKernelGGL(kernels[(sc ? 4 : 0) + (relu ? 2 : 0) + (b ? 1 : 0)], grid, dim3(512), lds3, stream, x, W, b, sc, sh, y, n, out_dim,
-                           in_dim, g.bn_blocks, (int)g.bm_blocks, total, XCD_ORDER);
-    } else {
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp2_kernel),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        if (attr != hipSuccess) return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds2, hipGetErrorString(attr));
-        hipLaunchKernelGGL(linear_fwd_pp2_kernel, dim3(pp_workgroups(PP_PER_TILE, g.grid, 0)), dim3(512), lds2, stream, x, W, b, sc, sh, y, n,
-                           out_dim, in_dim, relu, g.bn_blocks, (int)g.bm_blocks, XCD_ORDER);
+        hipLaunchKernelGGL(kernels[(sc ? 4 : 0) + (relu ? 2 : 0) + (b ? 1 : 0)], dim3(s.workgroups), dim3(512), lds3, stream, x, W, b, sc, sh, y,
+                           s.M, s.N, s.K, s.g.bn_blocks, (int)s.g.bm_blocks, (int)s.g.grid, XCD_ORDER);
+        return check_launch("linear_fwd_pp3_kernel");
     }
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_fwd_pp2_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+    if (attr != hipSuccess) return fail(LCREC_EHIP, "linear_forward: hipFuncSetAttribute(%zu): %s", lds2, hipGetErrorString(attr));
+    hipLaunchKernelGGL(linear_fwd_pp2_kernel, dim3(s.workgroups), dim3(512), lds2, stream, x, W, b, sc, sh, y, s.M, s.N, s.K, relu,
+                       s.g.bn_blocks, (int)s.g.bm_blocks, XCD_ORDER);
     return check_launch("linear_fwd_pp2_kernel");
 }
 
-// K % 32 == 0 (every layer of the run.sh architecture): the row-major instantiation whose staging path has no VALU
-static bool forward_fast(int in_dim, int tile_rows)
-{
-    return knobs().fast && in_dim % BK == 0 && (int64_t)in_dim * 4 * (tile_rows + 64) < (1ll << 31);
-}
-
-template <class T>
-static int launch_linear(T, const float *x, int64_t n, int in_dim, const float *W, const float *b, const float *sc, const float *sh,
-                         int relu, int out_dim, float *y, hipStream_t stream)
-{
-    TileGrid g;
-    if (int rc = tile_grid(g, "linear_forward", n, out_dim, T::BM, T::BN, XCD_ORDER)) return rc;
-    TraceScope trace(T::LABEL, stream);
-    const bool fast = forward_fast(in_dim, T::BM);
-    const auto kernel = fast ? linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true> : linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, false>;
-    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, stream, x, W, b, sc, sh, y, n, out_dim, in_dim, relu, g.bn_blocks,
-                       (int)g.bm_blocks, XCD_ORDER, 1 << 30, (int64_t)0);
-    return check_launch("linear_fwd_kernel");
-}
-
-// C[M][N] = A * B with A given [M][K] (TA false) or [K][M] (TA true) and B given [K][N] (always k-major here):
-// the two backward products of a Linear layer.  `splits` > 1 cuts K into that many runs of K-tiles whose partial
-// products go to `partial` [splits][M][N].
-// `s` is a product step: its splits > 1 cut K into that many runs of K-tiles whose partial products go to `partial`
-// [splits][M][N]; `reduce` (then given) adds them into C in the same trace bracket.
-static int launch_kmajor(const GemmStep &s, const GemmStep *reduce, const float *A, const float *B, float *C, float *partial,
-                         hipStream_t stream)
+// linear_fwd_kernel as a tile-body step says: C[M][N] = A * B with the epilogue b / sc / sh / relu.  Four instantiations per
+// tile are built: both operands row-major with guarded or fast staging (the forward), and fast staging with B given [K][N] and
+// A given [M][K] or [K][M] (the two backward products of a Linear layer, which pass no epilogue).  splits > 1 cut K into that
+// many runs of K-tiles whose partial products go to `partial` [splits][M][N]; `reduce` (then given) adds them into C in the
+// same trace bracket.
+static int launch_tile(const GemmStep &s, const GemmStep *reduce, const float *A, const float *B, const float *b, const float *sc,
+                       const float *sh, int relu, float *C, float *partial, hipStream_t stream)
 {
     TraceScope trace(s.label, stream);
-    with_tile(s.shape, [&](auto tile) {
+    // (the k-major pair of every tile is named before the row-major pairs: the code object lists kernels as they are first named)
+    const auto kernel = s.tb ? with_tile(s.shape, [&](auto tile) {
         using T = decltype(tile);
-        const auto kernel = s.ta ? linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, true, true>
-                                 : linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, false, true>;
-        hipLaunchKernelGGL(kernel, dim3(s.g.grid, (unsigned)s.splits), dim3(256), 0, stream, A, B, (const float *)nullptr,
-                           (const float *)nullptr, (const float *)nullptr, s.splits > 1 ? partial : C, s.M, s.N, s.K, 0, s.g.bn_blocks,
-                           (int)s.g.bm_blocks, XCD_ORDER, s.per, s.splits > 1 ? s.M * (int64_t)s.N : (int64_t)0);
-        return 0;
+        return s.ta ? linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, true, true>
+                    : linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true, false, true>;
+    }) : with_tile(s.shape, [&](auto tile) {
+        using T = decltype(tile);
+        return s.fast ? linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, true> : linear_fwd_kernel<T::WAVES_M, T::WAVES_N, T::TM, T::TN, false>;
     });
+    hipLaunchKernelGGL(kernel, dim3(s.g.grid, (unsigned)s.splits), dim3(256), 0, stream, A, B, b, sc, sh, s.splits > 1 ? partial : C, s.M, s.N,
+                       s.K, relu, s.g.bn_blocks, (int)s.g.bm_blocks, XCD_ORDER, s.per, s.splits > 1 ? s.M * (int64_t)s.N : (int64_t)0);
     if (reduce)
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(reduce->g.grid), dim3(256), 0, stream, partial, reduce->splits, reduce->total4, C);
-    return check_launch("linear_fwd_kernel (k-major operands)");
+    return check_launch(s.tb ? "linear_fwd_kernel (k-major operands)" : "linear_fwd_kernel");
 }
 
 static int launch_train_fwd(const GemmStep &s, const float *x, const float *W, const float *b, float *t, const TileExtras &ex,
@@ -2121,35 +2131,40 @@ static int launch_train_fwd(const GemmStep &s, const float *x, const float *W, c
 }
 
 // ---- entry points
-// What lcrec_linear_forward launches for a shape, as a pure step (no HIP call): row ranges in order, each with the
-// kernel family that takes it.  linear_forward() launches exactly these; lcrec_debug_linear_forward_plan() reports them.
-enum FwdKind { FWD_PP, FWD_S16, FWD_TILE };
-struct FwdStep { int64_t row0, rows; FwdKind kind; TileShape shape; };      // shape: FWD_TILE only
+// What lcrec_linear_forward launches for a shape (n > 0) on a device of `cus` compute units (DEVICE_CUS: the current one's, asked
+// only when a step is a persistent ping-pong launch), as pure steps: row ranges in order, each with the kernel that takes it.
+// Shapes the entry point refuses come back as its code, the last-error text set.  linear_forward() launches exactly these;
+// lcrec_debug_linear_forward_plan() reports them.
 constexpr int FWD_MAX_STEPS = 4;       // (a ping-pong head and its tail are two; a tail is below one round and is never cut again)
-static int forward_steps(int64_t n, int in_dim, int out_dim, FwdStep *steps)
+static int forward_steps(int64_t n, int in_dim, int out_dim, int cus, GemmStep *steps, int *count)
 {
+    *count = 0;
+    if (n < 0 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_forward: bad shape");
+    if (in_dim % 8 != 0) return fail(LCREC_EUNSUPPORTED, "linear_forward: in_dim=%d is not a multiple of 8", in_dim);
     const int pp = knobs().pp;
     const bool pp_ok = out_dim > 64 && in_dim % BK == 0 && (int64_t)in_dim * 4 * 192 < (1ll << 31);     // else the other kernels
-    int count = 0;
-    int64_t row0 = 0;
-    while (n > 0) {
-        const int64_t head = pp_ok && pp == -1 && count + 1 < FWD_MAX_STEPS ? pp_head_rows(n, out_dim) : 0;
-        if (head) {
-            steps[count++] = FwdStep{row0, head, FWD_PP, TILE_64x64};
-            row0 += head;
-            n -= head;
-            continue;
-        }
-        if (pp_ok && (pp == 1 || (pp == -1 && pp_fits(n, out_dim))))
-            steps[count++] = FwdStep{row0, n, FWD_PP, TILE_64x64};
+    for (int64_t row0 = 0; n > 0;) {
+        GemmStep &s = steps[*count];
+        const int64_t head = pp_ok && pp == -1 && *count + 1 < FWD_MAX_STEPS ? pp_head_rows(n, out_dim) : 0;
+        const int64_t rows = head ? head : n;
+        int rc;
+        if (head || (pp_ok && (pp == 1 || (pp == -1 && pp_fits(n, out_dim)))))
+            rc = pp_step(s, rows, out_dim, in_dim, cus);
         // launches that 64 x 64 tiles cannot fill the chip with: 32 x 64 tiles on the 16 x 16 x 4 MFMA (linear_s16_kernel)
         else if (use_s16_tiles(n, out_dim, in_dim))
-            steps[count++] = FwdStep{row0, n, FWD_S16, TILE_64x64};
-        else
-            steps[count++] = FwdStep{row0, n, FWD_TILE, forward_tile_shape(n, out_dim)};
-        break;
+            rc = s16_step(s, LCREC_GEMMR_FORWARD, false, n, out_dim, in_dim);
+        else {
+            const TileShape shape = forward_tile_shape(n, out_dim);
+            rc = tile_step(s, "linear_forward", LCREC_GEMMR_FORWARD, shape, forward_fast(in_dim, tile_dims(shape).bm), false, false, 0, false,
+                           n, out_dim, in_dim, 1);
+        }
+        if (rc) return rc;
+        s.row0 = row0;
+        ++*count;
+        row0 += rows;
+        n -= rows;
     }
-    return count;
+    return LCREC_OK;
 }
 
 int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const float *b,
@@ -2158,92 +2173,37 @@ int linear_forward(const float *x, int64_t n, int in_dim, const float *W, const 
 {
     if (n == 0) return LCREC_OK;                       // empty batch: nothing to read or write
     if (!x || !W || !y) return fail(LCREC_EINVAL, "linear_forward: NULL pointer");
-    if (n < 0 || in_dim <= 0 || out_dim <= 0) return fail(LCREC_EINVAL, "linear_forward: bad shape");
     if ((bn_scale == nullptr) != (bn_shift == nullptr))
         return fail(LCREC_EINVAL, "linear_forward: bn_scale and bn_shift must both be given or both NULL");
-    if (in_dim % 8 != 0)
-        return fail(LCREC_EUNSUPPORTED, "linear_forward: in_dim=%d is not a multiple of 8", in_dim);
     if (((uintptr_t)x | (uintptr_t)W) & 15)
         return fail(LCREC_EINVAL, "linear_forward: x and W must be 16-byte aligned");
-    FwdStep steps[FWD_MAX_STEPS];
-    const int count = forward_steps(n, in_dim, out_dim, steps);
+    GemmStep steps[FWD_MAX_STEPS];
+    int count = 0;
+    if (int rc = forward_steps(n, in_dim, out_dim, DEVICE_CUS, steps, &count)) return rc;
     for (int i = 0; i < count; ++i) {
-        const FwdStep &s = steps[i];
+        const GemmStep &s = steps[i];
         const float *xs = x + s.row0 * in_dim;
         float *ys = y + s.row0 * out_dim;
-        int rc;
-        if (s.kind == FWD_PP)
-            rc = launch_linear_pp(xs, s.rows, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, ys, stream);
-        else if (s.kind == FWD_S16) {
-            GemmStep step;
-            rc = s16_step(step, LCREC_GEMMR_FORWARD, false, s.rows, out_dim, in_dim);
-            if (!rc) rc = launch_s16(step, xs, W, b, bn_scale, bn_shift, relu, ys, stream);
-        } else
-            rc = with_tile(s.shape, [&](auto tile) { return launch_linear(tile, xs, s.rows, in_dim, W, b, bn_scale, bn_shift, relu, out_dim, ys, stream); });
+        const int rc = s.family == LCREC_GEMMK_PP      ? launch_linear_pp(s, xs, W, b, bn_scale, bn_shift, relu, ys, stream)
+                       : s.family == LCREC_GEMMK_32x64 ? launch_s16(s, xs, W, b, bn_scale, bn_shift, relu, ys, stream)
+                                                       : launch_tile(s, nullptr, xs, W, b, bn_scale, bn_shift, relu, ys, nullptr, stream);
         if (rc) return rc;
     }
     return LCREC_OK;
 }
 
-// The launches of linear_forward(n, in_dim, out_dim) on a device of `cus` compute units, for tests and tools: nothing is
-// launched and no HIP call is made.  Rows, label and form come from forward_steps(), pp_form() and pp_workgroups(), the
-// functions the launch path runs.  The tile lists of a persistent launch are walked here as linear_fwd_pp3_kernel's
-// tile_of() / next_tile() walk them (device code: restated, with the same arguments the launch passes).
-static int linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcrec_debug_forward_launch_ext *out, int capacity)
+static int linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcrec_gemm_launch *out, int capacity)
 {
+    // Unlike the other three plans, a refused question comes back as a plain code and leaves the thread's last-error text as it
+    // was: this export always did, and its callers ask it between calls whose text they still read.
     if (n == 0) return 0;
-    // (plain codes: a question about a launch does not touch the thread's last-error text)
     if (!out || capacity < FWD_MAX_STEPS || cus < 1) return LCREC_EINVAL;
-    if (n < 0 || in_dim <= 0 || out_dim <= 0) return LCREC_EINVAL;       // shapes linear_forward refuses
-    if (in_dim % 8 != 0) return LCREC_EUNSUPPORTED;
-    FwdStep steps[FWD_MAX_STEPS];
-    const int count = forward_steps(n, in_dim, out_dim, steps);
-    for (int i = 0; i < count; ++i) {
-        const FwdStep &s = steps[i];
-        memset(&out[i], 0, sizeof out[i]);
-        lcrec_debug_forward_launch &o = out[i].base;
-        o.row0 = s.row0;
-        o.rows = s.rows;
-        const TileDims d = s.kind == FWD_PP ? TileDims{256, 128} : s.kind == FWD_S16 ? TileDims{S16_BM, S16_BN} : tile_dims(s.shape);
-        const KernelId label = s.kind == FWD_PP    ? K_LINEAR_PP
-                               : s.kind == FWD_S16 ? K_LINEAR_32x64
-                                                   : with_tile(s.shape, [](auto tile) { return decltype(tile)::LABEL; });
-        o.label = kKernelNames[label];
-        o.tile_rows = d.bm;
-        o.tile_cols = d.bn;
-        o.k_tiles = (in_dim + BK - 1) / BK;
-        TileGrid g;
-        if (int rc = tile_grid(g, "linear_forward_plan", s.rows, out_dim, d.bm, d.bn, s.kind != FWD_S16)) return rc;
-        o.tiles = (int)(g.bm_blocks * g.bn_blocks);
-        o.virtual_tiles = (int)g.grid;
-        o.workgroups = (int)g.grid;
-        o.last_panel_rows = (int)(s.rows - (g.bm_blocks - 1) * d.bm);
-        out[i].fast = s.kind != FWD_TILE || forward_fast(in_dim, d.bm);
-        out[i].register_buffered = s.kind == FWD_S16 || (s.kind == FWD_TILE && out[i].fast && with_tile(s.shape, [](auto tile) { return decltype(tile)::RB; }));
-        if (s.kind != FWD_PP) continue;
-        o.form = pp_form(in_dim, out_dim);
-        o.workgroups = (int)pp_workgroups((PpForm)o.form, g.grid, cus);
-        if (o.form != PP_PERSISTENT) continue;
-        o.steady_iterations = (o.k_tiles - PP3_HEAD_KTILES - PP3_TAIL_KTILES) / 2;
-        o.list_min = o.tiles;
-        for (int wg = 0; wg < o.workgroups; ++wg) {
-            int len = 0, ragged = 0;             // ragged: ragged-panel tiles in this list; last_ragged: is its last tile one
-            bool last_ragged = false;
-            for (int64_t t = wg; t < g.grid; t += o.workgroups) {
-                const int xcd = (int)(t & 7);
-                const int64_t j = t >> 3, panels = (g.bm_blocks - xcd + 7) >> 3;
-                if (j >= panels * g.bn_blocks) continue;                       // a hole
-                last_ragged = o.last_panel_rows < d.bm && j / g.bn_blocks * 8 + xcd == g.bm_blocks - 1;
-                ragged += last_ragged;
-                ++len;
-            }
-            if (len < o.list_min) o.list_min = len;
-            if (len > o.list_max) o.list_max = len;
-            o.empty_workgroups += len == 0;
-            o.single_tile_workgroups += len == 1;
-            o.ragged_handed_over += ragged - (last_ragged ? 1 : 0);
-        }
-    }
+    GemmStep steps[FWD_MAX_STEPS];
+    int count = 0;
+    char kept[512];
+    snprintf(kept, sizeof kept, "%s", err_buf());
+    if (int rc = forward_steps(n, in_dim, out_dim, cus, steps, &count)) return fail(rc, "%s", kept);
+    for (int i = 0; i < count; ++i) describe_step(steps[i], out[i]);
     return count;
 }
 
@@ -2327,12 +2287,13 @@ int linear_backward(const float *gy, const float *x, const float *W, int64_t n, 
         int rc = LCREC_OK;
         if (s.role == LCREC_GEMMR_DX) {
             rc = s.family == LCREC_GEMMK_32x64 ? launch_s16(s, gy, W, nullptr, nullptr, nullptr, 0, gx, stream)
-                                               : launch_kmajor(s, nullptr, gy, W, gx, nullptr, stream);
+                                               : launch_tile(s, nullptr, gy, W, nullptr, nullptr, nullptr, 0, gx, nullptr, stream);
         } else if (s.role == LCREC_GEMMR_DW) {
             const size_t need = s.splits > 1 ? (size_t)s.splits * out_dim * in_dim * sizeof(float) : 0;
             if (need && (!workspace || workspace_bytes < need))
                 return fail(LCREC_EWORKSPACE, "linear_backward: workspace %zu B < required %zu B", workspace_bytes, need);
-            rc = launch_kmajor(s, s.splits > 1 ? &steps[i + 1] : nullptr, gy, x, gw, reinterpret_cast<float *>(workspace), stream);
+            rc = launch_tile(s, s.splits > 1 ? &steps[i + 1] : nullptr, gy, x, nullptr, nullptr, nullptr, 0, gw, reinterpret_cast<float *>(workspace),
+                             stream);
         }                                                      // (a reduce step is launched with its product)
         if (rc) return rc;
     }
@@ -2543,26 +2504,11 @@ static int linear_bn_forward_plan(int64_t n, int in_dim, int out_dim, int pro, i
 
 }  // namespace lcrec
 
-// Debug export (not in include/lcrec.h): the launches lcrec_linear_forward would make for [n][in_dim] -> [n][out_dim] on a
-// device of `cus` compute units, in order.  Host code only: it runs without a GPU.  Returns the number of launches written
-// to out[0 .. capacity) (capacity >= 4), or a negative LCREC_E* code.  tests/gemm_pp_cases.py holds the matching ctypes struct.
-extern "C" __attribute__((visibility("default"))) int lcrec_debug_linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus,
-                                                                                        lcrec_debug_forward_launch *out, int capacity)
-{
-    if (!out || capacity < lcrec::FWD_MAX_STEPS) return LCREC_EINVAL;
-    lcrec_debug_forward_launch_ext ext[lcrec::FWD_MAX_STEPS];
-    const int count = lcrec::linear_forward_plan(n, in_dim, out_dim, cus, ext, lcrec::FWD_MAX_STEPS);
-    for (int i = 0; i < count; ++i) out[i] = ext[i].base;
-    return count;
-}
-// The same with the extended records (tests/gemm_pp_cases.py holds the matching ctypes struct).
-extern "C" __attribute__((visibility("default"))) int lcrec_debug_linear_forward_plan_ext(int64_t n, int in_dim, int out_dim, int cus,
-                                                                                            lcrec_debug_forward_launch_ext *out, int capacity)
+// Debug exports (include/lcrec.h): the launches of the four GEMM entry points, from the step functions they launch by.
+LCREC_API int lcrec_debug_linear_forward_plan(int64_t n, int in_dim, int out_dim, int cus, lcrec_gemm_launch *out, int capacity)
 {
     return lcrec::linear_forward_plan(n, in_dim, out_dim, cus, out, capacity);
 }
-
-// Debug exports (include/lcrec.h): the launches of the other three GEMM entry points, from the step functions they launch by.
 LCREC_API int lcrec_debug_linear_backward_plan(int64_t n, int in_dim, int out_dim, int want_gx, int want_gw, lcrec_gemm_launch *out, int capacity)
 {
     return lcrec::linear_backward_plan(n, in_dim, out_dim, want_gx, want_gw, out, capacity);
@@ -2575,6 +2521,31 @@ LCREC_API int lcrec_debug_linear_backward_weights_plan(const lcrec_dw_problem *p
 LCREC_API int lcrec_debug_linear_bn_forward_plan(int64_t n, int in_dim, int out_dim, int pro, int stats, lcrec_gemm_launch *out)
 {
     return lcrec::linear_bn_forward_plan(n, in_dim, out_dim, pro, stats, out);
+}
+
+// The forward plan in the record it had before lcrec_gemm_launch carried the forward fields, under the name it had then (not in
+// include/lcrec.h): test helpers written against that record bind it by name and must keep working with this library.  The same
+// records as above, copied field by field (`rows` is m); nothing in the tree calls it, and it goes when those callers are gone.
+extern "C" struct lcrec_debug_forward_launch_ext {
+    int64_t row0, rows;
+    const char *label;
+    int form, tile_rows, tile_cols, k_tiles, tiles, virtual_tiles, workgroups, last_panel_rows;
+    int steady_iterations, list_min, list_max, empty_workgroups, single_tile_workgroups, ragged_handed_over;
+    int fast, register_buffered;
+};
+LCREC_API int lcrec_debug_linear_forward_plan_ext(int64_t n, int in_dim, int out_dim, int cus, lcrec_debug_forward_launch_ext *out,
+                                                  int capacity)
+{
+    lcrec_gemm_launch rec[lcrec::FWD_MAX_STEPS];
+    if (n != 0 && (!out || capacity < lcrec::FWD_MAX_STEPS)) return LCREC_EINVAL;
+    const int count = lcrec::linear_forward_plan(n, in_dim, out_dim, cus, rec, lcrec::FWD_MAX_STEPS);
+    for (int i = 0; i < count; ++i) {
+        const lcrec_gemm_launch &r = rec[i];
+        out[i] = {r.row0, r.m, r.label, r.form, r.tile_rows, r.tile_cols, r.k_tiles, r.tiles, r.virtual_tiles, r.workgroups,
+                  r.last_panel_rows, r.steady_iterations, r.list_min, r.list_max, r.empty_workgroups, r.single_tile_workgroups,
+                  r.ragged_handed_over, r.fast, r.register_buffered};
+    }
+    return count;
 }
 
 #ifdef LCREC_GEMM_STAMP

@@ -1,12 +1,13 @@
-// Stand-alone check of the host code in front of the generic GEMM launches, for a build with that code under AddressSanitizer +
-// UBSan (`make gemm_refusals && ./gemm_refusals`): every refusal of lcrec_linear_backward, lcrec_linear_backward_weights and
-// lcrec_linear_bn_forward comes back with its code and a text that names the entry point before anything touches a device, and
-// the three launch plans (lcrec_debug_*_plan) walk their steps on exact-size heap buffers.  It runs on a build host without a
+// Stand-alone check of the host code in front of the GEMM launches, for a build with that code under AddressSanitizer + UBSan
+// (`make gemm_refusals && ./gemm_refusals`): every refusal of lcrec_linear_forward, lcrec_linear_backward,
+// lcrec_linear_backward_weights and lcrec_linear_bn_forward comes back with its code and a text that names the entry point before
+// anything touches a device, and the four launch plans (lcrec_debug_linear_*_plan) walk their steps on exact-size heap buffers.  It runs on a build host without a
 // device.  Not part of liblcrec_hip.so, never loaded into Python.
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/lcrec.h"
@@ -27,6 +28,11 @@ static void expect_true(bool ok, const char *what)
     ++checks;
     if (!ok) { ++failures; printf("FAIL %s\n", what); }
 }
+
+struct Forward {
+    const float *x, *W, *b, *sc, *sh; int64_t n = 64; int in = 64, out = 64; float *y;
+    int call() const { return lcrec_linear_forward(x, n, in, W, b, sc, sh, 1, out, y, nullptr); }
+};
 
 struct Backward {
     const float *gy, *x, *W; int64_t n = 64; int in = 64, out = 64; float *gx, *gw; void *ws; size_t wsb = 0;
@@ -49,8 +55,26 @@ int main()
     char *p = reinterpret_cast<char *>(((uintptr_t)store.data() + 15) & ~(uintptr_t)15);
     float *f32 = reinterpret_cast<float *>(p), *off4 = reinterpret_cast<float *>(p + 4);
 
+    // ---- lcrec_linear_forward
+    const char *who = "linear_forward";
+    Forward fok;
+    fok.x = fok.W = fok.b = fok.sc = fok.sh = f32; fok.y = f32;
+    Forward f;
+    f = fok; f.x = nullptr; expect(f.call(), LCREC_EINVAL, who, "NULL pointer");
+    f = fok; f.W = nullptr; expect(f.call(), LCREC_EINVAL, who, "NULL pointer");
+    f = fok; f.y = nullptr; expect(f.call(), LCREC_EINVAL, who, "NULL pointer");
+    f = fok; f.n = -1; expect(f.call(), LCREC_EINVAL, who, "bad shape");
+    f = fok; f.in = 0; expect(f.call(), LCREC_EINVAL, who, "bad shape");
+    f = fok; f.out = -4; expect(f.call(), LCREC_EINVAL, who, "bad shape");
+    f = fok; f.in = 12; expect(f.call(), LCREC_EUNSUPPORTED, who, "in_dim=12 is not a multiple of 8");
+    f = fok; f.sh = nullptr; expect(f.call(), LCREC_EINVAL, who, "bn_scale and bn_shift");
+    f = fok; f.sc = nullptr; expect(f.call(), LCREC_EINVAL, who, "bn_scale and bn_shift");
+    f = fok; f.x = off4; expect(f.call(), LCREC_EINVAL, who, "16-byte aligned");
+    f = fok; f.W = off4; expect(f.call(), LCREC_EINVAL, who, "16-byte aligned");
+    f = fok; f.n = 0; f.x = nullptr; expect_true(f.call() == LCREC_OK, "linear_forward: an empty batch is not an error");
+
     // ---- lcrec_linear_backward
-    const char *who = "linear_backward";
+    who = "linear_backward";
     Backward ok;
     ok.gy = ok.x = ok.W = f32; ok.gx = ok.gw = f32; ok.ws = p;
     Backward a;
@@ -132,6 +156,26 @@ int main()
 
     // ---- the plans, on exact-size heap buffers
     {
+        std::vector<lcrec_gemm_launch> fwd(4);
+        expect_true(lcrec_debug_linear_forward_plan(8200, 384, 4096, 256, fwd.data(), 4) == 2 && fwd[0].family == LCREC_GEMMK_PP &&
+                        fwd[0].form == 3 && fwd[0].row0 == 0 && fwd[0].m == 8192 && fwd[0].workgroups == 256 && fwd[0].list_min == 4 &&
+                        fwd[0].list_max == 4 && fwd[1].family == LCREC_GEMMK_32x64 && fwd[1].row0 == 8192 && fwd[1].m == 8,
+                    "forward plan: a persistent head of 8192 rows and a tail of 8 on the 32 x 64 tiles");
+        expect_true(lcrec_debug_linear_forward_plan(70, 32, 68, 256, fwd.data(), 4) == 1 && fwd[0].family == LCREC_GEMMK_32x64 &&
+                        fwd[0].tiles == 3 * 2 && fwd[0].form == 0 && fwd[0].list_max == 0,
+                    "forward plan: one launch on the 32 x 64 tiles");
+        expect_true(lcrec_debug_linear_forward_plan(3336, 384, 3840, 256, fwd.data(), 4) == 1 && fwd[0].form == 3 &&
+                        fwd[0].virtual_tiles > fwd[0].tiles && fwd[0].empty_workgroups == 4 && fwd[0].list_min == 0 && fwd[0].list_max == 2,
+                    "forward plan: a persistent launch whose tile numbering has holes");
+        expect_true(lcrec_debug_linear_forward_plan(0, 384, 4096, 256, fwd.data(), 4) == 0 &&
+                        lcrec_debug_linear_forward_plan(0, 384, 4096, 0, nullptr, 0) == 0, "forward plan: empty batch, whatever the rest");
+        // (a refused forward plan is a plain code: it leaves the last-error text alone)
+        expect_true(lcrec_debug_linear_forward_plan(64, 64, 64, 256, fwd.data(), 3) == LCREC_EINVAL, "forward plan: capacity 3 is refused");
+        expect_true(lcrec_debug_linear_forward_plan(64, 64, 64, 0, fwd.data(), 4) == LCREC_EINVAL, "forward plan: 0 CUs are refused");
+        expect_true(lcrec_debug_linear_forward_plan(64, 64, 64, 256, nullptr, 4) == LCREC_EINVAL, "forward plan: NULL output is refused");
+        const std::string before = lcrec_last_error();
+        expect_true(lcrec_debug_linear_forward_plan(64, 12, 64, 256, fwd.data(), 4) == LCREC_EUNSUPPORTED && before == lcrec_last_error(),
+                    "forward plan: in_dim = 12 is refused, the last-error text untouched");
         std::vector<lcrec_gemm_launch> out(3);
         expect_true(lcrec_debug_linear_backward_plan(2048, 68, 64, 1, 1, out.data(), 3) == 3, "backward plan: dX, dW, reducer");
         expect_true(out[1].runs == 16 && out[2].family == LCREC_GEMMK_REDUCER && out[2].total4 == 64 * 68 / 4, "backward plan: S = 16");

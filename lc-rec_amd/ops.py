@@ -313,7 +313,7 @@ def linear_backward_splits(n, in_dim, out_dim):
 
 
 GEMM_ROLES = ("dx", "dw", "reduce", "forward")                 # LCREC_GEMMR_* of include/lcrec.h, in order
-GEMM_FAMILIES = ("tile_body", "32x64", "reducer")              # LCREC_GEMMK_*
+GEMM_FAMILIES = ("tile_body", "32x64", "reducer", "pp")        # LCREC_GEMMK_*
 
 
 def _gemm_launches(buf, count):
@@ -325,6 +325,20 @@ def _gemm_launches(buf, count):
         d["family"] = GEMM_FAMILIES[d["family"]]
         out.append(d)
     return out
+
+
+def linear_forward_plan(n, in_dim, out_dim, cus=256):
+    """The launches of linear_forward for [n][in_dim] -> [n][out_dim] on a device of `cus` compute units, in order (include/lcrec.h,
+    lcrec_debug_linear_forward_plan): a list of dicts as linear_backward_plan gives them.  Host only: no GPU is needed.  Raises
+    LcrecError for a shape the entry point refuses (this export leaves the library's last-error text alone)."""
+    buf = (_lib.GemmLaunch * 4)()
+    count = _lib.load().lcrec_debug_linear_forward_plan(int(n), int(in_dim), int(out_dim), int(cus), ctypes.addressof(buf), 4)
+    if count < 0:
+        err = _lib.LcrecError(f"lcrec_debug_linear_forward_plan({n}, {in_dim}, {out_dim}, {cus}) failed ({count}): "
+                              "a shape lcrec_linear_forward refuses")
+        err.code = count
+        raise err
+    return _gemm_launches(buf, count)
 
 
 def linear_backward_plan(n, in_dim, out_dim, need_gx=True, need_gw=True):

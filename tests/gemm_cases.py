@@ -1,7 +1,8 @@
 """The case table of the generic GEMM kernels of csrc/gemm_f32.hip -- linear_tile_body in all its instantiations,
 linear_s16_kernel<TB>, linear_dw_grouped_kernel<PRO> and the two split-K reducers -- shared by tests/test_gemm_plan_host.py (CPU:
 every row reaches the launches it claims, the reachability sweep) and tests/test_gpu_gemm_forms.py (GPU: every row bit for bit
-against the oracle), with the unified view of the four launch plans, the statistics reference with its bound, and the localiser.
+against the oracle), with the four launch plans (all records of lcrec_gemm_launch), the statistics reference with its bound, and
+the localiser.
 
 A row is a call of one entry point (`kind`: fwd = linear_forward, bwd = linear_backward, grp = linear_backward_weights, train =
 linear_bn_forward), its sizes, its switches (`opt`), what the plan must say of it on 256 CUs (`expect`) and the paths it exists
@@ -21,24 +22,15 @@ U = 2.0 ** -24                                           # float32 unit roundoff
 
 
 # ---------------------------------------------------------------- the plans, in one shape
-def _forward_launches(lib, n, k, out, cus):
-    launches = []
-    for d in pp.plan(lib, n, k, out, cus):
-        fam = {"linear_fwd_32x64": "32x64", pp.PP_LABEL: "pp"}.get(d["label"], "tile_body")
-        nk = d["k_tiles"]
-        bn_blocks = -(-out // d["tile_cols"])
-        launches.append(dict(d, role="forward", family=fam, a_kmajor=0, w_kmajor=0, pro=0, stats=0, m=d["rows"], n=out, k=k, runs=1,
-                             k_tiles_per_run=nk, k_tiles_last_run=nk, last_k_valid=k - (nk - 1) * 32, wg_start=0,
-                             last_tile_cols=out - (bn_blocks - 1) * d["tile_cols"], vector_stores=int(out % 4 == 0),
-                             chunk_row_tiles=0, chunks=0, total4=0, grouped=False))
-    return launches
+def _forward_launches(n, k, out, cus):
+    return [dict(l, grouped=False) for l in pp.plan(n, k, out, cus)]
 
 
-def launches_of(row, ops, lib, cus=CUS):
+def launches_of(row, ops, cus=CUS):
     """The planned launches of a row, every plan in the fields of lcrec_gemm_launch plus `grouped`; grp rows: the products of
     all problems, then the reducers' records."""
     if row.kind == "fwd":
-        return _forward_launches(lib, *row.dims, cus)
+        return _forward_launches(*row.dims, cus)
     if row.kind == "bwd":
         return [dict(l, grouped=False) for l in ops.linear_backward_plan(*row.dims, row.opt["gx"], row.opt["gw"])]
     if row.kind == "train":

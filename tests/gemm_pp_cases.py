@@ -1,11 +1,10 @@
 """The case table of the two ping-pong GEMM kernels (linear_fwd_pp3_kernel / linear_fwd_pp2_kernel of csrc/gemm_f32.hip),
 shared by tests/test_gemm_pp_plan_host.py (CPU: every row reaches the paths it claims) and tests/test_gpu_gemm_pp.py (GPU:
-every row bit for bit against the oracle), with the binding of the library's launch plan and the mismatch localiser.
+every row bit for bit against the oracle), with the library's launch plan (ops.linear_forward_plan) and the mismatch localiser.
 
 A row is a shape, its epilogue switches, the launches the dispatch rule must make of it on 256 CUs (`expect`) and the kernel
 paths it exists for (`covers`, names of PROPERTIES).  Each property is a predicate over the row and its planned launch, so a
 row cannot claim a path its shape does not reach, and REQUIRED lists the paths some row must keep claiming."""
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -15,33 +14,12 @@ PER_TILE, PERSISTENT = 2, 3          # `form` of a ping-pong launch: linear_fwd_
 TILE_M, TILE_N, GROUP_M = 256, 128, 128
 
 
-class ForwardLaunch(ctypes.Structure):
-    """lcrec_debug_forward_launch_ext of csrc/gemm_f32.hip: lcrec_debug_forward_launch with `fast` and `register_buffered` at its end"""
-    _fields_ = [("row0", ctypes.c_int64), ("rows", ctypes.c_int64), ("label", ctypes.c_char_p), ("form", ctypes.c_int),
-                ("tile_rows", ctypes.c_int), ("tile_cols", ctypes.c_int), ("k_tiles", ctypes.c_int), ("tiles", ctypes.c_int),
-                ("virtual_tiles", ctypes.c_int), ("workgroups", ctypes.c_int), ("last_panel_rows", ctypes.c_int),
-                ("steady_iterations", ctypes.c_int), ("list_min", ctypes.c_int), ("list_max", ctypes.c_int),
-                ("empty_workgroups", ctypes.c_int), ("single_tile_workgroups", ctypes.c_int),
-                ("ragged_handed_over", ctypes.c_int), ("fast", ctypes.c_int), ("register_buffered", ctypes.c_int)]
-
-
-def plan(lib, n, k, out, cus):
-    """The launches lcrec_linear_forward makes for [n][k] -> [n][out] on `cus` compute units: a list of dicts (the fields of
-    ForwardLaunch, label decoded).  Host code of the library: no GPU is needed."""
-    fn = lib.lcrec_debug_linear_forward_plan_ext
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ForwardLaunch), ctypes.c_int]
-    buf = (ForwardLaunch * 4)()
-    count = fn(n, k, out, cus, buf, 4)
-    if count < 0:
-        raise RuntimeError(f"lcrec_debug_linear_forward_plan({n}, {k}, {out}, {cus}) failed ({count}): "
-                           "a shape lcrec_linear_forward refuses")
-    launches = []
-    for i in range(count):
-        d = {name: getattr(buf[i], name) for name, _ in ForwardLaunch._fields_}
-        d["label"] = d["label"].decode()
-        launches.append(d)
-    return launches
+def plan(n, k, out, cus):
+    """The launches lcrec_linear_forward makes for [n][k] -> [n][out] on `cus` compute units: the dicts of
+    lcrec_amd.ops.linear_forward_plan (the fields of lcrec_gemm_launch) plus `rows`, the table's name for `m`.  Host code of
+    the library: no GPU is needed."""
+    from lcrec_amd import ops
+    return [dict(l, rows=l["m"]) for l in ops.linear_forward_plan(n, k, out, cus)]
 
 
 def plan_labels(launches, repeat=1):

@@ -18,15 +18,9 @@ def ops():
     return lcrec_amd.ops
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import lcrec_amd
-    return lcrec_amd._lib.load()
-
-
 @pytest.mark.parametrize("row", gc.ROWS, ids=gc.row_id)
-def test_row_reaches_what_it_claims(ops, lib, row):
-    launches = gc.launches_of(row, ops, lib)
+def test_row_reaches_what_it_claims(ops, row):
+    launches = gc.launches_of(row, ops)
     bad = gc.check_claims(row, launches)
     assert not bad, f"{gc.row_id(row)} on {gc.CUS} CUs:\n  " + "\n  ".join(bad) + f"\n  plan: {launches}"
     assert row.covers and set(row.expect) == {"form", "k_tiles", "runs"}
@@ -139,7 +133,7 @@ WIDTHS = (4, 32, 36, 64, 68, 128, 132, 1024, 2048, 4096)
 KS = (8, 32, 40, 64, 384)
 
 
-def test_plans_follow_the_restated_rule_and_reach_exactly_the_named_forms(ops, lib):
+def test_plans_follow_the_restated_rule_and_reach_exactly_the_named_forms(ops):
     """The four plans over a grid against the rule above, and the reachability sweep: every (form, S > 1) the grid reaches is
     claimed by a row of the table, and what it does not reach is exactly gemm_cases.UNREACHABLE -- a change of the rule that
     makes one of those reachable, or strands a form, fails here."""
@@ -149,7 +143,7 @@ def test_plans_follow_the_restated_rule_and_reach_exactly_the_named_forms(ops, l
             for k in KS:
                 if n * out > 2 ** 29 or n * k > 2 ** 27:
                     continue
-                got = [gc.form_of(l) for l in gc._forward_launches(lib, n, k, out, gc.CUS)]
+                got = [gc.form_of(l) for l in gc._forward_launches(n, k, out, gc.CUS)]
                 assert got == _forward_forms(n, k, out), (n, k, out, got)
                 reached |= {(f, False) for f in got}
     for n in NS:
@@ -187,14 +181,14 @@ def test_plans_follow_the_restated_rule_and_reach_exactly_the_named_forms(ops, l
     # every reachable combination is some row's
     rows = set()
     for row in gc.ROWS:
-        for l in gc.launches_of(row, ops, lib):
+        for l in gc.launches_of(row, ops):
             rows.add((gc.form_of(l), l["family"] == "tile_body" and l["runs"] > 1))
     assert reached <= rows, sorted(reached - rows)
 
 
-def test_the_forms_the_issue_names(ops, lib):
+def test_the_forms_the_issue_names(ops):
     """Literal spot checks, so that the restated rule and the library cannot drift together."""
-    f = lambda n, k, out: [gc.form_of(l) for l in gc._forward_launches(lib, n, k, out, 256)]
+    f = lambda n, k, out: [gc.form_of(l) for l in gc._forward_launches(n, k, out, 256)]
     assert f(200, 64, 30) == ["128x32_row_fast"] and f(8200, 32, 32) == ["128x32_row_fast"] and f(1024, 64, 640) == ["64x64_row_fast"]
     assert f(2048, 64, 1024) == ["64x128_row_fast"] and f(32641, 32, 64) == ["128x64_row_fast"] and f(32640, 32, 64) == ["64x64_row_fast"]
     assert f(8192, 72, 1024) == ["128x128_row_guarded"] and f(65409, 8, 128) == ["128x128_row_guarded"] and f(65408, 8, 128) == ["64x128_row_guarded"]

@@ -1,4 +1,4 @@
-"""CPU: every row of tests/gemm_pp_handover_cases.py has the launch plan it claims (lcrec_debug_linear_forward_plan_ext for
+"""CPU: every row of tests/gemm_pp_handover_cases.py has the launch plan it claims (lcrec_debug_linear_forward_plan for
 256 CUs, nothing launched), the rows add the switch combinations tests/gemm_pp_cases.py lacks, and the special-value inputs
 hold what they say -- by the oracle, -0.0 does reach the ReLU and comes out as +0.0."""
 import numpy as np
@@ -10,15 +10,9 @@ import gemm_pp_handover_cases as ho
 CUS = 256
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import lcrec_amd
-    return lcrec_amd._lib.load()
-
-
 @pytest.mark.parametrize("case", ho.CASES + [ho.SPECIAL], ids=pp.case_id)
-def test_row_plan_is_what_it_claims(lib, case):
-    launches = pp.plan(lib, case.n, case.k, case.out, CUS)
+def test_row_plan_is_what_it_claims(case):
+    launches = pp.plan(case.n, case.k, case.out, CUS)
     bad = ho.check_claims(case, launches)
     assert not bad, f"{pp.case_id(case)} on {CUS} CUs:\n  " + "\n  ".join(bad) + f"\n  plan: {launches}"
     head = launches[0]
@@ -41,9 +35,9 @@ def test_rows_add_what_the_first_table_lacks():
     assert (holes.n // 256, holes.out // 128) == (12, 64)
 
 
-def test_xcd_hole_row_counts(lib):
+def test_xcd_hole_row_counts():
     holes = next(c for c in ho.CASES if "pp3_xcd_holes" in c.covers)
-    head = pp.plan(lib, holes.n, holes.k, holes.out, CUS)[0]
+    head = pp.plan(holes.n, holes.k, holes.out, CUS)[0]
     assert (head["tiles"], head["virtual_tiles"]) == (768, 1024), head
 
 

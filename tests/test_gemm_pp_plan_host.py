@@ -10,15 +10,9 @@ import gemm_pp_cases as pp
 CUS = 256
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import lcrec_amd
-    return lcrec_amd._lib.load()
-
-
 @pytest.mark.parametrize("case", pp.CASES, ids=pp.case_id)
-def test_row_reaches_what_it_claims(lib, case):
-    launches = pp.plan(lib, case.n, case.k, case.out, CUS)
+def test_row_reaches_what_it_claims(case):
+    launches = pp.plan(case.n, case.k, case.out, CUS)
     bad = pp.check_claims(case, launches)
     assert not bad, f"{pp.case_id(case)} on {CUS} CUs:\n  " + "\n  ".join(bad) + f"\n  plan: {launches}"
     # the numbers the plan reports, against the shape itself
@@ -63,19 +57,19 @@ def test_row_inputs(case):
     assert all((p is None and q is None) or np.array_equal(p, q) for p, q in zip((x, W, b, sc, sh), again))
 
 
-def test_plan_follows_the_cu_count(lib):
+def test_plan_follows_the_cu_count():
     """The persistent form's grid is the CU count rounded down to a multiple of 8 (at least 8) and never above the virtual
     tiles; rows and labels do not depend on it.  The per-tile form and the other kernels ignore it."""
     for cus, want in ((256, 256), (304, 304), (250, 248), (8, 8), (5, 8), (2000, 1024)):
-        head, tail = pp.plan(lib, 8200, 384, 4096, cus)
+        head, tail = pp.plan(8200, 384, 4096, cus)
         assert (head["rows"], head["form"], head["workgroups"], tail["rows"], tail["label"]) == \
                (8192, pp.PERSISTENT, want, 8, "linear_fwd_32x64"), (cus, head, tail)
         assert head["list_min"] == 1024 // want and head["list_max"] == -(-1024 // want)
-    assert pp.plan(lib, 0, 384, 4096, 256) == []
-    assert [l["label"] for l in pp.plan(lib, 1000, 768, 2048, 256)] == ["linear_fwd_64x64"]      # below one round: generic
-    assert [l["label"] for l in pp.plan(lib, 8192, 72, 1024, 256)] == ["linear_fwd_128x128"]
+    assert pp.plan(0, 384, 4096, 256) == []
+    assert [l["label"] for l in pp.plan(1000, 768, 2048, 256)] == ["linear_fwd_64x64"]      # below one round: generic
+    assert [l["label"] for l in pp.plan(8192, 72, 1024, 256)] == ["linear_fwd_128x128"]
     with pytest.raises(RuntimeError):
-        pp.plan(lib, 128, 12, 64, 256)                                           # in_dim % 8 != 0: linear_forward refuses it
+        pp.plan(128, 12, 64, 256)                                           # in_dim % 8 != 0: linear_forward refuses it
 
 
 # ---- the localiser
@@ -83,9 +77,9 @@ def _fake(n, out, seed=0):
     return np.random.RandomState(seed).standard_normal((n, out)).astype(np.float32)
 
 
-def test_localiser_names_piece_row_and_tile(lib):
+def test_localiser_names_piece_row_and_tile():
     n, k, out = 776, 384, 8192                  # 4 panels x 64 column tiles on 256 workgroups: lists of two, ragged panel 3
-    launches = pp.plan(lib, n, k, out, CUS)
+    launches = pp.plan(n, k, out, CUS)
     want = _fake(n, out)
     assert pp.localise(want.copy(), want, launches) is None
 
@@ -118,14 +112,14 @@ def test_localiser_names_piece_row_and_tile(lib):
     assert "handed over: sent in the staging phase of K-tile 1 of the next tile" in msg      # group 0, piece 0
 
 
-def test_localiser_per_tile_form_and_tail(lib):
-    launches = pp.plan(lib, 8200, 384, 4096, CUS)
+def test_localiser_per_tile_form_and_tail():
+    launches = pp.plan(8200, 384, 4096, CUS)
     want = _fake(8200, 4096, 1)
     got = want.copy()
     got[8195, 70] = 1.0                                              # in the 8-row tail on the 32 x 64 tiles
     msg = pp.localise(got, want, launches)
     assert "rows 8192..8200 on linear_fwd_32x64" in msg and "tile (0, 1) of 32 x 64" in msg
-    launches = pp.plan(lib, 4096, 64, 1930, CUS)
+    launches = pp.plan(4096, 64, 1930, CUS)
     want = _fake(4096, 1930, 2)
     got = want.copy()
     got[4095, 1929] = -want[4095, 1929]                              # the last element: last panel, the 10-column tile

@@ -83,7 +83,7 @@ def _stream(hip):
 @pytest.fixture
 def planned(hip, cus, request):
     def plan(row):
-        launches = gc.launches_of(row, hip.ops, hip._lib.load(), cus)
+        launches = gc.launches_of(row, hip.ops, cus)
         bad = gc.check_claims(row, launches)
         assert not bad, f"on this device ({cus} CUs) the row {gc.row_id(row)} does not test what it says:\n  " + "\n  ".join(bad) + f"\n  plan: {launches}"
         return launches

@@ -30,8 +30,7 @@ def _launches(trace):
 
 @pytest.mark.parametrize("case", pp.CASES, ids=pp.case_id)
 def test_pp_bit_exact(hip, oracle, cus, case):
-    lib = hip._lib.load()
-    launches = pp.plan(lib, case.n, case.k, case.out, cus)
+    launches = pp.plan(case.n, case.k, case.out, cus)
     bad = pp.check_claims(case, launches)
     assert not bad, (f"on this device ({cus} CUs) the row {pp.case_id(case)} does not test what it says:\n  "
                      + "\n  ".join(bad) + f"\n  plan: {launches}")
@@ -69,9 +68,8 @@ def test_pp_bit_exact(hip, oracle, cus, case):
 def test_encode_assign_reaches_persistent_bn_kernel(hip, oracle, cus):
     """RQVAE.get_indices on a BatchNorm model: the widest encoder layer (384 -> 4096 at 2048 items) goes through
     linear_fwd_pp3_kernel<true>; latent, indices and xq against the oracle, bit for bit."""
-    lib = hip._lib.load()
     n, dims = 2048, [384, 4096, 256, 32]
-    plans = [pp.plan(lib, n, dims[l], dims[l + 1], cus) for l in range(3)]
+    plans = [pp.plan(n, dims[l], dims[l + 1], cus) for l in range(3)]
     assert [(l["label"], l["form"], l["rows"]) for l in plans[0]] == [(pp.PP_LABEL, pp.PERSISTENT, n)], plans[0]
     assert all(l["label"] != pp.PP_LABEL for p in plans[1:] for l in p), plans
     rs = np.random.RandomState(2048 + 384)

@@ -21,8 +21,7 @@ def cus(hip):
 
 def _run_twice_and_compare(hip, cus, case, arrays, want):
     """Two guarded launches of `case` on `arrays` back to back; each against `want` bit for bit; returns the first result."""
-    lib = hip._lib.load()
-    launches = pp.plan(lib, case.n, case.k, case.out, cus)
+    launches = pp.plan(case.n, case.k, case.out, cus)
     bad = ho.check_claims(case, launches)
     assert not bad, (f"on this device ({cus} CUs) the row {pp.case_id(case)} does not test what it says:\n  "
                      + "\n  ".join(bad) + f"\n  plan: {launches}")

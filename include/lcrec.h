@@ -740,6 +740,58 @@ int lcrec_debug_sinkhorn_batch(const float *resid, int64_t n, int e, const float
                                unsigned int *ticket, void *stream, int form, int64_t *runner_out, double *ratio_out,
                                int *form_ran);
 
+/* lcrec_sinkhorn_assign with several groups sorts them into size classes, one launch each: classes 0 .. 3 keep a group's g x K
+ * fp64 matrix in LDS (g * K <= 2048 / 4096 / 8192 / 16384 doubles, 256 threads, allocation sized by the class's largest group),
+ * class 4 keeps it in a slab of the workspace (1024 threads), and what is left (class 5: more than 4096 rows, or the slab-sized
+ * groups of a call in which running them side by side does not pay) goes one group at a time through the batch-sized solver
+ * above.  A group that meets a class-3 bound but whose allocation -- (g * K + ((g + 1) & ~1) + K) doubles plus 64 B static --
+ * would exceed the 163 840 B a workgroup can have (four rows at K >= 4094, or K = 4 from 4094 rows up) belongs to class 4.
+ * lcrec_debug_sinkhorn_groups_plan reports the launches lcrec_sinkhorn_assign makes for a group table: it is the function
+ * lcrec_sinkhorn_assign launches by.  Host only: nothing is launched, no device is needed. */
+#define LCREC_SK_GROUP_CLASSES 5          /* launches of the one-workgroup-per-group kernel: classes 0 .. 4 */
+#define LCREC_SK_CLASS_SLAB 4
+#define LCREC_SK_CLASS_BATCH 5
+enum { LCREC_SK_TABLE_NONE = 0,           /* no group takes the one-workgroup kernel: no table */
+       LCREC_SK_TABLE_ARGUMENT = 1,       /* <= 4 groups: the table travels as a kernel argument */
+       LCREC_SK_TABLE_RING = 2,           /* through the context's pinned ring, no host wait */
+       LCREC_SK_TABLE_SYNCHRONOUS = 3 };  /* no context: a copy the call waits for */
+typedef struct {
+    int groups;               /* groups of the class in this call (0: no launch) */
+    int maxg;                 /* rows of the largest of them */
+    int64_t lds_bytes;        /* dynamic LDS of the launch (class 4: 0) */
+    int set_attribute;        /* whether the launch has to raise the kernel's dynamic LDS limit first (more than 48 KB) */
+    int threads;              /* 256; class 4: 1024 */
+    int table_first;          /* position of the class's first group in the reordered table */
+    const char *label;        /* trace label of the launch (static string), NULL without a launch */
+} lcrec_sinkhorn_class_plan;
+typedef struct {
+    lcrec_sinkhorn_class_plan cls[LCREC_SK_GROUP_CLASSES];
+    int slab_ok;              /* whether the class-4 groups run side by side (else they take the batch path) */
+    int64_t slab_doubles;     /* doubles of the workspace slab */
+    int batch_groups;         /* groups routed to the batch-sized solver, one after another */
+    int64_t batch_biggest;    /* rows of the largest of them */
+    int table_groups;         /* groups in the reordered table (three int64 each: begin, end, slab offset) */
+    int transport;            /* LCREC_SK_TABLE_* */
+    int fork_mask;            /* bit 0: class 4 on helper stream 0; bit 1: classes 1 .. 3 on helper stream 1 (context only) */
+    int64_t workspace_bytes;  /* = lcrec_sinkhorn_assign_workspace */
+} lcrec_sinkhorn_groups_plan;
+typedef struct {
+    int cls;                  /* 0 .. 5; -1 for an empty group */
+    int position;             /* in the reordered table (classes in order, offset order inside a class); -1 if not in it */
+    int64_t slab_offset;      /* doubles from the slab's start (class 4 in the table), else 0 */
+} lcrec_sinkhorn_group_route;
+/* routes: NULL, or room for n_groups records. */
+int lcrec_debug_sinkhorn_groups_plan(int K, const int64_t *group_offsets, int n_groups, int has_context,
+                                     lcrec_sinkhorn_groups_plan *out, lcrec_sinkhorn_group_route *routes);
+/* lcrec_sinkhorn_assign with the same arguments and the same launch code, plus what lcrec_debug_sinkhorn_batch adds:
+ *   runner_out  device int64[n] or NULL: per row of a group the column of the second-largest entry (first one on ties)
+ *   ratio_out   device double[n] or NULL (given together with runner_out): second-largest / largest entry of the row
+ * Rows that belong to no group are not written.  With both NULL the kernels launched are lcrec_sinkhorn_assign's own. */
+int lcrec_debug_sinkhorn_groups(const float *resid, int64_t n, int e, const float *codebook, int K,
+                                const int64_t *group_offsets, int n_groups, double epsilon, int iters,
+                                int64_t *idx_out, int64_t idx_stride, void *workspace, size_t workspace_bytes,
+                                lcrec_context *ctx, unsigned int *ticket, void *stream, int64_t *runner_out, double *ratio_out);
+
 /* lcrec_rq_assign picks a form of its kernel by shape: the split form (one 64-item tile per 256-thread workgroup, a level's
  * 32-code blocks dealt over its four waves) or one tile per wave, 256 or 512 threads, a grid, and a greedy packing of consecutive
  * levels into launches whose codebooks fit in LDS.  lcrec_debug_rq_assign_plan reports that choice and its geometry,

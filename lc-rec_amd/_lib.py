@@ -126,6 +126,10 @@ _SIGNATURES = {
     "lcrec_debug_sinkhorn_batch": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                                   _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp, _vp,
                                                   ctypes.POINTER(ctypes.c_int)]),
+    "lcrec_debug_sinkhorn_groups_plan": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "lcrec_debug_sinkhorn_groups": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_double,
+                                                   ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     "lcrec_debug_rq_assign_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_int, _vp]),
     "lcrec_debug_rq_assign": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int),
@@ -154,6 +158,27 @@ class SinkhornPlan(ctypes.Structure):
                 ("sets", ctypes.c_int), ("rows_per_workgroup", ctypes.c_int), ("padded_columns", ctypes.c_int),
                 ("ragged_wave", ctypes.c_int), ("ragged_workgroup", ctypes.c_int), ("batch_route", ctypes.c_int),
                 ("workspace_bytes", ctypes.c_int64)]
+
+
+SK_GROUP_CLASSES = 5                 # LCREC_SK_GROUP_CLASSES of include/lcrec.h
+
+
+class SinkhornClassPlan(ctypes.Structure):
+    """lcrec_sinkhorn_class_plan of include/lcrec.h"""
+    _fields_ = [("groups", ctypes.c_int), ("maxg", ctypes.c_int), ("lds_bytes", ctypes.c_int64), ("set_attribute", ctypes.c_int),
+                ("threads", ctypes.c_int), ("table_first", ctypes.c_int), ("label", ctypes.c_char_p)]
+
+
+class SinkhornGroupsPlan(ctypes.Structure):
+    """lcrec_sinkhorn_groups_plan of include/lcrec.h"""
+    _fields_ = [("cls", SinkhornClassPlan * SK_GROUP_CLASSES), ("slab_ok", ctypes.c_int), ("slab_doubles", ctypes.c_int64),
+                ("batch_groups", ctypes.c_int), ("batch_biggest", ctypes.c_int64), ("table_groups", ctypes.c_int),
+                ("transport", ctypes.c_int), ("fork_mask", ctypes.c_int), ("workspace_bytes", ctypes.c_int64)]
+
+
+class SinkhornGroupRoute(ctypes.Structure):
+    """lcrec_sinkhorn_group_route of include/lcrec.h"""
+    _fields_ = [("cls", ctypes.c_int), ("position", ctypes.c_int), ("slab_offset", ctypes.c_int64)]
 
 
 MAX_LEVELS = 16                      # LCREC_MAX_LEVELS of include/lcrec.h

@@ -214,7 +214,8 @@ int rq_assign(const float *z, int64_t n, int e, const float *codebooks, const in
 size_t sinkhorn_workspace(int64_t n, int K, const int64_t *offs, int G);
 int sinkhorn_assign(const float *r, int64_t n, int e, const float *cb, int K, const int64_t *offs, int G, double eps,
                     int iters, int64_t *idx_out, int64_t idx_stride, void *workspace, size_t workspace_bytes,
-                    lcrec_context *ctx, unsigned *ticket, hipStream_t stream);
+                    lcrec_context *ctx, unsigned *ticket, hipStream_t stream, int64_t *runner_out = nullptr,
+                    double *ratio_out = nullptr);
 int apply_level(const float *r_in, int64_t n, int e, const float *cb, int K, const int64_t *idx, int64_t idx_stride,
                 float *xq, int xq_accumulate, float *r_out, double *sse_out, void *workspace, size_t workspace_bytes,
                 unsigned *ticket, hipStream_t stream);

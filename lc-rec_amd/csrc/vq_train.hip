@@ -402,11 +402,14 @@ __device__ __forceinline__ double block_sum(double v, double *scratch)
     return s;
 }
 
-template <int E, bool GLOBALQ, int THREADS>
+// DEBUG (lcrec_debug_sinkhorn_groups): the final argmax loop also writes the row's runner-up and second / best, as
+// sk_final_kernel does.  Production launches DEBUG = false, which never reads the two pointers.
+template <int E, bool GLOBALQ, int THREADS, bool DEBUG>
 __global__ __launch_bounds__(THREADS) void sk_small_kernel(const float *__restrict__ r, const float *__restrict__ cb,
                                                               int K, const int64_t *__restrict__ offs,
                                                               double eps, int iters, int64_t *idx_out,
-                                                              int64_t idx_stride, double *qslab)
+                                                              int64_t idx_stride, double *qslab, int64_t *runner_out,
+                                                              double *ratio_out)
 {
     extern __shared__ __attribute__((aligned(16))) double sks_sm[];
     __shared__ double scratch[THREADS / 64];
@@ -540,6 +543,15 @@ __global__ __launch_bounds__(THREADS) void sk_small_kernel(const float *__restri
             if (b2 > best || (b2 == best && j2 < bj)) { best = b2; bj = j2; }
         }
         if (lane == 0) idx_out[(i0 + t) * idx_stride] = bj;
+        if (DEBUG) {
+            double sec = -1.0;
+            int sj = 0;
+            for (int j = lane; j < K; j += 64) {
+                const double v = Q[(size_t)t * K + j] * Bd;
+                if (j != bj && v > sec) { sec = v; sj = j; }
+            }
+            sk_runner_up(sec, sj, best, lane, runner_out + i0 + t, ratio_out + i0 + t);
+        }
     }
 }
 
@@ -713,13 +725,20 @@ constexpr int SK_SLAB = 4, SK_BATCH = 5;
 
 static inline size_t sk_group_doubles(int64_t g, int K) { return (size_t)g * K + (size_t)((g + 1) & ~(int64_t)1) + K; }
 
+// What a workgroup of the LDS form may ask for: 160 KB less the kernel's static LDS (scratch[4] doubles + fred[2][4] floats).
+// Q alone fits by the class bound, but rsum and csum sit behind it: from K = 4094 up the four-row group that fills class 3 would
+// ask for more (K = 4096, g = 4: 163 872 B + 64), likewise K = 4 from 4094 rows up, and the launch would fail in the middle of a
+// call.  Such a group takes the slab form.
+constexpr size_t SKS_LDS_LIMIT = 160 * 1024, SKS_LDS_STATIC = 64;
+static_assert(SKS_LDS_STATIC == (SKS_THREADS / 64) * (sizeof(double) + 2 * sizeof(float)), "static LDS of sk_small_kernel<E, false, 256>");
+
 static inline int sk_class(int64_t sz, int K)
 {
     const int64_t q = sz * K;
     if (q <= SKS_TINY) return 0;
     if (q <= 2 * SKS_TINY) return 1;
     if (q <= 4 * SKS_TINY) return 2;
-    if (q <= SKS_MAX) return 3;
+    if (q <= SKS_MAX && sk_group_doubles(sz, K) * sizeof(double) + SKS_LDS_STATIC <= SKS_LDS_LIMIT) return 3;
     return sz <= SKS_SLAB_MAX_ROWS ? SK_SLAB : SK_BATCH;
 }
 
@@ -761,6 +780,73 @@ size_t sinkhorn_workspace(int64_t n, int K, const int64_t *offs, int G)
     const SkPlan p = sk_plan(K, offs, G);
     return align_up((size_t)3 * G * sizeof(int64_t), 256) + align_up((size_t)p.slab_doubles * sizeof(double), 256) +
            (p.biggest ? sk_big_bytes(p.biggest, K) : 0);
+}
+
+// ---- the launches of a grouped call, as a pure function of (K, the group table, whether there is a context): sinkhorn_assign()
+// launches by this plan, lcrec_debug_sinkhorn_groups_plan() reports it; neither restates the other.  offs is checked by the caller.
+constexpr int SK_TABLE_ARG_GROUPS = 4;           // groups whose table still travels as a kernel argument (SmallTable)
+
+static inline int sk_trace_id(int cls, int maxg, int K)           // the trace label of a class's launch
+{
+    return cls == SK_SLAB ? K_SINKHORN_SLAB : (int64_t)maxg * K <= SKS_TINY ? K_SINKHORN_TINY : K_SINKHORN_SMALL;
+}
+
+static void sk_groups_plan(int K, const int64_t *offs, int G, bool has_context, lcrec_sinkhorn_groups_plan *o,
+                           lcrec_sinkhorn_group_route *routes)
+{
+    static_assert(LCREC_SK_GROUP_CLASSES == SK_SLAB + 1 && LCREC_SK_CLASS_SLAB == SK_SLAB && LCREC_SK_CLASS_BATCH == SK_BATCH, "lcrec.h");
+    memset(o, 0, sizeof *o);
+    const SkPlan p = sk_plan(K, offs, G);
+    o->slab_ok = p.slab_ok;
+    o->slab_doubles = p.slab_doubles;
+    for (int g = 0; g < G; ++g) {
+        const int64_t sz = offs[g + 1] - offs[g];
+        int cls = sz > 0 ? sk_class(sz, K) : -1;
+        if (cls == SK_SLAB && !p.slab_ok) cls = SK_BATCH;
+        if (routes) routes[g] = {cls, -1, 0};
+        if (cls == SK_BATCH) {
+            ++o->batch_groups;
+            if (sz > o->batch_biggest) o->batch_biggest = sz;
+        } else if (cls >= 0) {
+            ++o->cls[cls].groups;
+            if (sz > o->cls[cls].maxg) o->cls[cls].maxg = (int)sz;
+        }
+    }
+    // the reordered table: classes in order, offset order inside a class; slab slices are cumulative sk_group_doubles
+    int first = 0;
+    for (int cls = 0; cls <= SK_SLAB; ++cls) {
+        lcrec_sinkhorn_class_plan &c = o->cls[cls];
+        c.table_first = first;
+        c.threads = cls == SK_SLAB ? 1024 : SKS_THREADS;
+        if (!c.groups) continue;
+        c.lds_bytes = cls == SK_SLAB ? 0 : (int64_t)(sk_group_doubles(c.maxg, K) * sizeof(double));
+        c.set_attribute = c.lds_bytes > 48 * 1024;
+        c.label = kKernelNames[sk_trace_id(cls, c.maxg, K)];
+        if (routes) {
+            int64_t slab = 0;
+            int at = first;
+            for (int g = 0; g < G; ++g) {
+                if (routes[g].cls != cls) continue;
+                routes[g].position = at++;
+                routes[g].slab_offset = cls == SK_SLAB ? slab : 0;
+                if (cls == SK_SLAB) slab += (int64_t)sk_group_doubles(offs[g + 1] - offs[g], K);
+            }
+        }
+        first += c.groups;
+    }
+    o->table_groups = first;
+    o->transport = first == 0 ? LCREC_SK_TABLE_NONE : first <= SK_TABLE_ARG_GROUPS ? LCREC_SK_TABLE_ARGUMENT
+                   : has_context ? LCREC_SK_TABLE_RING : LCREC_SK_TABLE_SYNCHRONOUS;
+    // The size classes are independent (disjoint rows of idx_out).  The slab launch is a hundred or so long-running
+    // workgroups; with a context it goes to helper stream 0, forked from the caller's stream (and joined back), so the tens
+    // of thousands of short workgroups of the LDS classes fill the CUs it leaves idle.  Likewise the three larger LDS classes
+    // (thousands of mid-length workgroups, launches with long tails) go to helper stream 1 beside the pair/triple class on
+    // the caller's: 20 rounds at 1 M items 148 -> 130-140 ms.
+    const int n_mid = o->cls[1].groups + o->cls[2].groups + o->cls[3].groups;
+    const bool fork_slab = has_context && o->cls[SK_SLAB].groups > 0 && o->cls[0].groups + n_mid > 0;
+    const bool fork_mid = has_context && o->cls[0].groups > 0 && n_mid > 0;
+    o->fork_mask = (fork_slab ? 1 : 0) | (fork_mid ? 2 : 0);
+    o->workspace_bytes = (int64_t)sinkhorn_workspace(0, K, offs, G);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1690,55 +1776,68 @@ static int sinkhorn_big(const float *r, int64_t B, int e, const float *cb, int K
     return check_launch("sinkhorn kernels");
 }
 
-template <int E, bool GLOBALQ>
-static int launch_sk_small(const float *r, const float *cb, int K, const int64_t *triples_dev, int G, int maxg, double eps,
-                           int iters, int64_t *idx_out, int64_t idx_stride, double *qslab, hipStream_t stream)
+// One size class of a grouped call, by its plan record (sk_groups_plan).  runner_out != NULL: the debug instantiation.
+template <int E, bool GLOBALQ, bool DEBUG>
+static int launch_sk_small(const lcrec_sinkhorn_class_plan &c, int trace_id, const float *r, const float *cb, int K,
+                           const int64_t *triples_dev, double eps, int iters, int64_t *idx_out, int64_t idx_stride, double *qslab,
+                           int64_t *runner_out, double *ratio_out, hipStream_t stream)
 {
     constexpr int THREADS = GLOBALQ ? 1024 : SKS_THREADS;
-    const size_t lds = GLOBALQ ? 0 : sk_group_doubles(maxg, K) * sizeof(double);
-    auto kern = sk_small_kernel<E, GLOBALQ, THREADS>;
-    if (lds > 48 * 1024) {
-        hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds = (size_t)c.lds_bytes;
+    const void *kern = reinterpret_cast<const void *>(sk_small_kernel<E, GLOBALQ, THREADS, DEBUG>);
+    if (c.set_attribute) {
+        hipError_t he = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (he != hipSuccess) return fail(LCREC_EHIP, "sinkhorn: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(he));
     }
-    TraceScope trace(GLOBALQ ? K_SINKHORN_SLAB : (int64_t)maxg * K <= SKS_TINY ? K_SINKHORN_TINY : K_SINKHORN_SMALL, stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(THREADS), lds, stream, r, cb, K, triples_dev, eps, iters, idx_out,
-                       idx_stride, qslab);
+    TraceScope trace(trace_id, stream);
+    hipLaunchKernelGGL((sk_small_kernel<E, GLOBALQ, THREADS, DEBUG>), dim3((unsigned)c.groups), dim3(THREADS), lds, stream, r, cb, K,
+                       triples_dev, eps, iters, idx_out, idx_stride, qslab, runner_out, ratio_out);
     return check_launch("sk_small_kernel");
 }
 
-template <bool GLOBALQ>
-static int launch_sk_small_e(int e, const float *r, const float *cb, int K, const int64_t *triples_dev, int G, int maxg,
-                             double eps, int iters, int64_t *idx_out, int64_t idx_stride, double *qslab, hipStream_t stream)
+static int launch_sk_class(int cls, const lcrec_sinkhorn_class_plan &c, int e, const float *r, const float *cb, int K,
+                           const int64_t *triples_dev, double eps, int iters, int64_t *idx_out, int64_t idx_stride, double *qslab,
+                           int64_t *runner_out, double *ratio_out, hipStream_t stream)
 {
-    if (e == 16) return launch_sk_small<16, GLOBALQ>(r, cb, K, triples_dev, G, maxg, eps, iters, idx_out, idx_stride, qslab, stream);
-    if (e == 32) return launch_sk_small<32, GLOBALQ>(r, cb, K, triples_dev, G, maxg, eps, iters, idx_out, idx_stride, qslab, stream);
-    return launch_sk_small<64, GLOBALQ>(r, cb, K, triples_dev, G, maxg, eps, iters, idx_out, idx_stride, qslab, stream);
+    const int trace_id = sk_trace_id(cls, c.maxg, K);
+    auto go = [&](auto ec, auto slab, auto debug) {
+        return launch_sk_small<decltype(ec)::value, decltype(slab)::value != 0, decltype(debug)::value != 0>(
+            c, trace_id, r, cb, K, triples_dev, eps, iters, idx_out, idx_stride, qslab, runner_out, ratio_out, stream);
+    };
+    auto by_e = [&](auto slab, auto debug) {
+        return e == 16 ? go(IntC<16>{}, slab, debug) : e == 32 ? go(IntC<32>{}, slab, debug) : go(IntC<64>{}, slab, debug);
+    };
+    if (cls == SK_SLAB) return runner_out ? by_e(IntC<1>{}, IntC<1>{}) : by_e(IntC<1>{}, IntC<0>{});
+    return runner_out ? by_e(IntC<0>{}, IntC<1>{}) : by_e(IntC<0>{}, IntC<0>{});
 }
 
-struct SmallTable { static constexpr size_t CAP = 12; int64_t v[CAP]; };
+struct SmallTable { static constexpr size_t CAP = 3 * SK_TABLE_ARG_GROUPS; int64_t v[CAP]; };
 __global__ void write_table_kernel(int64_t *dst, SmallTable t, int count)
 {
     if ((int)threadIdx.x < count) dst[threadIdx.x] = t.v[threadIdx.x];
 }
 
+// runner_out / ratio_out: lcrec_debug_sinkhorn_groups only (NULL in production)
 int sinkhorn_assign(const float *r, int64_t n, int e, const float *cb, int K, const int64_t *offs, int G, double eps,
                     int iters, int64_t *idx_out, int64_t idx_stride, void *workspace, size_t workspace_bytes,
-                    lcrec_context *ctx, unsigned *ticket, hipStream_t stream)
+                    lcrec_context *ctx, unsigned *ticket, hipStream_t stream, int64_t *runner_out, double *ratio_out)
 {
     if (n == 0 || G == 0) return LCREC_OK;
     if (!r || !cb || !offs || !idx_out) return fail(LCREC_EINVAL, "sinkhorn_assign: NULL pointer");
+    if ((runner_out == nullptr) != (ratio_out == nullptr))
+        return fail(LCREC_EINVAL, "sinkhorn_assign: runner_out and ratio_out are given together");
     if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "sinkhorn_assign: e_dim=%d (supported: 16, 32, 64)", e);
     if (G < 0 || K < 1 || iters < 1 || !(eps > 0)) return fail(LCREC_EINVAL, "sinkhorn_assign: bad G/K/iters/eps");
-    if (G == 0) return LCREC_OK;
     if (int rc = check_context(ctx, "sinkhorn_assign")) return rc;
     if (offs[0] < 0 || offs[G] > n) return fail(LCREC_EINVAL, "sinkhorn_assign: group offsets outside [0, n]");
     for (int g = 0; g < G; ++g)
         if (offs[g + 1] < offs[g]) return fail(LCREC_EINVAL, "sinkhorn_assign: group offsets not ascending");
-    const size_t need = sinkhorn_workspace(n, K, offs, G);
+    lcrec_sinkhorn_groups_plan plan;
+    std::vector<lcrec_sinkhorn_group_route> route((size_t)G);
+    sk_groups_plan(K, offs, G, ctx != nullptr, &plan, route.data());
+    const size_t need = (size_t)plan.workspace_bytes;
     if (!workspace || workspace_bytes < need)
         return fail(LCREC_EWORKSPACE, "sinkhorn_assign: workspace %zu B < required %zu B", workspace_bytes, need);
-    const SkPlan plan = sk_plan(K, offs, G);
     char *ws = reinterpret_cast<char *>(workspace);
     int64_t *triples_dev = reinterpret_cast<int64_t *>(ws);
     ws += align_up((size_t)3 * G * sizeof(int64_t), 256);
@@ -1747,30 +1846,21 @@ int sinkhorn_assign(const float *r, int64_t n, int e, const float *cb, int K, co
 
     // Size classes, one launch each (see sk_class): four LDS allocations, then the slab; anything larger is a
     // batch-sized problem (below).
-    constexpr int NCLS = SK_SLAB + 1;
-    std::vector<int64_t> triples;
-    triples.reserve((size_t)3 * G);
-    int count[NCLS] = {0}, maxg[NCLS] = {0};
-    for (int cls = 0; cls < NCLS; ++cls) {
-        int64_t slab = 0;
+    if (plan.table_groups > 0) {
+        std::vector<int64_t> triples((size_t)3 * plan.table_groups);
         for (int g = 0; g < G; ++g) {
-            const int64_t sz = offs[g + 1] - offs[g];
-            if (sz <= 0 || sk_class(sz, K) != cls || (cls == SK_SLAB && !plan.slab_ok)) continue;
-            triples.push_back(offs[g]);
-            triples.push_back(offs[g + 1]);
-            triples.push_back(cls == SK_SLAB ? slab : 0);
-            if (cls == SK_SLAB) slab += (int64_t)sk_group_doubles(sz, K);
-            ++count[cls];
-            if (sz > maxg[cls]) maxg[cls] = (int)sz;
+            if (route[g].position < 0) continue;
+            int64_t *t = &triples[(size_t)3 * route[g].position];
+            t[0] = offs[g];
+            t[1] = offs[g + 1];
+            t[2] = route[g].slab_offset;
         }
-    }
-    if (!triples.empty()) {
         // Group table -> device.  With a context it goes through the context's pinned ring (the copy reads pinned memory
         // asynchronously; the slot is reused RING calls later), so the call returns without waiting; without one the
         // table is a host temporary and the copy has to be waited for.
         const size_t tbytes = sizeof(int64_t) * triples.size();
         hipError_t he;
-        if (triples.size() <= SmallTable::CAP) {
+        if (plan.transport == LCREC_SK_TABLE_ARGUMENT) {
             // a handful of groups (a small training batch is ONE): the table travels as a kernel argument -- no host
             // buffer whose lifetime matters, no wait, and safe to capture in a hipGraph (a captured copy would re-read a
             // host address on every replay)
@@ -1778,7 +1868,7 @@ int sinkhorn_assign(const float *r, int64_t n, int e, const float *cb, int K, co
             for (size_t i = 0; i < triples.size(); ++i) tb.v[i] = triples[i];
             hipLaunchKernelGGL(write_table_kernel, dim3(1), dim3(64), 0, stream, triples_dev, tb, (int)triples.size());
             he = hipGetLastError();
-        } else if (ctx) {
+        } else if (plan.transport == LCREC_SK_TABLE_RING) {
             int slot = -1;
             void *pin = ctx->ring_acquire(tbytes, &slot);
             if (!pin) return LCREC_EHIP;
@@ -1790,37 +1880,29 @@ int sinkhorn_assign(const float *r, int64_t n, int e, const float *cb, int K, co
             if (he == hipSuccess) he = hipStreamSynchronize(stream);
         }
         if (he != hipSuccess) return fail(LCREC_EHIP, "sinkhorn_assign: %s", hipGetErrorString(he));
-        // The size classes are independent (disjoint rows of idx_out).  The slab launch is a hundred or so long-running
-        // workgroups; with a context it goes to helper stream 0, forked from `stream` (and joined back on leaving this
-        // block), so the tens of thousands of short workgroups of the LDS classes fill the CUs it leaves idle.
-        // Likewise the three larger LDS classes (thousands of mid-length workgroups, launches with long tails) go to
-        // helper stream 1 beside the pair/triple class on the caller's: 20 rounds at 1 M items 148 -> 130-140 ms.
-        const int n_lds = count[0] + count[1] + count[2] + count[3];
-        const bool fork_slab = ctx && count[SK_SLAB] > 0 && n_lds > 0;
-        const bool fork_mid = ctx && count[0] > 0 && (count[1] + count[2] + count[3]) > 0;
-        if (fork_slab || fork_mid) {
+        // helper streams: see sk_groups_plan
+        if (plan.fork_mask) {
             if (int rc = ctx->ensure_streams()) return rc;
         }
-        ForkJoin fj(ctx, stream, (fork_slab ? 1u : 0u) | (fork_mid ? 2u : 0u));
-        const int64_t *t = triples_dev;
-        for (int cls = 0; cls < NCLS; ++cls) {
-            if (!count[cls]) continue;
+        ForkJoin fj(ctx, stream, (unsigned)plan.fork_mask);
+        for (int cls = 0; cls <= SK_SLAB; ++cls) {
+            const lcrec_sinkhorn_class_plan &c = plan.cls[cls];
+            if (!c.groups) continue;
             hipStream_t on = cls == SK_SLAB ? fj.on(0) : (cls > 0 ? fj.on(1) : stream);
-            int rc = cls == SK_SLAB ? launch_sk_small_e<true>(e, r, cb, K, t, count[cls], maxg[cls], eps, iters, idx_out, idx_stride, qslab, on)
-                                    : launch_sk_small_e<false>(e, r, cb, K, t, count[cls], maxg[cls], eps, iters, idx_out, idx_stride, nullptr, on);
-            if (rc) return rc;
-            t += (size_t)3 * count[cls];
-        }
-    }
-    // larger problems (a training batch) go through the multi-launch path, one at a time
-    for (int g = 0; g < G; ++g) {
-        const int64_t sz = offs[g + 1] - offs[g];
-        const int cls = sz > 0 ? sk_class(sz, K) : -1;
-        if (cls == SK_BATCH || (cls == SK_SLAB && !plan.slab_ok)) {
-            int rc = sinkhorn_big(r + offs[g] * e, sz, e, cb, K, eps, iters, idx_out + offs[g] * idx_stride, idx_stride, ws, ticket, stream);
+            int rc = launch_sk_class(cls, c, e, r, cb, K, triples_dev + (size_t)3 * c.table_first, eps, iters, idx_out, idx_stride,
+                                     cls == SK_SLAB ? qslab : nullptr, runner_out, ratio_out, on);
             if (rc) return rc;
         }
     }
+    // larger problems (a training batch) go through the batch-sized solver, one at a time
+    if (plan.batch_groups > 0)
+        for (int g = 0; g < G; ++g) {
+            if (route[g].cls != SK_BATCH) continue;
+            SkDebug dbg = {SKF_AUTO, runner_out ? runner_out + offs[g] : nullptr, ratio_out ? ratio_out + offs[g] : nullptr, 0};
+            int rc = sinkhorn_big(r + offs[g] * e, offs[g + 1] - offs[g], e, cb, K, eps, iters, idx_out + offs[g] * idx_stride, idx_stride,
+                                  ws, ticket, stream, runner_out ? &dbg : nullptr);
+            if (rc) return rc;
+        }
     return LCREC_OK;
 }
 
@@ -2126,7 +2208,36 @@ int debug_sinkhorn_batch(const float *r, int64_t n, int e, const float *cb, int 
     return rc;
 }
 
+int debug_sinkhorn_groups_plan(int K, const int64_t *offs, int G, int has_context, lcrec_sinkhorn_groups_plan *out,
+                               lcrec_sinkhorn_group_route *routes)
+{
+    if (!offs || !out) return fail(LCREC_EINVAL, "debug_sinkhorn_groups_plan: NULL pointer");
+    if (G < 0 || K < 1) return fail(LCREC_EINVAL, "debug_sinkhorn_groups_plan: bad G/K");
+    if (offs[0] < 0) return fail(LCREC_EINVAL, "debug_sinkhorn_groups_plan: group offsets outside [0, n]");
+    for (int g = 0; g < G; ++g)
+        if (offs[g + 1] < offs[g]) return fail(LCREC_EINVAL, "debug_sinkhorn_groups_plan: group offsets not ascending");
+    sk_groups_plan(K, offs, G, has_context != 0, out, routes);
+    return LCREC_OK;
+}
+
 }  // namespace lcrec
+
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_sinkhorn_groups_plan(int K, const int64_t *group_offsets, int n_groups,
+                                                                                      int has_context, lcrec_sinkhorn_groups_plan *out,
+                                                                                      lcrec_sinkhorn_group_route *routes)
+{
+    return lcrec::debug_sinkhorn_groups_plan(K, group_offsets, n_groups, has_context, out, routes);
+}
+
+extern "C" __attribute__((visibility("default"))) int lcrec_debug_sinkhorn_groups(const float *resid, int64_t n, int e, const float *codebook, int K,
+                                                                                 const int64_t *group_offsets, int n_groups, double epsilon,
+                                                                                 int iters, int64_t *idx_out, int64_t idx_stride, void *workspace,
+                                                                                 size_t workspace_bytes, lcrec_context *ctx, unsigned int *ticket,
+                                                                                 void *stream, int64_t *runner_out, double *ratio_out)
+{
+    return lcrec::sinkhorn_assign(resid, n, e, codebook, K, group_offsets, n_groups, epsilon, iters, idx_out, idx_stride, workspace,
+                                  workspace_bytes, ctx, ticket, (hipStream_t)stream, runner_out, ratio_out);
+}
 
 extern "C" __attribute__((visibility("default"))) int lcrec_debug_sinkhorn_plan(int64_t B, int K, int iters, int form, lcrec_sinkhorn_plan *out)
 {

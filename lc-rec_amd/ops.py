@@ -648,6 +648,63 @@ def sinkhorn_debug(resid, codebook, epsilon, iters, form=0, out=None, runner_out
     return out, runner_out, ratio_out, ran.value
 
 
+SK_TABLE_TRANSPORTS = {0: "none", 1: "argument", 2: "ring", 3: "synchronous"}
+
+
+def sinkhorn_groups_plan(K, group_offsets, has_context=True, routes=False):
+    """The launches lcrec_sinkhorn_assign makes for a group table (lcrec_debug_sinkhorn_groups_plan, the function it launches by),
+    as a dict of the fields of lcrec_sinkhorn_groups_plan (include/lcrec.h); "cls" is a list of five dicts.  routes=True adds
+    "routes": per group (class, position in the reordered table, slab offset).  Host only: no GPU is needed."""
+    import numpy as np
+    offs = np.ascontiguousarray(group_offsets, dtype=np.int64)
+    G = len(offs) - 1
+    plan = _lib.SinkhornGroupsPlan()
+    route = (_lib.SinkhornGroupRoute * max(G, 1))() if routes else None
+    rc = _lib.load().lcrec_debug_sinkhorn_groups_plan(int(K), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), G, int(bool(has_context)),
+                                                      ctypes.addressof(plan), ctypes.addressof(route) if routes else None)
+    _lib.check(rc, "lcrec_debug_sinkhorn_groups_plan")
+    out = {name: int(getattr(plan, name)) for name, _ in _lib.SinkhornGroupsPlan._fields_ if name != "cls"}
+    out["cls"] = [{name: (getattr(c, name).decode() if getattr(c, name) else None) if name == "label" else int(getattr(c, name))
+                   for name, _ in _lib.SinkhornClassPlan._fields_} for c in plan.cls]
+    if routes:
+        out["routes"] = [(int(route[g].cls), int(route[g].position), int(route[g].slab_offset)) for g in range(G)]
+    return out
+
+
+def sinkhorn_groups_debug(resid, codebook, epsilon, iters, group_offsets, out=None, runner_out=None, ratio_out=None, context=True):
+    """lcrec_debug_sinkhorn_groups: lcrec_sinkhorn_assign's launch code with the runner-up column and second / best of every
+    grouped row.  Returns (idx int64 [n], runner int64 [n], ratio double [n]); rows of no group keep what the outputs held (-1 /
+    NaN when they are made here).  context=False: the call is made with a NULL context."""
+    import numpy as np
+    lib = _lib.load()
+    resid = _dev(resid, "resid")
+    codebook = _dev(codebook, "codebook")
+    n, e = resid.shape
+    K = codebook.shape[0]
+    dev = resid.device
+    offs = np.ascontiguousarray(group_offsets, dtype=np.int64)
+    G = len(offs) - 1
+    if out is None:
+        out = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    out, stride = _idx_col(out, n)
+    if runner_out is None:
+        runner_out = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    if ratio_out is None:
+        ratio_out = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    for t, dt in ((runner_out, torch.int64), (ratio_out, torch.float64)):
+        if not t.is_cuda or t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
+            raise _lib.LcrecError("runner_out / ratio_out must be contiguous device vectors of length n (int64 / float64)")
+    oarr = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    with _on(dev):
+        nbytes = lib.lcrec_sinkhorn_assign_workspace(n, K, oarr, G)
+        ws = _workspace(nbytes, dev)
+        rc = lib.lcrec_debug_sinkhorn_groups(_ptr(resid), n, e, _ptr(codebook), K, oarr, G, float(epsilon), int(iters), _ptr(out), stride,
+                                             _ptr(ws), ws.numel(), _context(dev) if context else None, _ptr(_ticket(dev)), _stream_ptr(),
+                                             _ptr(runner_out), _ptr(ratio_out))
+    _lib.check(rc, "lcrec_debug_sinkhorn_groups")
+    return out, runner_out, ratio_out
+
+
 _deferred = None
 _deferred_raw = False
 _POISON_MSG = ("lcrec_sinkhorn_assign: grid barrier timed out (device oversubscribed?); "

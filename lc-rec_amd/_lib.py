@@ -1,231 +1,137 @@
 """ctypes binding of liblcrec_hip.so -- the C-ABI declared in include/lcrec.h.
 
+The header is the only statement of that ABI: parse_header() derives every signature, plan record and constant from its
+text, so an entry point or a field declared there needs nothing added here.
+
 There is no CPU fallback: if the library has not been built (or cannot be
 loaded) every entry point raises.  Build it with ``python -c "import
 __graft_entry__ as g; g.build()"`` or ``make -C lc-rec_amd/csrc``.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (first, so the HIP runtime torch ships is the one this library binds to)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LCREC_LIB_PATH") or os.path.join(_HERE, "csrc", "liblcrec_hip.so")   # override: diagnostic builds
-
-_f32p = ctypes.c_void_p
-_vp = ctypes.c_void_p
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lcrec.h")
 
 
 class LcrecError(RuntimeError):
     code = None                      # the LCREC_E* code of a refused library call (check); None: raised by the binding itself
 
 
-EUNSUPPORTED = -2                    # LCREC_EUNSUPPORTED of include/lcrec.h
+# ---- include/lcrec.h -> ctypes.  The header is plain C of a few forms (below); anything else is an error, never skipped.
+_SCALARS = {"int": ctypes.c_int, "unsigned int": ctypes.c_uint, "unsigned char": ctypes.c_ubyte, "char": ctypes.c_char,
+            "float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "size_t": ctypes.c_size_t}
+_NOT_CODE = re.compile(r"/\*.*?\*/|^#ifdef __cplusplus$.*?^#endif$", re.S | re.M)     # comments, the two extern "C" brackets
+_IGNORED_LINE = re.compile(r"#\s*(?:ifndef|endif|include)\b.*|#\s*define\s+\w+")        # the include guard, the includes
+_DEFINE = re.compile(r"#\s*define\s+(LCREC_\w+)\s+\(?\s*(-?\w+)\s*\)?")
+_FORMS = re.compile(r"\s*(?:enum\s*\{(?P<enum>[^{}]*)\}"
+                    r"|typedef\s+struct\s*\{(?P<fields>[^{}]*)\}\s*(?P<struct>lcrec_\w+)"
+                    r"|typedef\s+struct\s+(?P<opaque>lcrec_\w+)\s+(?P=opaque)"
+                    r"|(?P<ret>[\w\s*]+?)\b(?P<fn>lcrec_\w+)\s*\((?P<params>[^()]*)\))\s*;")
 
 
-_SIGNATURES = {
-    "lcrec_version": (ctypes.c_int, []),
-    "lcrec_last_error": (ctypes.c_char_p, []),
-    "lcrec_linear_forward": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
-                                            ctypes.c_int, _vp, _vp]),
-    "lcrec_linear_backward_splits": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
-    "lcrec_linear_backward_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
-    "lcrec_linear_backward": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
-                                             ctypes.c_size_t, _vp]),
-    "lcrec_linear_backward_weights_workspace": (ctypes.c_size_t, [_vp, ctypes.c_int]),
-    "lcrec_linear_backward_weights": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp]),
-    "lcrec_rq_assign_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                                    ctypes.c_int]),
-    "lcrec_context_create": (ctypes.c_int, [ctypes.POINTER(_vp)]),
-    "lcrec_context_destroy": (ctypes.c_int, [_vp]),
-    "lcrec_context_set_pipelines": (ctypes.c_int, [_vp, ctypes.c_int]),
-    "lcrec_rq_assign": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int),
-                                       ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_float,
-                                       _vp, ctypes.c_size_t, _vp, _vp]),
-    "lcrec_encode_assign_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
-                                                        ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
-    "lcrec_encode_assign_chunk_rows": (ctypes.c_int64, []),
-    "lcrec_encode_assign": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
-                                           ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                           ctypes.POINTER(_vp), _vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
-                                           _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, ctypes.c_size_t, _vp,
-                                           _vp]),
-    "lcrec_sinkhorn_assign_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int,
-                                                          ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),
-    "lcrec_sinkhorn_assign": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int,
-                                             ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_double,
-                                             ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
-    "lcrec_rq_apply_level": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, _vp,
-                                            ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp]),
-    "lcrec_code_stats": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                        _vp, _vp, _vp]),
-    "lcrec_code_stats_levels": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                               ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                               ctypes.POINTER(_vp), ctypes.c_float, ctypes.c_float, _vp]),
-    "lcrec_ema_update": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_float,
-                                        ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp]),
-    "lcrec_bn_relu_forward": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp,
-                                             _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
-    "lcrec_bn_relu_backward": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp,
-                                              _vp, _vp, _vp, _vp, _vp, _vp]),
-    "lcrec_linear_bn_forward_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
-    "lcrec_linear_bn_forward": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
-                                               ctypes.c_int, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
-                                               _vp, ctypes.c_size_t, _vp, _vp]),
-    "lcrec_bn_stats": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
-    "lcrec_bn_relu_apply": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
-    "lcrec_bn_backward_reduce": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp,
-                                                _vp]),
-    "lcrec_bn_merge_stats": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
-    "lcrec_bn_backward_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp, _vp,
-                                               ctypes.c_float, _vp, _vp, _vp]),
-    "lcrec_relu_bias_backward": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
-    "lcrec_train_reduce_workspace": (ctypes.c_size_t, []),
-    "lcrec_recon_loss_grad": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp,
-                                             _vp]),
-    "lcrec_grad_norm_clip": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp, _vp]),
-    "lcrec_codebook_grad": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp, _vp]),
-    "lcrec_step_losses": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp,
-                                         _vp, _vp, _vp, _vp]),
-    "lcrec_quantizer_input_grad": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_float,
-                                                  ctypes.c_float, _vp, _vp, _vp]),
-    "lcrec_quantizer_input_grad_bias": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_float,
-                                                       ctypes.c_float, _vp, _vp, _vp, _vp]),
-    "lcrec_adamw_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_double, ctypes.c_double,
-                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp]),
-    "lcrec_sgd_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_double, ctypes.c_double,
-                                      ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                      _vp, _vp, _vp, _vp]),
-    "lcrec_adagrad_step": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                          ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp]),
-    "lcrec_rmsprop_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_double, ctypes.c_double,
-                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
-                                          ctypes.c_int64, _vp, _vp, _vp, _vp]),
-    "lcrec_dropout_apply": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, _vp, _vp, ctypes.c_int,
-                                           ctypes.c_int64, _vp]),
-    "lcrec_dropout_mask": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.c_int, ctypes.c_int64, _vp]),
-    "lcrec_cast_rows": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
-    "lcrec_collision_groups_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
-    "lcrec_collision_groups": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp,
-                                              _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    "lcrec_finish_nearest_free": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp, ctypes.c_int, _vp,
-                                                 _vp, _vp, ctypes.c_int64, _vp, _vp]),
-    "lcrec_extend_nearest_free": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp,
-                                                 ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
-    "lcrec_spill_nearest_free_workspace": (ctypes.c_size_t, [ctypes.c_int64]),
-    "lcrec_spill_nearest_free": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp, _vp,
-                                                ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp,
-                                                ctypes.c_size_t, _vp]),
-    "lcrec_index_json_bound": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
-    "lcrec_index_json_format": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int64]),
-    "lcrec_index_json_parse": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64]),
-    "lcrec_trace_enable": (ctypes.c_int, [ctypes.c_int]),
-    "lcrec_trace_collect": (ctypes.c_int, [_vp, ctypes.c_int]),
-    "lcrec_debug_sinkhorn_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
-    "lcrec_debug_sinkhorn_batch": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
-                                                  _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp, _vp,
-                                                  ctypes.POINTER(ctypes.c_int)]),
-    "lcrec_debug_sinkhorn_groups_plan": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int, _vp, _vp]),
-    "lcrec_debug_sinkhorn_groups": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int,
-                                                   ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_double,
-                                                   ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp]),
-    "lcrec_debug_rq_assign_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
-                                                  ctypes.c_int, ctypes.c_int, _vp]),
-    "lcrec_debug_rq_assign": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int),
-                                             ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_float,
-                                             _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "lcrec_debug_bn_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
-    "lcrec_debug_step_tail_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
-    "lcrec_debug_linear_forward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
-    "lcrec_debug_linear_backward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
-                                                        ctypes.c_int]),
-    "lcrec_debug_linear_backward_weights_plan": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
-    "lcrec_debug_linear_bn_forward_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
-}
+def _integer(text, constants, what):
+    try:
+        return constants[text] if text in constants else int(text, 0)
+    except ValueError:
+        raise LcrecError(f"include/lcrec.h: {what}: `{text}` is neither a number nor a constant defined above it") from None
 
 
-class DwProblem(ctypes.Structure):
-    """lcrec_dw_problem of include/lcrec.h"""
-    _fields_ = [("gy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("gw", ctypes.c_void_p), ("n", ctypes.c_int64),
-                ("in_dim", ctypes.c_int), ("out_dim", ctypes.c_int), ("x_scale", ctypes.c_void_p), ("x_shift", ctypes.c_void_p),
-                ("x_relu", ctypes.c_int), ("splits", ctypes.c_int)]
+def _declarator(text, base, known, what):
+    """`[const] type [*[const]]... name[[length]]`, the type being `base` after a comma -> (type, is pointer, name, length)."""
+    m = re.fullmatch(r"(.*?)(\w+)\s*(?:\[\s*(\w+)\s*\])?", text.strip(), re.S)
+    stem = " ".join(re.sub(r"\*|\bconst\b", " ", m.group(1)).split()) if m else ""
+    if not m or not (stem or base) or (stem and stem not in known):
+        raise LcrecError(f"include/lcrec.h: {what}: cannot type `{' '.join(text.split())}`")
+    return stem or base, "*" in m.group(1), m.group(2), m.group(3)
 
 
-class SinkhornPlan(ctypes.Structure):
-    """lcrec_sinkhorn_plan of include/lcrec.h"""
-    _fields_ = [("form", ctypes.c_int), ("cpl", ctypes.c_int), ("rw", ctypes.c_int), ("workgroups", ctypes.c_int),
-                ("sets", ctypes.c_int), ("rows_per_workgroup", ctypes.c_int), ("padded_columns", ctypes.c_int),
-                ("ragged_wave", ctypes.c_int), ("ragged_workgroup", ctypes.c_int), ("batch_route", ctypes.c_int),
-                ("workspace_bytes", ctypes.c_int64)]
+def parse_header(text):
+    """(constants, structs, signatures) of the text of include/lcrec.h: {LCREC_X: int} from the #defines and enumerators,
+    {lcrec_x: ctypes.Structure subclass} in header order, {lcrec_fn: (restype, [argtypes])} in header order.  Every pointer
+    is c_void_p, except that a `const char *` field or return is c_char_p.  Raises LcrecError naming the declaration for a
+    type outside _SCALARS and the records declared above it, and for file-scope text that is no #define, enum, record or
+    prototype."""
+    constants, structs, signatures = {}, {}, {}
+    known = dict(_SCALARS, void=None)
+    lines = _NOT_CODE.sub(lambda m: " " + "\n" * m.group().count("\n"), text).split("\n")
+    for i, line in enumerate(lines):
+        line = line.strip()
+        if line.startswith("#"):
+            m = _DEFINE.fullmatch(line)
+            if m:
+                constants[m.group(1)] = _integer(m.group(2), constants, f"#define {m.group(1)}")
+            elif not _IGNORED_LINE.fullmatch(line):
+                raise LcrecError(f"include/lcrec.h line {i + 1}: `{line}` is not a form this binding reads")
+            lines[i] = ""
+    text, pos = "\n".join(lines).rstrip(), 0
+    while pos < len(text):
+        m = _FORMS.match(text, pos)
+        if not m:
+            raise LcrecError("include/lcrec.h: not a #define, enum, record or prototype (or its semicolon is missing): `"
+                             + " ".join(text[pos:].split(";")[0].split())[:120] + "`")
+        pos = m.end()
+        if m.group("enum") is not None:
+            value = -1
+            for item in filter(None, (s.strip() for s in m.group("enum").split(","))):
+                name, _, given = (s.strip() for s in item.partition("="))
+                value = _integer(given, constants, f"enumerator {name}") if given else value + 1
+                constants[name] = value
+        elif m.group("struct"):
+            name, fields = m.group("struct"), []
+            for decl in filter(None, (s.strip() for s in m.group("fields").split(";"))):
+                base = None
+                for part in decl.split(","):
+                    base, pointer, field, length = _declarator(part, base, known, f"{name}, field `{decl}`")
+                    ctype = (ctypes.c_char_p if base == "char" else ctypes.c_void_p) if pointer else known[base]
+                    if ctype is None:
+                        raise LcrecError(f"include/lcrec.h: {name}, field `{decl}`: {base} has no size")
+                    fields.append((field, ctype * _integer(length, constants, f"{name}.{field}") if length else ctype))
+            structs[name] = known[name] = type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"{name} of include/lcrec.h"})
+        elif m.group("opaque"):
+            known[m.group("opaque")] = None
+        else:
+            name, params = m.group("fn"), m.group("params").strip()
+            base, pointer, _, _ = _declarator(m.group("ret") + " result", None, known, f"{name}, return type")
+            if base != "char" if pointer else base != "void" and base not in _SCALARS:
+                raise LcrecError(f"include/lcrec.h: {name}: cannot return `{m.group('ret').strip()}`")
+            argtypes = []
+            for part in ([] if params == "void" else params.split(",")):
+                kind, is_pointer, _, length = _declarator(part, None, known, name)
+                if length or not (is_pointer or kind in _SCALARS):
+                    raise LcrecError(f"include/lcrec.h: {name}: cannot pass `{' '.join(part.split())}`")
+                argtypes.append(ctypes.c_void_p if is_pointer else _SCALARS[kind])
+            signatures[name] = (ctypes.c_char_p if pointer else _SCALARS.get(base), argtypes)
+    return constants, structs, signatures
 
 
-SK_GROUP_CLASSES = 5                 # LCREC_SK_GROUP_CLASSES of include/lcrec.h
-
-
-class SinkhornClassPlan(ctypes.Structure):
-    """lcrec_sinkhorn_class_plan of include/lcrec.h"""
-    _fields_ = [("groups", ctypes.c_int), ("maxg", ctypes.c_int), ("lds_bytes", ctypes.c_int64), ("set_attribute", ctypes.c_int),
-                ("threads", ctypes.c_int), ("table_first", ctypes.c_int), ("label", ctypes.c_char_p)]
-
-
-class SinkhornGroupsPlan(ctypes.Structure):
-    """lcrec_sinkhorn_groups_plan of include/lcrec.h"""
-    _fields_ = [("cls", SinkhornClassPlan * SK_GROUP_CLASSES), ("slab_ok", ctypes.c_int), ("slab_doubles", ctypes.c_int64),
-                ("batch_groups", ctypes.c_int), ("batch_biggest", ctypes.c_int64), ("table_groups", ctypes.c_int),
-                ("transport", ctypes.c_int), ("fork_mask", ctypes.c_int), ("workspace_bytes", ctypes.c_int64)]
-
-
-class SinkhornGroupRoute(ctypes.Structure):
-    """lcrec_sinkhorn_group_route of include/lcrec.h"""
-    _fields_ = [("cls", ctypes.c_int), ("position", ctypes.c_int), ("slab_offset", ctypes.c_int64)]
-
-
-MAX_LEVELS = 16                      # LCREC_MAX_LEVELS of include/lcrec.h
-
-
-class RqPlan(ctypes.Structure):
-    """lcrec_rq_plan of include/lcrec.h"""
-    _fields_ = [("split", ctypes.c_int), ("threads", ctypes.c_int), ("grid", ctypes.c_int), ("tiles", ctypes.c_int64),
-                ("trips_max", ctypes.c_int64), ("trips_min", ctypes.c_int64), ("launches", ctypes.c_int),
-                ("l0", ctypes.c_int * MAX_LEVELS), ("l1", ctypes.c_int * MAX_LEVELS), ("rows", ctypes.c_int * MAX_LEVELS),
-                ("lds_bytes", ctypes.c_int64 * MAX_LEVELS), ("row_off", ctypes.c_int * MAX_LEVELS),
-                ("blocks_per_wave", ctypes.c_int * MAX_LEVELS), ("idle_waves", ctypes.c_int * MAX_LEVELS),
-                ("handover_reuse", ctypes.c_int)]
-
-
-class BnPlan(ctypes.Structure):
-    """lcrec_bn_plan of include/lcrec.h"""
-    _fields_ = [("float4", ctypes.c_int), ("cols", ctypes.c_int), ("rows_per_lane", ctypes.c_int), ("cached", ctypes.c_int), ("grid", ctypes.c_int),
-                ("xcd_order", ctypes.c_int)]
-
-
-class StepTailPlan(ctypes.Structure):
-    """lcrec_step_tail_plan of include/lcrec.h"""
-    _fields_ = [("K", ctypes.c_int), ("family", ctypes.c_int), ("grid", ctypes.c_int), ("grid_sse", ctypes.c_int), ("cols", ctypes.c_int),
-                ("xcd_order", ctypes.c_int), ("vec16", ctypes.c_int), ("second_launch", ctypes.c_int), ("tail", ctypes.c_int64)]
-
-
-class GemmLaunch(ctypes.Structure):
-    """lcrec_gemm_launch of include/lcrec.h"""
-    _fields_ = [("label", ctypes.c_char_p), ("role", ctypes.c_int), ("family", ctypes.c_int), ("tile_rows", ctypes.c_int),
-                ("tile_cols", ctypes.c_int), ("fast", ctypes.c_int), ("a_kmajor", ctypes.c_int), ("w_kmajor", ctypes.c_int),
-                ("pro", ctypes.c_int), ("stats", ctypes.c_int), ("register_buffered", ctypes.c_int), ("m", ctypes.c_int64),
-                ("n", ctypes.c_int), ("k", ctypes.c_int), ("k_tiles", ctypes.c_int), ("runs", ctypes.c_int),
-                ("k_tiles_per_run", ctypes.c_int), ("k_tiles_last_run", ctypes.c_int), ("last_k_valid", ctypes.c_int),
-                ("tiles", ctypes.c_int), ("virtual_tiles", ctypes.c_int), ("workgroups", ctypes.c_int), ("wg_start", ctypes.c_int),
-                ("last_panel_rows", ctypes.c_int), ("last_tile_cols", ctypes.c_int), ("vector_stores", ctypes.c_int),
-                ("chunk_row_tiles", ctypes.c_int), ("chunks", ctypes.c_int), ("total4", ctypes.c_int64), ("row0", ctypes.c_int64),
-                ("form", ctypes.c_int), ("steady_iterations", ctypes.c_int), ("list_min", ctypes.c_int), ("list_max", ctypes.c_int),
-                ("empty_workgroups", ctypes.c_int), ("single_tile_workgroups", ctypes.c_int), ("ragged_handed_over", ctypes.c_int)]
-
-
-class TraceEntry(ctypes.Structure):
-    _fields_ = [("kernel", ctypes.c_char_p), ("launches", ctypes.c_int64), ("total_ms", ctypes.c_double)]
-
+try:
+    with open(HEADER_PATH) as _f:
+        CONSTANTS, STRUCTS, _SIGNATURES = parse_header(_f.read())
+except OSError as exc:
+    raise LcrecError(f"cannot read {HEADER_PATH}: {exc}") from exc
 
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 3                      # LCREC_ABI_VERSION of include/lcrec.h this binding was written against
+ABI_VERSION = CONSTANTS["LCREC_ABI_VERSION"]
+EUNSUPPORTED = CONSTANTS["LCREC_EUNSUPPORTED"]
+MAX_LEVELS = CONSTANTS["LCREC_MAX_LEVELS"]
+SK_GROUP_CLASSES = CONSTANTS["LCREC_SK_GROUP_CLASSES"]
+
+DwProblem = STRUCTS["lcrec_dw_problem"]
+SinkhornPlan = STRUCTS["lcrec_sinkhorn_plan"]
+SinkhornClassPlan = STRUCTS["lcrec_sinkhorn_class_plan"]
+SinkhornGroupsPlan = STRUCTS["lcrec_sinkhorn_groups_plan"]
+SinkhornGroupRoute = STRUCTS["lcrec_sinkhorn_group_route"]
+RqPlan = STRUCTS["lcrec_rq_plan"]
+BnPlan = STRUCTS["lcrec_bn_plan"]
+StepTailPlan = STRUCTS["lcrec_step_tail_plan"]
+GemmLaunch = STRUCTS["lcrec_gemm_launch"]
+TraceEntry = STRUCTS["lcrec_trace_entry"]
 
 _lib = None
 

@@ -6,6 +6,8 @@ stream.  Inputs must already live on a HIP device; nothing here computes on
 the CPU.
 """
 import ctypes
+import functools
+import threading
 
 import torch
 
@@ -197,9 +199,21 @@ def linear_forward(x, weight, bias=None, bn_scale=None, bn_shift=None, relu=Fals
 
 
 def linear_bn_supported(n, in_dim, out_dim):
-    """Whether lcrec_linear_bn_forward takes this shape (a batch-sized launch; include/lcrec.h)."""
-    return (n >= 2 and in_dim % 32 == 0 and out_dim % 4 == 0 and out_dim <= 4096
-            and ((n + 127) // 128) * ((out_dim + 127) // 128) < 512 and in_dim * 4 * (n + 128) < (1 << 31))
+    """Whether lcrec_linear_bn_forward takes this shape (a batch-sized launch; include/lcrec.h), input fold and batch
+    statistics both asked for.  The library is asked (lcrec_debug_linear_bn_forward_plan, the function the entry point
+    launches by), not a copy of its rule: a host-only call, nothing is launched and no device is needed.  A refusal writes the
+    last-error text of the thread that asked, and a question is no error of the caller's: each shape is asked once, on a
+    thread of its own, and remembered (the training engine asks for every layer of every eager step)."""
+    return _linear_bn_supported(int(n), int(in_dim), int(out_dim))
+
+
+@functools.lru_cache(maxsize=None)
+def _linear_bn_supported(n, in_dim, out_dim):
+    plan, answer = _lib.load().lcrec_debug_linear_bn_forward_plan, []
+    asker = threading.Thread(target=lambda: answer.append(plan(n, in_dim, out_dim, 1, 1, ctypes.byref(_lib.GemmLaunch())) == 1))
+    asker.start()
+    asker.join()
+    return answer[0]
 
 
 def linear_bn_forward(x, weight, bias, in_fold=None, in_relu=True, bn=None):
@@ -1439,7 +1453,7 @@ def dropout_mask(shape, p, seed, step, position, row_offset=0, device=None):
     return keep
 
 
-_CAST_DTYPES = {torch.float16: 1, torch.float64: 2}       # LCREC_DTYPE_F16 / LCREC_DTYPE_F64 of include/lcrec.h
+_CAST_DTYPES = {torch.float16: _lib.CONSTANTS["LCREC_DTYPE_F16"], torch.float64: _lib.CONSTANTS["LCREC_DTYPE_F64"]}
 
 
 def cast_rows(src, out=None):
@@ -1477,3 +1491,17 @@ def trace_collect():
     if n < 0:
         _lib.check(n, "lcrec_trace_collect")
     return {buf[i].kernel.decode(): (int(buf[i].launches), float(buf[i].total_ms)) for i in range(n)}
+
+
+def _check_names(constants):
+    """The display-name tables above against the header's enumerators of their prefix (`constants` of _lib.parse_header): one
+    name per enumerator, numbered 0 .. len-1 -- so an enumerator added in C without its name here fails at import."""
+    for what, names, prefix in (("GEMM_ROLES", GEMM_ROLES, "LCREC_GEMMR_"), ("GEMM_FAMILIES", GEMM_FAMILIES, "LCREC_GEMMK_"),
+                                ("BN_CALLS", BN_CALLS, "LCREC_BN_"), ("TAIL_CALLS", TAIL_CALLS, "LCREC_TAIL_"),
+                                ("TAIL_FAMILIES", TAIL_FAMILIES, "LCREC_TAILK_"), ("SK_TABLE_TRANSPORTS", SK_TABLE_TRANSPORTS, "LCREC_SK_TABLE_")):
+        declared = {k: v for k, v in constants.items() if k.startswith(prefix)}
+        if sorted(declared.values()) != (sorted(names) if isinstance(names, dict) else list(range(len(names)))):
+            raise _lib.LcrecError(f"ops.{what} names {len(names)} values, include/lcrec.h declares {prefix}* as {declared}")
+
+
+_check_names(_lib.CONSTANTS)

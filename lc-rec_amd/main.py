@@ -11,6 +11,7 @@ non-empty value -- including the `--bn False` in index/run.sh:9 -- parses as Tru
 """
 import argparse
 import logging
+import os
 import random
 
 import numpy as np
@@ -21,7 +22,7 @@ from .rqvae import RQVAE
 from .trainer import Trainer
 
 
-def parse_args(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser(description="Index")
 
     parser.add_argument('--lr', type=float, default=1e-3, help='learning rate')
@@ -79,7 +80,31 @@ def parse_args(argv=None):
                              "multi-rank step has not been run on more than one GPU yet (DESIGN.md section 6)")
     parser.add_argument("--kmeans_impl", type=str, default="sklearn", choices=["sklearn", "device"],
                         help="sklearn = the reference's host KMeans call; device = k-means++/Lloyd in HBM")
-    args = parser.parse_args(argv)
+    parser.add_argument("--save_state", action="store_true",
+                        help="write <run dir>/train_state.pth after every evaluation epoch and at the end: what --resume "
+                             "needs beyond a checkpoint to continue the run bit for bit")
+    parser.add_argument("--resume", type=str, default=None, metavar="RUN_DIR",
+                        help="continue the run in RUN_DIR (or the train_state.pth given) after its last finished epoch, with "
+                             "its saved configuration; only --epochs, --device, --data_path, --save_limit and "
+                             "--stop_after_epoch may differ")
+    parser.add_argument("--stop_after_epoch", type=int, default=None, metavar="K",
+                        help="return cleanly after K epochs (epoch index K-1) of a run that is configured for --epochs")
+    parser.add_argument("--init_from", type=str, default=None, metavar="CKPT",
+                        help="start from the weights of a checkpoint or state file (same architecture) instead of k-means / "
+                             "random codebooks; optimizer, schedule, epoch counter and run directory are fresh")
+    return parser
+
+
+def given_flags(argv=None):
+    """The dests that `argv` sets itself, as opposed to those left at their defaults."""
+    parser = build_parser()
+    for action in parser._actions:
+        action.default = argparse.SUPPRESS
+    return set(vars(parser.parse_args(argv)))
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
     from . import layers
     layers.KMEANS_IMPL = args.kmeans_impl
     if args.no_bn:
@@ -112,6 +137,19 @@ def build_model(args, in_dim):
 def main(argv=None):
     seed_everything(2024)
     args = parse_args(argv)
+    from . import train_state
+    if args.resume and args.init_from:
+        raise ValueError("--resume and --init_from exclude each other: a resumed run keeps its own weights")
+    state = run_dir = None
+    if args.resume:
+        path = train_state.locate(args.resume)
+        state, run_dir = train_state.load(path), os.path.dirname(os.path.abspath(path))
+        args = train_state.resume_args(state["args"], args, given_flags(argv))     # (raises before any data is read)
+        from . import layers
+        layers.KMEANS_IMPL = args.kmeans_impl
+        if args.epochs != state["args"].epochs and str(args.lr_scheduler_type).lower() == "linear":
+            logging.getLogger().warning("--resume: --epochs %d instead of %d moves the end of the linear schedule's decay",
+                                        args.epochs, state["args"].epochs)
     print("=================================================")
     print(args)
     print("=================================================")
@@ -119,9 +157,18 @@ def main(argv=None):
 
     from . import dist as ldist
     ctx = ldist.init_from_env(args)          # single process unless launched under torchrun
+    train_state.refuse_ranks(args, ctx.world_size)
+    if state is not None:
+        train_state.check_world(state, ctx.world_size)
     # to a GPU the file goes from the page cache through the pinned ring of EmbDataset.to_device: no host copy of the matrix
     data = EmbDataset(args.data_path, mmap=str(args.device).startswith("cuda"))
+    if state is not None:
+        train_state.check_data(state, len(data), int(data.dim))
     model = build_model(args, data.dim)
+    if args.init_from:
+        model.load_state_dict(train_state.init_weights(args.init_from, args, data.dim))
+        for q in model.rq.vq_layers:
+            q.initted = True                      # the codebooks are the file's: no k-means on the first batch
     if getattr(args, "reset_seed", None) is not None and str(args.device).startswith("cuda"):
         for l, q in enumerate(model.rq.vq_layers):      # one stream of draws per level, the same on every rank
             q.reset_generator = torch.Generator(device=args.device).manual_seed(int(args.reset_seed) + l)
@@ -129,8 +176,10 @@ def main(argv=None):
         print(model)
     loader = DeviceLoader(data, batch_size=args.batch_size, shuffle=True, device=args.device, rank=ctx.rank,
                           world_size=ctx.world_size)
-    trainer = Trainer(args, model, len(loader))
+    trainer = Trainer(args, model, len(loader), run_dir=run_dir, data_shape=(len(data), int(data.dim)))
     ldist.attach(trainer, ctx)
+    if state is not None:
+        train_state.restore(trainer, state)       # last: the generators, so nothing draws between here and the first step
     best_loss, best_collision_rate = trainer.fit(loader)
     if ctx.rank == 0:
         print("Best Loss", best_loss)

@@ -73,7 +73,9 @@ class CheckpointKeeper:
 
 class Trainer(object):
 
-    def __init__(self, args, model, data_num):
+    def __init__(self, args, model, data_num, run_dir=None, data_shape=None):
+        """run_dir: continue in this run directory (main.py --resume) instead of making a time-stamped one.
+        data_shape: (rows, columns) of the data file, for the state file (train_state.py)."""
         self.args = args
         self.model = model
         self.logger = logging.getLogger()
@@ -90,8 +92,16 @@ class Trainer(object):
         self.keeper = CheckpointKeeper(self.save_limit)
         self.eval_step = min(args.eval_step, self.epochs)
         self.device = torch.device(args.device)
-        self.ckpt_dir = os.path.join(args.ckpt_dir, "{}".format(get_local_time()))
+        self.ckpt_dir = run_dir if run_dir is not None else os.path.join(args.ckpt_dir, "{}".format(get_local_time()))
         ensure_dir(self.ckpt_dir)
+        # <run dir>/train_state.pth (train_state.py): written under --save_state and by a run that was itself resumed
+        self.save_state = bool(getattr(args, "save_state", False)) or run_dir is not None
+        self.stop_after_epoch = getattr(args, "stop_after_epoch", None)
+        self.data_shape = data_shape
+        self.start_epoch = 0            # train_state.restore moves these four
+        self.cur_eval_step = 0
+        self.dropout_seed = None        # the engine's dropout seed of the run being continued (None: the engine draws one)
+        self.resumed_engine = None      # whether that run trained on the engine
 
         self.best_loss = np.inf
         self.best_collision_rate = np.inf
@@ -189,11 +199,15 @@ class Trainer(object):
                 kind = "linear" if self.lr_scheduler_type.lower() == "linear" else "constant"
                 self.engine = TrainEngine(self.model, self.optimizer, kind, self.warmup_steps, self.max_steps,
                                           use_ema=self.use_ema, dist=self.dist,
-                                          dp_graph=getattr(self.args, "dp_graph", "auto"), scheduler=self.scheduler)
+                                          dp_graph=getattr(self.args, "dp_graph", "auto"), scheduler=self.scheduler,
+                                          dropout_seed=self.dropout_seed)
                 self.logger.info("training step: %s (lcrec_amd.engine)", "one captured hipGraph per batch size"
                                  if self.engine.use_graph else "the engine's straight line, launched eagerly")
             else:
                 self.logger.info("training step: autograd path (%s)", reason)
+            if self.resumed_engine is not None and self.resumed_engine != (self.engine is not None):
+                was, now = (("the engine", "the autograd path") if self.resumed_engine else ("the autograd path", "the engine"))
+                raise ValueError(f"--resume: the saved run trained on {was}, this one would train on {now}")
         return self.engine
 
     def _reducer(self):
@@ -338,9 +352,16 @@ class Trainer(object):
     def _is_main(self):
         return self.dist is None or self.dist.rank == 0
 
+    def _write_state(self, epoch):
+        if self.save_state and self._is_main():
+            from . import train_state
+            train_state.write(self.ckpt_dir, train_state.capture(self, epoch))
+
     def fit(self, data):
-        cur_eval_step = 0
-        for epoch_idx in range(self.epochs):
+        # --stop_after_epoch K: the run is configured for self.epochs (the linear schedule's end), and ends after epoch K-1
+        stop = self.epochs if self.stop_after_epoch is None else min(self.epochs, self.stop_after_epoch)
+        last_epoch = self.start_epoch - 1
+        for epoch_idx in range(self.start_epoch, stop):
             t0 = time()
             train_loss, train_recon_loss = self._train_epoch(data, epoch_idx)
             t1 = time()
@@ -356,10 +377,10 @@ class Trainer(object):
                     self._save_checkpoint(epoch=epoch_idx, ckpt_file=self.best_loss_ckpt)
                 if collision_rate < self.best_collision_rate:
                     self.best_collision_rate = collision_rate
-                    cur_eval_step = 0
+                    self.cur_eval_step = 0
                     self._save_checkpoint(epoch_idx, collision_rate=collision_rate, ckpt_file=self.best_collision_ckpt)
                 else:
-                    cur_eval_step += 1
+                    self.cur_eval_step += 1
 
                 v1 = time()
                 if avg_util is None:
@@ -378,6 +399,11 @@ class Trainer(object):
                 ckpt_path = self._save_checkpoint(epoch_idx, collision_rate=collision_rate)
                 if self._is_main():
                     self.keeper.add(collision_rate, ckpt_path)
+                self._write_state(epoch_idx)
+            last_epoch = epoch_idx
+        if stop < self.epochs:
+            self.logger.info("--stop_after_epoch %d: %d of %d epochs done", self.stop_after_epoch, last_epoch + 1, self.epochs)
+        self._write_state(last_epoch)
         if self.engine is not None:
             self.engine.release()            # captured graphs go now, in order, not at interpreter teardown
         return self.best_loss, self.best_collision_rate

@@ -3,7 +3,7 @@
 the reference's CPU path does ~7-12 k items/s at batch 2048).
 
     python tools/train_probe.py [--in_dim 768] [--batch 2048] [--steps 30] [--bn] [--ema] [--learner AdamW|Adam|SGD|Adagrad|RMSprop]
-                                 [--dropout P]
+                                 [--dropout P] [--trainer [--save_state]]
 """
 import argparse
 import os
@@ -65,6 +65,22 @@ def trainer_probe(a):
             pstats.Stats(prof).sort_stats("tottime").print_stats(30)
         steps = epochs * len(loader)
         eng = trainer.engine
+        if a.save_state:
+            # what --save_state adds to an evaluation epoch: one train_state.pth (weights, moments, generator states),
+            # beside what the epoch's checkpoint -- the same tensors, the reference's six keys -- costs anyway
+            from lcrec_amd import train_state
+            costs = {"checkpoint": [], "train_state": []}
+            for _ in range(5):
+                t1 = time.perf_counter()
+                path = trainer._save_checkpoint(epoch=0, ckpt_file="probe.pth")
+                t2 = time.perf_counter()
+                state_path = train_state.write(trainer.ckpt_dir, train_state.capture(trainer, 0))
+                t3 = time.perf_counter()
+                costs["checkpoint"].append(t2 - t1)
+                costs["train_state"].append(t3 - t2)
+            print("state file: " + ", ".join(f"{k} {min(v) * 1e3:.1f} ms (median {sorted(v)[len(v) // 2] * 1e3:.1f}) "
+                                             f"for {os.path.getsize(f) / 1e6:.1f} MB" for (k, v), f in
+                                             zip(costs.items(), (path, state_path))))
         if ctx is not None:
             ldist.shutdown(ctx)
         print(f"Trainer._train_epoch{' [one-rank RCCL group, %d collectives/step]' % (eng.collectives // 2 if eng is not None else -1) if a.rccl1 else ''}: "
@@ -88,6 +104,8 @@ def main():
     ap.add_argument("--learner", default="AdamW", choices=["AdamW", "Adam", "SGD", "Adagrad", "RMSprop"],
                     help="the optimiser (--learner of lcrec_amd.main)")
     ap.add_argument("--dropout", type=float, default=0.0, help="dropout probability (--dropout_prob of lcrec_amd.main)")
+    ap.add_argument("--save_state", action="store_true",
+                    help="with --trainer: also time one checkpoint write and one train_state.pth write (--save_state of lcrec_amd.main)")
     ap.add_argument("--trainer", action="store_true",
                     help="time lcrec_amd.trainer.Trainer._train_epoch itself (loader, NaN check, fused AdamW, schedule)")
     a = ap.parse_args()

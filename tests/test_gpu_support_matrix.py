@@ -21,7 +21,18 @@ reach what the two architectures of tests/test_gpu_train.py never do:
 
 test_step_check_host.py checks on the CPU that in every case the fp32 and fp64 evaluations choose the same codes on every
 row (default seeds, dropout masks of step counters 0 and 1 included), so the cap on differently assigned rows is the device
-path's alone."""
+path's alone.
+
+The codes the device assigned are judged on every row and level, not only counted (step_check.CodeRule).  With C64 and C32 a
+level's cost matrix -- torch_ref.distances on an argmin level, -ln Q of torch_ref.sinkhorn on a Sinkhorn level -- of the CPU
+evaluation in fp64 and in fp32, both with the device's codes forced, b_i the fp64 minimum of row i and D = |C32 - C64|, the
+code k of row i has to satisfy
+
+    C64[i, k] - C64[i, b_i]  <=  f11_check.SLACK * (D[i, k] + D[i, b_i]) + floor(i, k)
+
+floor = 2^-22 * (||R64_i||^2 + ||c_k||^2) on an argmin level, 1e-9 on a Sinkhorn level.  The one row a case may assign
+differently from the fp32 evaluation is therefore a near-tie of the fp64 evaluation; a wrong code on the last row of a ragged
+tile, on row 0 or on the first row of a workgroup's share is refused (test_step_check_host.py does exactly that to case F)."""
 import numpy as np
 import pytest
 import torch

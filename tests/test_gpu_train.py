@@ -518,26 +518,20 @@ def test_run_sh_step_gradients_against_the_fp64_reference(hip, path):
     from lcrec_amd.engine import TrainEngine
     g = np.load(os.path.join(GOLD, "f11_run_sh_step.npz"))
     model, x = _run_sh_model(hip, g)
-    want = g["f64__scalars"]
     names = [k for k, _ in model.named_parameters()]
     assert sorted(names) == sorted(f11_check.tensors(g))
 
     def judge(grads, scalars, idx, what):
-        flipped = int((idx != g["idx"].astype(np.int64)).any(1).sum())
         # An evaluation whose latents differ in the last bit (BatchNorm statistics summed in another order; the folded form's
         # single fma) may send a near-tied row or two of the 1024 to another code on the Sinkhorn level: a different, equally
         # valid problem for those rows, not different arithmetic.  Then the yardstick is the fp64 evaluation of THAT problem
         # (f11_check.f64_gradients_for: the oracle's torch restatement in fp64 with the codes forced; with the fixture's codes
         # it reproduces the reference's fp64 run to 1e-9, tests/test_oracle_golden.py) -- same bounds, nothing loosened.
-        assert flipped <= 3, (what, flipped)
-        target, f64 = want, None
-        if flipped:
-            target, f64 = f11_check.f64_gradients_for(g, idx)
-        np.testing.assert_allclose(scalars[:3], target[:3], rtol=1e-5, err_msg=what)      # loss, recon, rq_loss
-        np.testing.assert_allclose(scalars[3], target[3], rtol=1e-4, err_msg=what)        # gradient norm before clipping
-        rows, bad = f11_check.report(g, grads, f64)
-        print(f"\n[{what}] rows assigned differently: {flipped}\n" + f11_check.table(rows))
-        assert not bad, what + "\n" + f11_check.table(bad)
+        # f11_check.judge caps such rows at 3 AND asks of every assigned code, on every row and level, that its fp64 regret
+        # C64[i, k] - C64[i, b_i] stays within SLACK x what fp32 does to those two costs on the CPU plus a floor of four fp32
+        # ulps (argmin levels) / 1e-9 in -ln Q (Sinkhorn level): a row that differs is a near-tie in fp64, not a wrong
+        # assignment (step_check.CodeRule; shown to bite on the host by tests/test_oracle_golden.py).
+        f11_check.judge(g, grads, scalars, idx, what)
 
     if path == "autograd":
         out, rq_loss, idx = model(x)

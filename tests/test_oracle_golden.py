@@ -204,3 +204,52 @@ def test_torch_ref_training_step_at_the_run_sh_width_against_fp64_reference():
     # what the fixture says about fp32 itself: the first encoder layers lose 3-4 digits, the rest sits at ~1e-6
     m = manifest()["fixtures"]["f11_run_sh_step.npz"]["reference_f32_vs_f64_gradient_rel_err"]
     assert m["encoder.mlp_layers.1.weight"] > 1e-4 and m["decoder.mlp_layers.25.weight"] < 1e-5
+
+
+def _f11_moved(g, row, level, code, monkeypatch=None):
+    """f11_check.judge on the fp32 evaluation of the run.sh step with `row` sent to `code` on `level`: gradients and scalars
+    are that problem's own and one row is within the cap of 3, so only the rule on the codes can refuse it."""
+    import f11_check
+    import step_check
+    moved = g["idx"].astype(np.int64)
+    moved[row, level] = code
+    _, _, s32, g32, _ = f11_check.yardsticks(g, moved)
+    if monkeypatch is not None:
+        monkeypatch.setattr(step_check.CodeRule, "check", lambda self, idx, what: [])
+    f11_check.judge(g, g32, s32, moved, f"F11, row {row} level {level} sent to code {code}")
+
+
+def test_the_rule_on_the_codes_at_the_run_sh_width(monkeypatch):
+    """F11's judge asks of every assigned code that it be acceptable by its fp64 regret (tests/step_check.py CodeRule).  For
+    the reference alone: every cost of the fp64 and the fp32 evaluation is finite, the fixture's codes are acceptable and
+    are the fp64 minimum on all 1024 rows of all 4 levels, and per level at most max(3, 1024 // 100) rows have more than one
+    acceptable code.  And the rule bites: a row with one acceptable code sent to its fp64 runner-up is refused, on an argmin
+    level and on the Sinkhorn level, by the rule alone (without it the same step passes); a row with two acceptable codes
+    sent to the other one on the Sinkhorn level passes."""
+    import f11_check
+    g = gold("f11_run_sh_step.npz")
+    idx = g["idx"].astype(np.int64)
+    _, _, s32, g32, rule = f11_check.yardsticks(g, idx)
+    f11_check.judge(g, g32, s32, idx, "F11, fp32 evaluation with the fixture's codes forced")
+    order = {}
+    for l, v in enumerate(rule.levels):
+        several = rule.undecidable(l)
+        rows = np.arange(1024)
+        order[l] = np.argsort(v["regret"], 1, kind="stable")
+        ratio = np.median(v["threshold"][rows, order[l][:, 1]] / v["margin"])
+        print(f"F11 level {l}: rows with more than one acceptable code {several.tolist()}, acceptable codes on them "
+              f"{v['ok'][several].sum(1).tolist()}; median threshold of the runner-up / top-2 margin {ratio:.3g}")
+        assert v["finite"], l
+        assert np.array_equal(idx[:, l], v["best"]), l
+        assert len(several) <= max(3, 1024 // 100), (l, several)
+    for level in (0, 3):                                         # an argmin level and the Sinkhorn level
+        row = int(np.flatnonzero(rule.levels[level]["ok"].sum(1) == 1)[0])
+        code = int(order[level][row, 1])
+        with pytest.raises(AssertionError, match=rf"row {row} level {level}:"):
+            _f11_moved(g, row, level, code)
+        with monkeypatch.context() as m:
+            _f11_moved(g, row, level, code, m)
+    row = int(rule.undecidable(3)[0])
+    code = int(order[3][row, 1])
+    assert rule.levels[3]["ok"][row, code]
+    _f11_moved(g, row, 3, code)

@@ -1,5 +1,7 @@
 """tests/step_check.py and the case recipe of tests/test_gpu_support_matrix.py on the host: what the GPU test relies on holds
-for the CPU evaluations alone, and the judge does refuse a wrong gradient."""
+for the CPU evaluations alone, and the judge does refuse a wrong gradient -- and a wrong code: one row sent to another code
+than its only acceptable one is refused by its fp64 regret (step_check.CodeRule), where the count cap, the gradients and
+the scalars all let it through; a row with two acceptable codes may take either."""
 import numpy as np
 import pytest
 import torch
@@ -28,7 +30,10 @@ def host_masks(c, step, seed=SEED):
 def test_the_reference_alone_satisfies_what_the_gpu_test_asks(letter):
     """Per case (and, with dropout, per step counter 0 and 1): the fp32 and the fp64 evaluation choose the same codes on every
     row, so the cap on differently assigned rows leaves the device path its whole allowance; the fp32 evaluation passes its
-    own judgement; and every case of 16 rows or more uses more than one code per level."""
+    own judgement; and every case of 16 rows or more uses more than one code per level.  The rule on the codes
+    (step_check.CodeRule) holds for the reference alone: every cost of both evaluations is finite, the fp32 evaluation's own
+    codes are acceptable on every row (the judge asserts it) and are the fp64 minimum, and the rule is not vacuous -- per
+    level at most max(3, rows // 100) rows have more than one acceptable code."""
     c, sd, x = gi.support_matrix_case(letter)
     spec = step_check.spec_of(c, gi.SUPPORT_MATRIX_SK_ITERS)
     judge = step_check.Judge(spec, sd, x, exact_codes=True)
@@ -43,6 +48,14 @@ def test_the_reference_alone_satisfies_what_the_gpu_test_asks(letter):
         scalars, g32 = step_check.evaluate(spec, sd, x, idx32, torch.float32, masks)
         rows = judge(g32, scalars, idx32, f"case {letter}, fp32 evaluation, step counter {step}", masks, step)
         assert max(r[3] for r in rows if r[1] == "rel") < 2e-5               # the reference's own fp32 distances stay small
+        rule = judge.yardsticks(idx32, masks, step)[4]
+        for l, v in enumerate(rule.levels):
+            several = rule.undecidable(l)
+            print(f"case {letter}, step counter {step}, level {l}: rows with more than one acceptable code {several.tolist()} of "
+                  f"{c['batch']}, acceptable codes on them {v['ok'][several].sum(1).tolist()}")
+            assert v["finite"], (letter, step, l)
+            assert np.array_equal(idx32[:, l], v["best"]), (letter, step, l)
+            assert len(several) <= max(3, c["batch"] // 100), (letter, step, l, several)
 
 
 def test_the_judge_refuses_wrong_gradients_scalars_and_codes():
@@ -68,6 +81,14 @@ def test_the_judge_refuses_wrong_gradients_scalars_and_codes():
     s2, g2 = step_check.evaluate(spec, sd, x, moved, torch.float32)
     with pytest.raises(AssertionError, match="2"):
         judge(g2, s2, moved, "two rows moved")
+    # ONE row with a single acceptable code sent to its fp64 runner-up: within the cap, gradients and scalars those of its own
+    # problem -- refused by its fp64 regret alone
+    row, code = _to_the_runner_up(judge.yardsticks(idx)[4], 1)
+    moved = idx.copy()
+    moved[row, 1] = code
+    s1, g1 = step_check.evaluate(spec, sd, x, moved, torch.float32)
+    with pytest.raises(AssertionError, match=rf"row {row} level 1:"):
+        judge(g1, s1, moved, "one decidable row moved")
 
 
 def _bump(a):
@@ -75,6 +96,75 @@ def _bump(a):
     i = np.unravel_index(np.abs(b).argmax(), b.shape)
     b[i] *= 2.0
     return b
+
+
+def _to_the_runner_up(rule, level):
+    """(the first row of `level` with exactly one acceptable code, its fp64 runner-up)."""
+    v = rule.levels[level]
+    row = int(np.flatnonzero(v["ok"].sum(1) == 1)[0])
+    return row, int(np.argsort(v["regret"][row], kind="stable")[1])
+
+
+def _to_the_other_acceptable_code(rule, level):
+    """(the first row of `level` with more than one acceptable code, the best of its acceptable codes but the fp64 minimum)."""
+    v = rule.levels[level]
+    row = int(rule.undecidable(level)[0])
+    order = np.argsort(v["regret"][row], kind="stable")
+    assert order[0] == v["best"][row] and v["ok"][row, order[1]]
+    return row, int(order[1])
+
+
+@pytest.fixture(scope="module")
+def case_f():
+    """Case F (131 rows: three 64-row tiles, the last one ragged; an argmin level, then a Sinkhorn level), its judge with the
+    device paths' allowance of one row, the fp32 evaluation's own codes and the rule on them."""
+    c, sd, x = gi.support_matrix_case("F")
+    spec = step_check.spec_of(c, gi.SUPPORT_MATRIX_SK_ITERS)
+    judge = step_check.Judge(spec, sd, x, exact_codes=False)
+    idx = step_check.free_codes(spec, sd, x)
+    return c, spec, sd, x, judge, idx, judge.yardsticks(idx)[4]
+
+
+def _judge_moved(case, row, level, code, monkeypatch=None):
+    """The fp32 evaluation of the problem with `row` sent to `code` on `level`, judged: its gradients and scalars are that
+    problem's own and one row is within the cap, so only the rule on the codes can refuse it."""
+    c, spec, sd, x, judge, idx, _ = case
+    moved = idx.copy()
+    moved[row, level] = code
+    scalars, grads = step_check.evaluate(spec, sd, x, moved, torch.float32)
+    if monkeypatch is not None:
+        monkeypatch.setattr(step_check.CodeRule, "check", lambda self, idx, what: [])
+    judge(grads, scalars, moved, f"case F, row {row} level {level} sent to code {code}")
+
+
+@pytest.mark.parametrize("level", [0, 1])
+def test_a_decidable_row_sent_to_its_runner_up_is_refused(case_f, level, monkeypatch):
+    """Once on the argmin level and once on the Sinkhorn level of case F: the nearest wrong code there is.  Without the rule
+    the same step passes -- gradients, scalars and the count cap do not see it."""
+    row, code = _to_the_runner_up(case_f[6], level)
+    with pytest.raises(AssertionError, match=rf"row {row} level {level}:"):
+        _judge_moved(case_f, row, level, code)
+    _judge_moved(case_f, row, level, code, monkeypatch)
+
+
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("row", [0, 128, 130])
+def test_a_wrong_code_on_an_edge_row_is_refused(case_f, row, level):
+    """Row 0, the first row of the ragged last 64-row tile and the last row, each sent to the next code: the rows an
+    assignment kernel gets wrong at its edges, one at a time, which the count cap lets through."""
+    c, idx = case_f[0], case_f[5]
+    assert c["batch"] == 131 and row < c["batch"]
+    with pytest.raises(AssertionError, match=rf"row {row} level {level}:"):
+        _judge_moved(case_f, row, level, (idx[row, level] + 1) % c["codes"][level])
+
+
+def test_an_undecidable_row_sent_to_its_other_acceptable_code_passes(case_f):
+    """The allowance is still there for what it was made for: a near-tie of the fp64 evaluation (case F, last level)."""
+    rule = case_f[6]
+    row, code = _to_the_other_acceptable_code(rule, 1)
+    print(f"case F level 1: row {row} to code {code}, regret {rule.levels[1]['regret'][row, code]:.3e}, threshold "
+          f"{rule.levels[1]['threshold'][row, code]:.3e}")
+    _judge_moved(case_f, row, 1, code)
 
 
 def test_masks_in_the_oracle():

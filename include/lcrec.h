@@ -450,7 +450,21 @@ int lcrec_quantizer_input_grad_bias(const float *z, const float *codebook0, cons
  * ticket: NULL, or see "ticket arguments": the increment is then made by the last workgroup of the update launch.
  * skip_flag: NULL, or a device byte; non-zero = update nothing and leave *step (see lcrec_ema_update).
  * base_lr and weight_decay must be >= 0, as for the other learners below (all four share one launcher; torch refuses
- * such an optimiser at construction). */
+ * such an optimiser at construction).
+ *
+ * The arithmetic, per element (p param, m exp_avg, v exp_avg_sq): every op one fp32 rounding and, but for the lerp, none
+ * fused; IEEE sqrt and division.  Each constant is computed in double from the double hyper-parameters and rounded to
+ * float once; t = *step + 1, lr = lr(*step):
+ *   g = grads * clip[1]                        stored back to grads when clip is given and clip[1] != 1
+ *   weight_decay != 0, decoupled (AdamW):      p = p - (float)(lr * weight_decay) * p
+ *   weight_decay != 0, not decoupled (Adam):   g = g + p * (float)weight_decay      (grads keeps the clipped value alone)
+ *   m = m.lerp(g, w), w = (float)(1 - beta1)   torch's lerp: |w| < 0.5: fma(w, g - m, m), else fma(w - 1, g - m, g), w - 1 in float
+ *   v = (float)beta2 * v + ((float)(1 - beta2) * g) * g
+ *   denom = sqrt(v) / (float)sqrt(bc2) + (float)eps,        bc2 = 1 - pow(beta2, t)
+ *   p = p - ((float)(lr / bc1) * m) / denom,                bc1 = 1 - pow(beta1, t)
+ * exp_avg then has the bits of torch's single-tensor Adam (but under L2, which torch adds fused); torch decays AdamW's
+ * parameters by p.mul_(1 - lr * weight_decay), so those differ from it in the last bit on about a third of the elements
+ * (the learners). */
 int lcrec_adamw_step(float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t count, const float *clip,
                      int64_t *step, double base_lr, double beta1, double beta2, double eps, double weight_decay,
                      int decoupled, int schedule, int64_t warmup_steps, int64_t total_steps, float *lr_out,
@@ -463,6 +477,19 @@ int lcrec_adamw_step(float *params, float *grads, float *exp_avg, float *exp_avg
  * g = grads * clip[1], then g += weight_decay * param when weight_decay != 0; the rules are torch 2.10's
  * _single_tensor_{sgd,adagrad,rmsprop}, with each op rounded as torch's CPU kernel rounds it (add with alpha and addcmul
  * fused, addcdiv as x + (value * y) / z, IEEE sqrt and division).  State is fp32, hyper-parameters are double.
+ * The ops, a and w being double constants rounded to float once (so -lr is (float)(-lr), 1 - alpha is (float)(1 - alpha)):
+ *   x.add(y, alpha=a)         fma(a, y, x)               x.mul(a), x + y, sqrt(x), x / y   one rounding each
+ *   x.addcmul(y, z, value=a)  fma(a * y, z, x)           x.addcdiv(y, z, value=a)          x + (a * y) / z
+ *   x.lerp(y, w)              |w| < 0.5: fma(w, y - x, x), else fma(w - 1, y - x, y), w - 1 in float
+ * and the rules in them (g after the clipping and the weight decay g = g.add(param, alpha=weight_decay); grads keeps
+ * the clipped value alone):
+ *   SGD       buf = first ? g : buf.mul(momentum).add(g, alpha=1 - dampening);  g = nesterov ? g.add(buf, alpha=momentum) : buf;
+ *             param = param.add(g, alpha=-lr)
+ *   Adagrad   sum = sum.addcmul(g, g, value=1);  std = sqrt(sum) + eps;  param = param.addcdiv(g, std, value=-clr)
+ *   RMSprop   sq = sq.mul(alpha).addcmul(g, g, value=1 - alpha);  centered: ga = ga.lerp(g, 1 - alpha),
+ *             avg = sqrt(sq.addcmul(ga, ga, value=-1)) + eps, else avg = sqrt(sq) + eps;
+ *             momentum > 0: buf = buf.mul(momentum).addcdiv(g, avg, value=1), param = param.add(buf, alpha=-lr),
+ *             else param = param.addcdiv(g, avg, value=-lr)
  *
  * torch.optim.SGD: with momentum != 0, momentum_buffer[count] and momentum_ready (device byte) are required, otherwise
  * both are NULL.  momentum_ready == 0: buf = g (torch's first step) and the byte is set to 1 with the step increment;
@@ -881,6 +908,23 @@ typedef struct {
                                * loads; else 0 */
 } lcrec_step_tail_plan;
 int lcrec_debug_step_tail_plan(int call, int64_t n_or_count, int width, int aligned, lcrec_step_tail_plan *out);
+
+/* The launch of the four optimiser entry points (lcrec_adamw_step .. lcrec_rmsprop_step: one kernel, one launcher) for
+ * `count` elements; the launcher takes its grid from the same function.  Host only: nothing is launched.
+ *   aligned     whether params, grads and every state buffer the rule uses sit on 16 bytes (one that does not sends
+ *               every element through the scalar loop)
+ *   has_ticket  whether the call is given a ticket
+ * A lane is one of the workgroups x 1024 threads; both loops stride by that many, so lane t makes
+ * ceil((items - t) / lanes) trips over a loop's items (0 when t >= items): the first lane the most, the last the fewest. */
+typedef struct {
+    int workgroups;           /* gridDim.x: ceil(count / 8192), at most 256 */
+    int second_launch;        /* no ticket: a one-thread launch advances *step (and momentum_ready) */
+    int64_t quads;            /* float4 items of the 16-byte loop: count / 4 when aligned, else 0 */
+    int64_t scalars;          /* elements of the scalar loop: count % 4 when aligned, else count */
+    int64_t quad_trips_max, quad_trips_min;       /* trips of the 16-byte loop: the first lane's, the last lane's */
+    int64_t scalar_trips_max, scalar_trips_min;   /* the same for the scalar loop */
+} lcrec_optim_plan;
+int lcrec_debug_optim_plan(int64_t count, int aligned, int has_ticket, lcrec_optim_plan *out);
 
 /* The launches of lcrec_linear_forward, lcrec_linear_backward, lcrec_linear_backward_weights and lcrec_linear_bn_forward
  * (csrc/gemm_f32.hip): each entry point decides its launches with one pure host function; the launch code launches by it and the

@@ -130,6 +130,7 @@ SinkhornGroupRoute = STRUCTS["lcrec_sinkhorn_group_route"]
 RqPlan = STRUCTS["lcrec_rq_plan"]
 BnPlan = STRUCTS["lcrec_bn_plan"]
 StepTailPlan = STRUCTS["lcrec_step_tail_plan"]
+OptimPlan = STRUCTS["lcrec_optim_plan"]
 GemmLaunch = STRUCTS["lcrec_gemm_launch"]
 TraceEntry = STRUCTS["lcrec_trace_entry"]
 

@@ -536,6 +536,11 @@ LCREC_API int lcrec_debug_step_tail_plan(int call, int64_t n_or_count, int width
     return debug_step_tail_plan(call, n_or_count, width, aligned, out);
 }
 
+LCREC_API int lcrec_debug_optim_plan(int64_t count, int aligned, int has_ticket, lcrec_optim_plan *out)
+{
+    return debug_optim_plan(count, aligned, has_ticket, out);
+}
+
 LCREC_API int lcrec_bn_relu_apply(const float *t, int64_t n, int features, const float *gamma, const float *beta, const float *mean,
                                   const float *rstd, int relu, float *y, void *stream)
 {

@@ -289,6 +289,7 @@ int adagrad_step(float *p, float *g, float *state_sum, int64_t count, const floa
 int rmsprop_step(float *p, float *g, float *square_avg, float *buf, float *grad_avg, int64_t count, const float *clip, int64_t *step,
                  double base_lr, double alpha, double eps, double weight_decay, double momentum, int centered, int schedule,
                  int64_t warmup_steps, int64_t total_steps, float *lr_out, unsigned *ticket, const unsigned char *skip, hipStream_t stream);
+int debug_optim_plan(int64_t count, int aligned, int has_ticket, lcrec_optim_plan *out);
 int dropout_apply(const float *in, float *out, int64_t n, int F, uint32_t T, float s, const int64_t *seed, const int64_t *step,
                   int position, int64_t row_offset, hipStream_t stream);
 int dropout_mask(unsigned char *keep_out, int64_t n, int F, uint32_t T, const int64_t *seed, const int64_t *step, int position,

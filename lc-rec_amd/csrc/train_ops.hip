@@ -805,9 +805,9 @@ __device__ __forceinline__ double lr_at(const OptimParams &a, int64_t s)
 // applied to the gradient on the way in (and stored back when it changed it, as clip_grad_norm_ leaves it), the learning
 // rate from the device step counter, lr_out, the step advance (ticket) and the NaN skip.  State in fp32,
 // hyper-parameters in double folded to float once.
-// Adam is the fused torch kernel's arithmetic, written out op by op (the file is built with -ffp-contract=off).  For the
-// other three, element by element the arithmetic is that of torch's CPU kernels for each op of
-// _single_tensor_{sgd,adagrad,rmsprop}:
+// Adam's arithmetic is written out op by op in include/lcrec.h (the file is built with -ffp-contract=off): exp_avg by torch's
+// lerp (below), the rest one rounding per op, none fused.  For the other three, element by element the arithmetic is that of
+// torch's CPU kernels for each op of _single_tensor_{sgd,adagrad,rmsprop}:
 //   x.add(y, alpha=a)          fma(a, y, x)
 //   x.addcmul(y, z, value=a)   fma(a * y, z, x)
 //   x.addcdiv(y, z, value=a)   x + (a * y) / z
@@ -837,6 +837,8 @@ __global__ __launch_bounds__(OPTIM_THREADS) void optim_step_kernel(OptimParams a
         b2 = (float)a.beta2; one_m_b1 = (float)(1.0 - a.beta1); one_m_b2 = (float)(1.0 - a.beta2);
         bc2s = (float)bc2_sqrt;
         lr_wd = (float)(lr * a.weight_decay);
+        lerp_small = __builtin_fabsf(one_m_b1) < 0.5f;
+        lerp_w = lerp_small ? one_m_b1 : one_m_b1 - 1.0f;
     } else {
         // SGD: buf.mul_(momentum).add_(grad, alpha=1 - dampening).  Adagrad: clr = lr / (1 + (step - 1) * lr_decay), step the
         // post-increment count.  RMSprop: square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha), grad_avg.lerp_(grad, 1 - alpha).
@@ -863,7 +865,7 @@ __global__ __launch_bounds__(OPTIM_THREADS) void optim_step_kernel(OptimParams a
                     if (a.decoupled) p -= lr_wd * p;
                     else g += p * wd;
                 }
-                b = b + one_m_b1 * (g - b);                  // lerp(exp_avg, g, 1 - beta1)
+                b = __builtin_fmaf(lerp_w, g - b, lerp_small ? b : g);   // exp_avg.lerp_(g, 1 - beta1)
                 q = b2 * q + one_m_b2 * g * g;
                 const float denom = __builtin_sqrtf(q) / bc2s + epsf;
                 p -= step_size * b / denom;
@@ -1534,6 +1536,33 @@ static OptimParams optim_params(float *p, float *g, int64_t count, const float *
     return a;
 }
 
+// The launch of optim_step_kernel (include/lcrec.h, lcrec_optim_plan): launch_optim_step launches by it and
+// lcrec_debug_optim_plan() reports it.  The kernel's two loops stride by the whole grid's lanes.
+static lcrec_optim_plan optim_plan(int64_t count, bool aligned, bool has_ticket)
+{
+    lcrec_optim_plan p = {};
+    int64_t blocks = (count + OPTIM_THREADS * 8 - 1) / (OPTIM_THREADS * 8);
+    if (blocks > TICKET_MAX_WORKGROUPS) blocks = TICKET_MAX_WORKGROUPS;
+    p.workgroups = (int)blocks;
+    p.second_launch = !has_ticket;
+    p.quads = aligned ? count / 4 : 0;
+    p.scalars = count - 4 * p.quads;
+    const int64_t lanes = blocks * OPTIM_THREADS;
+    p.quad_trips_max = (p.quads + lanes - 1) / lanes;
+    p.quad_trips_min = p.quads / lanes;
+    p.scalar_trips_max = (p.scalars + lanes - 1) / lanes;
+    p.scalar_trips_min = p.scalars / lanes;
+    return p;
+}
+
+int debug_optim_plan(int64_t count, int aligned, int has_ticket, lcrec_optim_plan *out)
+{
+    if (!out) return fail(LCREC_EINVAL, "debug_optim_plan: NULL pointer");
+    if (count < 1) return fail(LCREC_EINVAL, "debug_optim_plan: count=%lld", (long long)count);
+    *out = optim_plan(count, aligned != 0, has_ticket != 0);
+    return LCREC_OK;
+}
+
 // `what`: the entry point, for error texts; `label`: its trace label (K_ADAMW | K_OPTIM_STEP)
 template <int RULE>
 static int launch_optim_step(const OptimParams &a, const char *what, int label, hipStream_t stream)
@@ -1542,11 +1571,10 @@ static int launch_optim_step(const OptimParams &a, const char *what, int label, 
     if (a.count < 1) return fail(LCREC_EINVAL, "%s: empty parameter buffer", what);
     if (a.schedule < -1 || a.schedule > 1) return fail(LCREC_EINVAL, "%s: schedule %d (supported: -1 none, 0 constant, 1 linear)", what, a.schedule);
     if (!(a.base_lr >= 0.0) || !(a.weight_decay >= 0.0)) return fail(LCREC_EINVAL, "%s: lr and weight_decay must be >= 0", what);
-    int64_t blocks = (a.count + OPTIM_THREADS * 8 - 1) / (OPTIM_THREADS * 8);
-    if (blocks > TICKET_MAX_WORKGROUPS) blocks = TICKET_MAX_WORKGROUPS;
+    const lcrec_optim_plan plan = optim_plan(a.count, aligned16({a.p, a.g, a.buf, a.sq, a.gavg}), a.ticket != nullptr);
     TraceScope trace(label, stream);
-    hipLaunchKernelGGL(optim_step_kernel<RULE>, dim3((unsigned)blocks), dim3(OPTIM_THREADS), 0, stream, a);
-    if (!a.ticket) hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(1), 0, stream, a.step, a.buf_ready, a.skip);
+    hipLaunchKernelGGL(optim_step_kernel<RULE>, dim3((unsigned)plan.workgroups), dim3(OPTIM_THREADS), 0, stream, a);
+    if (plan.second_launch) hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(1), 0, stream, a.step, a.buf_ready, a.skip);
     return check_launch(what);
 }
 

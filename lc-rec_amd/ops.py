@@ -1165,6 +1165,15 @@ def step_tail_plan(call, n_or_count, width=0, aligned=True, K=0):
     return out
 
 
+def optim_plan(count, aligned=True, has_ticket=True):
+    """The launch of the optimiser step kernel for `count` elements (include/lcrec.h, lcrec_debug_optim_plan), as a dict of the
+    fields of lcrec_optim_plan.  Host only: no GPU is needed."""
+    plan = _lib.OptimPlan()
+    rc = _lib.load().lcrec_debug_optim_plan(int(count), int(bool(aligned)), int(bool(has_ticket)), ctypes.addressof(plan))
+    _lib.check(rc, "lcrec_debug_optim_plan")
+    return {name: int(getattr(plan, name)) for name, _ in _lib.OptimPlan._fields_}
+
+
 def bn_merge_stats(rows, eps, momentum=0.0, running_mean=None, running_var=None):
     """(mean, rstd) of the union of the ranks' rows from rows [world, 2F+1] = (n_r, mean_r, m2_r); updates the running
     statistics in place when given (lcrec_bn_merge_stats)."""

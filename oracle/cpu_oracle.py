@@ -218,6 +218,35 @@ def ema_update(ema_count, ema_sum, codebook, count, s, decay, eps):
     return ema_count, ema_sum, codebook
 
 
+OPTIM_RULES = ("sgd", "adagrad", "rmsprop", "adam")
+OPTIM_HYPER = ("weight_decay", "momentum", "dampening", "lr_decay", "alpha", "eps", "beta1", "beta2")
+
+
+def optim_step(rule, params, grads, s, lr, buf=None, sq=None, gavg=None, clip=None, schedule=-1, warmup_steps=0, total_steps=0,
+               momentum_ready=None, skip=False, nesterov=False, centered=False, decoupled=False, **hyper):
+    """One step of lcrec_{sgd,adagrad,rmsprop,adamw}_step (include/lcrec.h) in place on contiguous float32 arrays.
+    rule: one of OPTIM_RULES; buf: the momentum buffer / exp_avg, sq: state_sum / square_avg / exp_avg_sq, gavg: grad_avg
+    (None where the rule has none); clip: None or the coefficient clip[1]; s: the steps taken before this one; hyper: any of
+    OPTIM_HYPER as Python floats (default 0); momentum_ready: a uint8 array of one element, read and set (SGD with momentum).
+    Returns the learning rate used as a float32, or None when skipped."""
+    fn = lib().lcrec_oracle_optim_step
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_int64,
+                   ctypes.c_double, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                   ctypes.POINTER(ctypes.c_ubyte), ctypes.c_int, _f32p]
+    arrays = [a for a in (params, grads, buf, sq, gavg) if a is not None]
+    assert all(a.dtype == np.float32 and a.flags.c_contiguous and a.size == params.size for a in arrays)
+    assert set(hyper) <= set(OPTIM_HYPER), hyper
+    h = np.array([float(hyper.get(k, 0.0)) for k in OPTIM_HYPER], dtype=np.float64)
+    lr_out = np.zeros(1, dtype=np.float32)
+    rc = fn(OPTIM_RULES.index(rule), _p(params), _p(grads), _p(buf), _p(sq), _p(gavg), params.size, int(clip is not None),
+            np.float32(0.0 if clip is None else clip), int(s), float(lr), _p(h, _f64p), int(bool(nesterov)) | int(bool(centered)) << 1
+            | int(bool(decoupled)) << 2, int(schedule), int(warmup_steps), int(total_steps),
+            _p(momentum_ready, ctypes.POINTER(ctypes.c_ubyte)), int(bool(skip)), _p(lr_out))
+    assert rc == 0, rc
+    return None if skip else lr_out[0]
+
+
 def distances(z, codebook):
     """vq.py:71-73 as a [n, K] fp32 matrix in the canonical fma-chain order."""
     z, cb = _f32(z), _f32(codebook)

@@ -244,7 +244,9 @@ int lcrec_rq_assign(const float *z, int64_t n, int e, const float *codebooks, co
  * the context's first helper stream, forked from `stream` by an event at entry and joined back into it before
  * the quantiser pass (and on every error exit), so everything is ordered after prior work on `stream` and
  * before later work on it, without any host synchronisation; with ctx == NULL or pipelines == 1 every launch
- * is on `stream`. */
+ * is on `stream`.  The walk and the layout of the workspace are one host function's decision, which
+ * lcrec_debug_encode_assign_plan (below, debug entries) reports.
+ * lcrec_encode_assign_workspace returns 0 for arguments lcrec_encode_assign refuses. */
 size_t lcrec_encode_assign_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L);
 /* rows per chunk of the walk described above (a build constant; results do not depend on it) */
 int64_t lcrec_encode_assign_chunk_rows(void);
@@ -855,6 +857,52 @@ int lcrec_debug_rq_assign(const float *z, int64_t n, int e, const float *codeboo
                           float *resid_out, float *margin_out, uint32_t *neartie_out, float tie_tau,
                           void *workspace, size_t workspace_bytes, unsigned int *ticket, void *stream,
                           int force_split, int force_threads, int force_grid);
+
+/* lcrec_encode_assign walks its n rows in chunks; one pure host function decides the walk and the layout of the workspace, and
+ * the workspace query, the launch code and the export below all go through it:
+ *   - chunk c covers rows c * chunk_rows .. and every chunk but the last has chunk_rows rows;
+ *   - it runs on pipeline c % pipelines (0: the caller's stream, 1: the context's first helper stream), the pipelines in use
+ *     being min(asked for, chunks, LCREC_ENC_PIPES_MAX), at least 1;
+ *   - layer l of the chunk writes activation buffer first_act + (l & 1) -- every pipeline ping-pongs between two buffers of its
+ *     own, each act_bytes = chunk_rows x widest hidden width floats rounded up to 256 B -- and the last layer writes rows
+ *     row0 .. row0 + rows of the latent matrix, which is latent_out or, when that is NULL, the slab at latent_offset;
+ *   - one lcrec_rq_assign over all n rows follows, with the rq_bytes at rq_offset as its workspace.
+ * The workspace always has room for LCREC_ENC_PIPES_MAX pipelines and for the latent slab, used or not, so its size depends on
+ * the shapes and the chunk size alone.  chunk_rows: 0 = the built-in lcrec_encode_assign_chunk_rows(); any positive value is
+ * admitted (results do not depend on it); a batch shorter than a chunk is one chunk of n rows. */
+#define LCREC_ENC_PIPES_MAX 2
+#define LCREC_ENC_ACT_BUFFERS 4           /* 2 * LCREC_ENC_PIPES_MAX */
+typedef struct {
+    int64_t n;                /* rows of the call */
+    int64_t chunk_rows;       /* the chunk size in effect: min(asked for, max(n, 1)) */
+    int64_t n_chunks;         /* ceil(n / chunk_rows) */
+    int pipelines;            /* pipelines in use */
+    int64_t act_bytes;        /* one activation buffer */
+    int64_t act_offset[LCREC_ENC_ACT_BUFFERS];   /* byte offsets into the workspace: pipeline p owns buffers 2p and 2p + 1 */
+    int64_t latent_offset, latent_bytes;         /* the slab for [n][e] latents (used when latent_out is NULL) */
+    int64_t rq_offset, rq_bytes;                 /* lcrec_rq_assign's workspace for n rows */
+    int64_t total_bytes;      /* = lcrec_encode_assign_workspace */
+} lcrec_encode_plan;
+typedef struct {
+    int64_t row0, rows;
+    int pipeline;
+    int first_act;            /* index into act_offset of the buffer the chunk's first layer writes (when it is not the last) */
+} lcrec_encode_chunk;
+/* Host only: nothing is launched, no device is needed.  pipelines: 1 .. LCREC_ENC_PIPES_MAX, what the context would be set to.
+ * plan_out is required; chunks_out is NULL (capacity is then not read), or room for `capacity` >= n_chunks records.  Returns
+ * LCREC_OK or the code lcrec_encode_assign refuses the arguments with (LCREC_EINVAL too for a capacity that is too small). */
+int lcrec_debug_encode_assign_plan(int64_t n, const int *dims, int n_layers, const int *K, int L, int64_t chunk_rows, int pipelines,
+                                   lcrec_encode_plan *plan_out, lcrec_encode_chunk *chunks_out, int64_t capacity);
+/* lcrec_encode_assign_workspace for a chunk size (0 for refused arguments, chunk_rows < 0 among them). */
+size_t lcrec_debug_encode_assign_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int64_t chunk_rows);
+/* lcrec_encode_assign with the chunk size as an argument: the same launch code, plan and kernels. */
+int lcrec_debug_encode_assign(const float *x, int64_t n, const int *dims, int n_layers,
+                              const float *const *W, const float *const *b,
+                              const float *const *bn_scale, const float *const *bn_shift,
+                              const float *codebooks, const int *K, int L, int64_t *idx_out,
+                              float *latent_out, float *xq_out, double *sse_out,
+                              float *margin_out, uint32_t *neartie_out, float tie_tau,
+                              void *workspace, size_t workspace_bytes, lcrec_context *ctx, void *stream, int64_t chunk_rows);
 
 /* The BatchNorm strip calls pick a kernel form by shape and alignment; lcrec_debug_bn_plan reports it.  Host only: nothing is
  * launched.  call: LCREC_BN_*; aligned: whether every pointer the call would be given sits on 16 bytes; 1 <= n <= 2^20. */

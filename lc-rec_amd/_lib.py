@@ -128,6 +128,8 @@ SinkhornClassPlan = STRUCTS["lcrec_sinkhorn_class_plan"]
 SinkhornGroupsPlan = STRUCTS["lcrec_sinkhorn_groups_plan"]
 SinkhornGroupRoute = STRUCTS["lcrec_sinkhorn_group_route"]
 RqPlan = STRUCTS["lcrec_rq_plan"]
+EncodePlan = STRUCTS["lcrec_encode_plan"]
+EncodeChunk = STRUCTS["lcrec_encode_chunk"]
 BnPlan = STRUCTS["lcrec_bn_plan"]
 StepTailPlan = STRUCTS["lcrec_step_tail_plan"]
 OptimPlan = STRUCTS["lcrec_optim_plan"]

@@ -63,25 +63,50 @@ void trace_end(hipStream_t stream)
 #define LCREC_ENC_CHUNK 524288
 #endif
 constexpr int64_t ENC_CHUNK = LCREC_ENC_CHUNK;
-constexpr int ENC_PIPES_MAX = 2;      // measured: a third and fourth pipeline add nothing (and cost 2 GB of scratch each)
+constexpr int ENC_PIPES_MAX = LCREC_ENC_PIPES_MAX;   // measured: a third and fourth pipeline add nothing (and cost 2 GB of scratch each)
+static_assert(LCREC_ENC_ACT_BUFFERS == 2 * ENC_PIPES_MAX, "an activation ping-pong pair per chunk pipeline");
 
-struct EncLayout {
-    int64_t chunk;
-    size_t act_bytes;     // one activation buffer
-    size_t latent_bytes;  // [n][e]
-    size_t rq_bytes;
-};
-
-static EncLayout enc_layout(int64_t n, const int *dims, int n_layers, const int *K, int L)
+// ---- the encode pass as a pure function of (n, dims, K, L, chunk_rows, pipelines): how the rows are cut into chunks, which
+// pipeline and activation pair a chunk takes, and where everything lies in the workspace (include/lcrec.h, lcrec_encode_plan).
+// lcrec_encode_assign / lcrec_debug_encode_assign launch by enc_plan() and enc_chunk(), the workspace queries return its total and
+// lcrec_debug_encode_assign_plan reports it; none restates the other.  chunk_rows: 0 = ENC_CHUNK.
+static int enc_plan(int64_t n, const int *dims, int n_layers, const int *K, int L, int64_t chunk_rows, int pipelines,
+                    lcrec_encode_plan *o)
 {
-    EncLayout o;
-    o.chunk = n < ENC_CHUNK ? (n > 0 ? n : 1) : ENC_CHUNK;
+    if (!dims || !K) return fail(LCREC_EINVAL, "encode_assign: NULL pointer (dims or K)");
+    if (n_layers < 1 || n_layers > LCREC_MAX_LAYERS)
+        return fail(LCREC_EINVAL, "encode_assign: n_layers=%d out of range", n_layers);
+    if (n < 0) return fail(LCREC_EINVAL, "encode_assign: n < 0");
+    if (L < 1) return fail(LCREC_EINVAL, "encode_assign: L=%d < 1", L);
+    if (chunk_rows < 0) return fail(LCREC_EINVAL, "encode_assign: chunk_rows=%lld < 0", (long long)chunk_rows);
+    if (pipelines < 1 || pipelines > ENC_PIPES_MAX)
+        return fail(LCREC_EINVAL, "encode_assign: pipelines=%d (supported: 1 .. %d)", pipelines, ENC_PIPES_MAX);
+    const int64_t rows = n > 0 ? n : 1, want = chunk_rows ? chunk_rows : ENC_CHUNK;
+    o->n = n;
+    o->chunk_rows = rows < want ? rows : want;
+    o->n_chunks = (n + o->chunk_rows - 1) / o->chunk_rows;
+    o->pipelines = o->n_chunks < pipelines ? (o->n_chunks > 1 ? (int)o->n_chunks : 1) : pipelines;
     int widest = 1;
     for (int l = 1; l < n_layers; ++l) widest = dims[l] > widest ? dims[l] : widest;
-    o.act_bytes = align_up((size_t)o.chunk * widest * sizeof(float), 256);
-    o.latent_bytes = align_up((size_t)(n > 0 ? n : 1) * dims[n_layers] * sizeof(float), 256);
-    o.rq_bytes = rq_assign_workspace(n, dims[n_layers], K, L);
-    return o;
+    const int e = dims[n_layers];
+    o->act_bytes = (int64_t)align_up((size_t)o->chunk_rows * widest * sizeof(float), 256);
+    for (int i = 0; i < LCREC_ENC_ACT_BUFFERS; ++i) o->act_offset[i] = i * o->act_bytes;
+    o->latent_offset = LCREC_ENC_ACT_BUFFERS * o->act_bytes;
+    o->latent_bytes = (int64_t)align_up((size_t)rows * e * sizeof(float), 256);
+    o->rq_offset = o->latent_offset + o->latent_bytes;
+    o->rq_bytes = (int64_t)rq_assign_workspace(n, e, K, L);
+    o->total_bytes = o->rq_offset + o->rq_bytes;
+    return LCREC_OK;
+}
+
+static lcrec_encode_chunk enc_chunk(const lcrec_encode_plan &p, int64_t c)
+{
+    lcrec_encode_chunk k;
+    k.row0 = c * p.chunk_rows;
+    k.rows = p.n - k.row0 < p.chunk_rows ? p.n - k.row0 : p.chunk_rows;
+    k.pipeline = (int)(c % p.pipelines);
+    k.first_act = 2 * k.pipeline;
+    return k;
 }
 
 int check_context(const lcrec_context *ctx, const char *who)
@@ -220,14 +245,86 @@ LCREC_API int lcrec_rq_assign(const float *z, int64_t n, int e, const float *cod
                      neartie_out, tie_tau, workspace, workspace_bytes, ticket, (hipStream_t)stream);
 }
 
+static size_t encode_assign_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int64_t chunk_rows)
+{
+    lcrec_encode_plan p;
+    return enc_plan(n, dims, n_layers, K, L, chunk_rows, 1, &p) ? 0 : (size_t)p.total_bytes;
+}
+
 LCREC_API size_t lcrec_encode_assign_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L)
 {
-    if (!dims || n_layers < 1 || n_layers > LCREC_MAX_LAYERS || !K || L < 1) return 0;
-    EncLayout o = enc_layout(n, dims, n_layers, K, L);
-    return 2 * ENC_PIPES_MAX * o.act_bytes + o.latent_bytes + o.rq_bytes;      // an activation ping-pong pair per chunk pipeline
+    return encode_assign_workspace(n, dims, n_layers, K, L, 0);
+}
+
+LCREC_API size_t lcrec_debug_encode_assign_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int64_t chunk_rows)
+{
+    return encode_assign_workspace(n, dims, n_layers, K, L, chunk_rows);
 }
 
 LCREC_API int64_t lcrec_encode_assign_chunk_rows(void) { return ENC_CHUNK; }
+
+LCREC_API int lcrec_debug_encode_assign_plan(int64_t n, const int *dims, int n_layers, const int *K, int L, int64_t chunk_rows,
+                                             int pipelines, lcrec_encode_plan *plan_out, lcrec_encode_chunk *chunks_out,
+                                             int64_t capacity)
+{
+    if (!plan_out) return fail(LCREC_EINVAL, "encode_assign_plan: NULL plan_out");
+    lcrec_encode_plan p;
+    if (int rc = enc_plan(n, dims, n_layers, K, L, chunk_rows, pipelines, &p)) return rc;
+    if (chunks_out && capacity < p.n_chunks)
+        return fail(LCREC_EINVAL, "encode_assign_plan: capacity %lld < %lld chunks", (long long)capacity, (long long)p.n_chunks);
+    *plan_out = p;
+    for (int64_t c = 0; chunks_out && c < p.n_chunks; ++c) chunks_out[c] = enc_chunk(p, c);
+    return LCREC_OK;
+}
+
+// lcrec_encode_assign (chunk_rows = 0) and lcrec_debug_encode_assign
+static int encode_assign(const float *x, int64_t n, const int *dims, int n_layers, const float *const *W, const float *const *b,
+                         const float *const *bn_scale, const float *const *bn_shift, const float *codebooks, const int *K, int L,
+                         int64_t *idx_out, float *latent_out, float *xq_out, double *sse_out, float *margin_out,
+                         uint32_t *neartie_out, float tie_tau, void *workspace, size_t workspace_bytes, lcrec_context *ctx,
+                         hipStream_t s, int64_t chunk_rows)
+{
+    if (chunk_rows < 0) return fail(LCREC_EINVAL, "encode_assign: chunk_rows=%lld < 0", (long long)chunk_rows);
+    if (n == 0 && dims && K) return LCREC_OK;              // empty batch
+    if (!x || !dims || !W || !b || !codebooks || !K || !idx_out)
+        return fail(LCREC_EINVAL, "encode_assign: NULL pointer");
+    // Chunk pipelines: chunk c runs on pipeline c % P, pipeline 0 being the caller's stream and pipeline 1 the
+    // context's first helper stream, forked from the caller's and joined back before the quantiser pass -- so two
+    // layers' kernels are in flight at once and their workgroups interleave on the CUs: one kernel's store bursts,
+    // prologues, narrow tail layers and last partial round run under the other's K loops.  Measured on C3: P = 2 is
+    // +1.5 .. +1.9 % over P = 1 in the common case, P = 3 and 4 give nothing -- but in a few percent of passes one stream's
+    // persistent launches are starved of CUs by the other's and the pass takes 1.6-3x (tools/generate_probe.py: wall 101 ms
+    // with 125 ms of kernel brackets against 61 / 120), so P = 1 is the default.  The call does not synchronise with the host.
+    lcrec_encode_plan p;
+    if (int rc = enc_plan(n, dims, n_layers, K, L, chunk_rows, ctx ? ctx->pipelines : 1, &p)) return rc;
+    if (!workspace || workspace_bytes < (size_t)p.total_bytes)
+        return fail(LCREC_EWORKSPACE, "encode_assign: workspace %zu B < required %zu B", workspace_bytes, (size_t)p.total_bytes);
+    if (int rc = check_context(ctx, "encode_assign")) return rc;
+    char *ws = reinterpret_cast<char *>(workspace);
+    float *latent = latent_out ? latent_out : reinterpret_cast<float *>(ws + p.latent_offset);
+    const int e = dims[n_layers];
+    if (p.pipelines > 1) {
+        if (int rc = ctx->ensure_streams()) return rc;
+    }
+    {
+        ForkJoin fj(ctx, s, p.pipelines > 1 ? 1u : 0u);    // joins on every exit from this block
+        for (int64_t c = 0; c < p.n_chunks; ++c) {
+            const lcrec_encode_chunk k = enc_chunk(p, c);
+            const float *src = x + k.row0 * dims[0];
+            hipStream_t cs = k.pipeline ? fj.on(k.pipeline - 1) : s;
+            for (int l = 0; l < n_layers; ++l) {
+                const bool last = l == n_layers - 1;
+                float *dst = last ? latent + k.row0 * e : reinterpret_cast<float *>(ws + p.act_offset[k.first_act + (l & 1)]);
+                int rc = linear_forward(src, k.rows, dims[l], W[l], b[l], bn_scale ? bn_scale[l] : nullptr,
+                                        bn_shift ? bn_shift[l] : nullptr, last ? 0 : 1, dims[l + 1], dst, cs);
+                if (rc) return rc;
+                src = dst;
+            }
+        }
+    }
+    return rq_assign(latent, n, e, codebooks, K, L, idx_out, L, xq_out, 0, sse_out, nullptr, margin_out, neartie_out, tie_tau,
+                     ws + p.rq_offset, (size_t)p.rq_bytes, nullptr, s);
+}
 
 LCREC_API int lcrec_encode_assign(const float *x, int64_t n, const int *dims, int n_layers,
                                   const float *const *W, const float *const *b,
@@ -237,60 +334,20 @@ LCREC_API int lcrec_encode_assign(const float *x, int64_t n, const int *dims, in
                                   float *margin_out, uint32_t *neartie_out, float tie_tau,
                                   void *workspace, size_t workspace_bytes, lcrec_context *ctx, void *stream)
 {
-    if (n == 0 && dims && K) return LCREC_OK;              // empty batch
-    if (!x || !dims || !W || !b || !codebooks || !K || !idx_out)
-        return fail(LCREC_EINVAL, "encode_assign: NULL pointer");
-    if (n_layers < 1 || n_layers > LCREC_MAX_LAYERS)
-        return fail(LCREC_EINVAL, "encode_assign: n_layers=%d out of range", n_layers);
-    if (n < 0) return fail(LCREC_EINVAL, "encode_assign: n < 0");
-    if (n == 0) return LCREC_OK;
-    const size_t need = lcrec_encode_assign_workspace(n, dims, n_layers, K, L);
-    if (!workspace || workspace_bytes < need)
-        return fail(LCREC_EWORKSPACE, "encode_assign: workspace %zu B < required %zu B", workspace_bytes, need);
-    if (int rc = check_context(ctx, "encode_assign")) return rc;
-    const EncLayout o = enc_layout(n, dims, n_layers, K, L);
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *latent = latent_out ? latent_out : reinterpret_cast<float *>(ws + 2 * ENC_PIPES_MAX * o.act_bytes);
-    void *rq_ws = ws + 2 * ENC_PIPES_MAX * o.act_bytes + o.latent_bytes;
-    const int e = dims[n_layers];
-    hipStream_t s = (hipStream_t)stream;
+    return encode_assign(x, n, dims, n_layers, W, b, bn_scale, bn_shift, codebooks, K, L, idx_out, latent_out, xq_out, sse_out,
+                         margin_out, neartie_out, tie_tau, workspace, workspace_bytes, ctx, (hipStream_t)stream, 0);
+}
 
-    // Chunk pipelines: chunk c runs on pipeline c % P, pipeline 0 being the caller's stream and pipeline 1 the
-    // context's first helper stream, forked from the caller's and joined back before the quantiser pass -- so two
-    // layers' kernels are in flight at once and their workgroups interleave on the CUs: one kernel's store bursts,
-    // prologues, narrow tail layers and last partial round run under the other's K loops.  Measured on C3: P = 2 is
-    // +1.5 .. +1.9 % over P = 1 in the common case, P = 3 and 4 give nothing -- but in a few percent of passes one stream's
-    // persistent launches are starved of CUs by the other's and the pass takes 1.6-3x (tools/generate_probe.py: wall 101 ms
-    // with 125 ms of kernel brackets against 61 / 120), so P = 1 is the default.  The call does not synchronise with the host.
-    const int64_t n_chunks = (n + o.chunk - 1) / o.chunk;
-    int P = ctx ? ctx->pipelines : 1;
-    if (P > ENC_PIPES_MAX) P = ENC_PIPES_MAX;
-    if (n_chunks < P) P = (int)n_chunks;
-    if (P > 1) {
-        if (int rc = ctx->ensure_streams()) return rc;
-    }
-    {
-        ForkJoin fj(ctx, s, P > 1 ? 1u : 0u);              // joins on every exit from this block
-        int64_t c = 0;
-        for (int64_t i0 = 0; i0 < n; i0 += o.chunk, ++c) {
-            const int64_t m = (n - i0 < o.chunk) ? n - i0 : o.chunk;
-            const float *src = x + i0 * dims[0];
-            const int pipe = (int)(c % P);
-            hipStream_t cs = pipe ? fj.on(pipe - 1) : s;
-            float *act[2] = {reinterpret_cast<float *>(ws + (size_t)(2 * pipe) * o.act_bytes),
-                             reinterpret_cast<float *>(ws + (size_t)(2 * pipe + 1) * o.act_bytes)};
-            for (int l = 0; l < n_layers; ++l) {
-                const bool last = l == n_layers - 1;
-                float *dst = last ? latent + i0 * e : act[l & 1];
-                int rc = linear_forward(src, m, dims[l], W[l], b[l], bn_scale ? bn_scale[l] : nullptr,
-                                        bn_shift ? bn_shift[l] : nullptr, last ? 0 : 1, dims[l + 1], dst, cs);
-                if (rc) return rc;
-                src = dst;
-            }
-        }
-    }
-    return rq_assign(latent, n, e, codebooks, K, L, idx_out, L, xq_out, 0, sse_out, nullptr, margin_out, neartie_out, tie_tau,
-                     rq_ws, o.rq_bytes, nullptr, s);
+LCREC_API int lcrec_debug_encode_assign(const float *x, int64_t n, const int *dims, int n_layers,
+                                        const float *const *W, const float *const *b,
+                                        const float *const *bn_scale, const float *const *bn_shift,
+                                        const float *codebooks, const int *K, int L, int64_t *idx_out,
+                                        float *latent_out, float *xq_out, double *sse_out,
+                                        float *margin_out, uint32_t *neartie_out, float tie_tau,
+                                        void *workspace, size_t workspace_bytes, lcrec_context *ctx, void *stream, int64_t chunk_rows)
+{
+    return encode_assign(x, n, dims, n_layers, W, b, bn_scale, bn_shift, codebooks, K, L, idx_out, latent_out, xq_out, sse_out,
+                         margin_out, neartie_out, tie_tau, workspace, workspace_bytes, ctx, (hipStream_t)stream, chunk_rows);
 }
 
 LCREC_API int lcrec_trace_enable(int on)

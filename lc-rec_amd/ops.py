@@ -522,13 +522,42 @@ def rq_assign_into(z, codebooks_flat, ks, idx, idx_stride, xq=None, xq_accumulat
     _lib.check(rc, what)
 
 
+def encode_plan(n, dims, ks, chunk_rows=0, pipelines=None):
+    """How encode_assign walks n rows of an encoder of widths `dims` (in_dim, hidden sizes ..., e_dim) and where everything lies in
+    its workspace (include/lcrec.h, lcrec_debug_encode_assign_plan): (dict of the fields of lcrec_encode_plan, list of one dict per
+    chunk of the fields of lcrec_encode_chunk).  chunk_rows: 0 = the built-in chunk; pipelines: None = the current set_pipelines
+    setting.  Host only: no GPU is needed.  LcrecError for arguments lcrec_encode_assign refuses."""
+    lib = _lib.load()
+    plan = _lib.EncodePlan()
+    nl, L = len(dims) - 1, len(ks)
+    P = _pipelines if pipelines is None else int(pipelines)
+    darr, karr = _ints(dims), _ints(ks)
+    rc = lib.lcrec_debug_encode_assign_plan(int(n), darr, nl, karr, L, int(chunk_rows), P, ctypes.addressof(plan), None, 0)
+    _lib.check(rc, "lcrec_debug_encode_assign_plan")
+    count = int(plan.n_chunks)
+    buf = (_lib.EncodeChunk * max(count, 1))()
+    rc = lib.lcrec_debug_encode_assign_plan(int(n), darr, nl, karr, L, int(chunk_rows), P, ctypes.addressof(plan), ctypes.addressof(buf), count)
+    _lib.check(rc, "lcrec_debug_encode_assign_plan")
+    out = {}
+    for name, _ in _lib.EncodePlan._fields_:
+        value = getattr(plan, name)
+        out[name] = [int(v) for v in value] if name == "act_offset" else int(value)
+    return out, [{name: int(getattr(buf[c], name)) for name, _ in _lib.EncodeChunk._fields_} for c in range(count)]
+
+
 def encode_assign(x, weights, biases, codebooks_flat, ks, bn_scales=None, bn_shifts=None, want_latent=False,
-                  want_xq=False, want_sse=False, audit=None, tie_tau=None):
+                  want_xq=False, want_sse=False, audit=None, tie_tau=None, chunk_rows=None, into=None, workspace=None):
     """RQVAE.get_indices(xs, use_sk=False) (rqvae.py:68-72): encoder MLP + L-level argmin assignment.
     audit / tie_tau: as rq_assign (near-tie audit of the quantiser).
 
     weights[l] is nn.Linear.weight of encoder layer l ([out_l, in_l]); bn_scales/bn_shifts are
-    per-layer folded eval-mode BatchNorm affines or None.
+    per-layer folded eval-mode BatchNorm affines or None (the whole list, or single entries).
+    chunk_rows: None = lcrec_encode_assign; a number = lcrec_debug_encode_assign with that chunk size (0: the built-in one) -- the
+    same launch code, for the tests (encode_plan reports the walk).
+    into: a dict of buffers the caller owns, written instead of fresh ones -- "idx" int64 (required), "latent", "xq", "margin"
+    float32, "sse" float64, "neartie" int32, each contiguous on x's device with at least the elements the call writes (it may
+    be LARGER, so that a test can look at what lies past the end); an output that is not in the dict is passed as NULL, and
+    want_* / audit are not read.  workspace: a uint8 device tensor passed as the workspace as it is, its size included.
     Returns (idx, latent | None, xq | None, sse | None)."""
     lib = _lib.load()
     x = _dev(x, "x")
@@ -545,24 +574,47 @@ def encode_assign(x, weights, biases, codebooks_flat, ks, bn_scales=None, bn_shi
         if ws_[l].shape[1] != dims[l]:
             raise _lib.LcrecError(f"encoder layer {l}: weight {tuple(ws_[l].shape)} does not chain")
     n, e, L, dev = x.shape[0], dims[-1], len(ks), x.device
-    idx = torch.empty((n, L), dtype=torch.int64, device=dev)
-    latent = torch.empty((n, e), dtype=torch.float32, device=dev) if want_latent else None
-    xq = torch.empty((n, e), dtype=torch.float32, device=dev) if want_xq else None
-    sse = torch.zeros(L, dtype=torch.float64, device=dev) if want_sse else None
+    if into is None:
+        idx = torch.empty((n, L), dtype=torch.int64, device=dev)
+        latent = torch.empty((n, e), dtype=torch.float32, device=dev) if want_latent else None
+        xq = torch.empty((n, e), dtype=torch.float32, device=dev) if want_xq else None
+        sse = torch.zeros(L, dtype=torch.float64, device=dev) if want_sse else None
+        margin, neartie, tau = _audit_buffers(audit, tie_tau, n, L, dev)
+    else:
+        sizes = {"idx": (torch.int64, n * L), "latent": (torch.float32, n * e), "xq": (torch.float32, n * e),
+                 "sse": (torch.float64, L), "margin": (torch.float32, n * L), "neartie": (torch.int32, n)}
+        if "idx" not in into or set(into) - set(sizes):
+            raise _lib.LcrecError(f"into must hold idx and may hold {sorted(sizes)}, got {sorted(into)}")
+        for name, t in into.items():
+            dtype, need = sizes[name]
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()
+                    and t.numel() >= need):
+                raise _lib.LcrecError(f"into[{name!r}] must be a contiguous {dtype} tensor on x's device with at least {need} elements")
+        idx, latent, xq, sse, margin, neartie = (into.get(k) for k in ("idx", "latent", "xq", "sse", "margin", "neartie"))
+        tau = float(tie_tau or 0.0)
+    if workspace is not None and not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == dev
+                                      and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise _lib.LcrecError("workspace must be a contiguous uint8 tensor on x's device")
     PA = ctypes.c_void_p * nl
     wp = PA(*[t.data_ptr() for t in ws_])
     bp = PA(*[t.data_ptr() for t in bs_])
-    scp = PA(*[0 if t is None else t.data_ptr() for t in scs])
-    shp = PA(*[0 if t is None else t.data_ptr() for t in shs])
+    scp = None if bn_scales is None else PA(*[0 if t is None else t.data_ptr() for t in scs])    # (no list: the NULL array)
+    shp = None if bn_shifts is None else PA(*[0 if t is None else t.data_ptr() for t in shs])
     darr, karr = _ints(dims), _ints(ks)
-    margin, neartie, tau = _audit_buffers(audit, tie_tau, n, L, dev)
     with _on(dev):
-        nbytes = lib.lcrec_encode_assign_workspace(n, darr, nl, karr, L)
-        ws = _workspace(nbytes, dev)
-        rc = lib.lcrec_encode_assign(_ptr(x), n, darr, nl, wp, bp, scp, shp, _ptr(cb), karr, L, _ptr(idx),
-                                     _ptr(latent), _ptr(xq), _ptr(sse), _ptr(margin), _ptr(neartie), tau, _ptr(ws),
-                                     ws.numel(), _context(dev), _stream_ptr())
-    _lib.check(rc, "lcrec_encode_assign")
+        if workspace is not None:
+            ws = workspace
+        elif chunk_rows is None:
+            ws = _workspace(lib.lcrec_encode_assign_workspace(n, darr, nl, karr, L), dev)
+        else:
+            ws = _workspace(lib.lcrec_debug_encode_assign_workspace(n, darr, nl, karr, L, int(chunk_rows)), dev)
+        args = (_ptr(x), n, darr, nl, wp, bp, scp, shp, _ptr(cb), karr, L, _ptr(idx), _ptr(latent), _ptr(xq), _ptr(sse),
+                _ptr(margin), _ptr(neartie), tau, _ptr(ws), ws.numel(), _context(dev), _stream_ptr())
+        if chunk_rows is None:
+            rc, what = lib.lcrec_encode_assign(*args), "lcrec_encode_assign"
+        else:
+            rc, what = lib.lcrec_debug_encode_assign(*args, int(chunk_rows)), "lcrec_debug_encode_assign"
+    _lib.check(rc, what)
     return idx, latent, xq, sse
 
 

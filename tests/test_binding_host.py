@@ -43,7 +43,7 @@ def test_records_have_the_layout_the_c_compiler_gives_them(binding, tmp_path):
     for name, cls in binding.STRUCTS.items():
         want[name] = (ctypes.sizeof(cls),)
         want.update({f"{name}.{f}": (getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_})
-    assert len(binding.STRUCTS) >= 10 and sum(len(c._fields_) for c in binding.STRUCTS.values()) >= 110
+    assert len(binding.STRUCTS) >= 13 and sum(len(c._fields_) for c in binding.STRUCTS.values()) >= 133
     assert got == want
 
 
@@ -52,6 +52,7 @@ def test_constants_follow_c(binding, header):
     c = binding.parse_header(header)[0]
     assert (c["LCREC_ABI_VERSION"], c["LCREC_OK"], c["LCREC_EINVAL"], c["LCREC_EHIP"], c["LCREC_MAX_LEVELS"]) == (3, 0, -1, -4, 16)
     assert (c["LCREC_DTYPE_F16"], c["LCREC_DTYPE_F64"], c["LCREC_SK_GROUP_CLASSES"]) == (1, 2, 5)
+    assert (c["LCREC_ENC_PIPES_MAX"], c["LCREC_ENC_ACT_BUFFERS"]) == (2, 4)
     assert (c["LCREC_SK_TABLE_SYNCHRONOUS"], c["LCREC_BN_BACKWARD_APPLY"], c["LCREC_TAILK_CS_PER_LEVEL"], c["LCREC_GEMMR_FORWARD"]) == (3, 4, 8, 3)
     c = binding.parse_header(damaged(header, "LCREC_GEMMK_32x64,", "LCREC_GEMMK_32x64 = 0x10,"))[0]
     assert (c["LCREC_GEMMK_TILE_BODY"], c["LCREC_GEMMK_32x64"], c["LCREC_GEMMK_REDUCER"], c["LCREC_GEMMK_PP"]) == (0, 16, 17, 18)
@@ -78,11 +79,16 @@ def test_what_the_parser_cannot_type_is_an_error_naming_the_declaration(binding,
 def test_the_result_follows_the_header(binding, header):
     """An extra parameter, a widened parameter and a field inserted mid-record each move exactly what they should."""
     _, structs, sigs = binding.parse_header(header)
-    assert tuple(sigs) == binding.EXPORTS and len(sigs) >= 69
+    assert tuple(sigs) == binding.EXPORTS and len(sigs) >= 73
     res, args = sigs["lcrec_cast_rows"]
     assert res is ctypes.c_int and args == [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
     assert sigs["lcrec_last_error"] == (ctypes.c_char_p, []) and sigs["lcrec_context_create"] == (ctypes.c_int, [ctypes.c_void_p])
     assert sigs["lcrec_rq_assign_workspace"] == (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int])
+    assert sigs["lcrec_debug_encode_assign_workspace"] == (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                                             ctypes.c_int, ctypes.c_int64])
+    assert sigs["lcrec_debug_encode_assign"][1] == sigs["lcrec_encode_assign"][1] + [ctypes.c_int64]
+    assert [f for f, _ in structs["lcrec_encode_chunk"]._fields_] == ["row0", "rows", "pipeline", "first_act"]
+    assert ctypes.sizeof(structs["lcrec_encode_plan"]) == 8 * (10 + binding.CONSTANTS["LCREC_ENC_ACT_BUFFERS"])
 
     more = binding.parse_header(damaged(header, "float *dst, void *hip_stream);", "float *dst, void *hip_stream, uint32_t flags);"))[2]
     assert more["lcrec_cast_rows"] == (res, args + [ctypes.c_uint32])

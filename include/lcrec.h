@@ -559,16 +559,39 @@ int lcrec_cast_rows(const void *src, int src_dtype, int64_t count, float *dst, v
  * groups (tuples held by >= 2 items) by first occurrence of the tuple in item order, item ids
  * ascending inside a group.
  *   idx               device [n][L] int64, K host [L] (codes per level; sum of ceil(log2 K) <= 128)
+ *                     A code outside its level's range is clamped into it before tuples are compared: v < 0 counts as 0,
+ *                     v >= K[l] as K[l] - 1.  So the -1 an index matrix is pre-filled with collides with code 0, and two
+ *                     out-of-range codes on the same side of a level are the same code.  idx itself is never written.
  *   members_out       device [n] int64 or NULL: ids of the items of all groups, group after group
  *   group_offsets_out device [n/2+2] int64 or NULL (given together with members_out):
  *                     group g = members_out[off[g] .. off[g+1])
- *   counters_out      device int64[4]: {distinct tuples, groups, items in groups, largest tuple count}
- *                     (entries 1 and 2 only when members_out is given);
- *                     collision_rate = (n - counters[0]) / n */
+ *                     Only members_out[0 .. counters[2]) and group_offsets_out[0 .. counters[1]] are written.
+ *   counters_out      device int64[4]: {distinct tuples, groups, items in groups, largest tuple count};
+ *                     entries 1 and 2 are 0 when members_out is NULL;
+ *                     collision_rate = (n - counters[0]) / n
+ * The argument checks (NULL pointers, n, L, K[l] < 1, more than 128 bits, members without offsets, a workspace smaller than
+ * lcrec_collision_groups_workspace(n, L) for n > 0) return before the device is touched.  The workspace may hold anything. */
 size_t lcrec_collision_groups_workspace(int64_t n, int L);
 int lcrec_collision_groups(const int64_t *idx, int64_t n, int L, const int *K, int64_t *members_out,
                            int64_t *group_offsets_out, int64_t *counters_out, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* What lcrec_collision_groups decides on the host for n items of L levels with K[l] codes: the key layout, the bit ranges of its
+ * three sorts and where everything lies in the workspace.  lcrec_collision_groups runs by the same function and
+ * lcrec_collision_groups_workspace returns its workspace_bytes.  Host only: nothing is launched.  n >= 0 (0 is sized as 1).
+ * The key of a tuple is its clamped codes, level 0 in the highest bits, bits[l] bits per level; bit b of the key is bit b of
+ * the low word for b < 64, bit b - 64 of the high word above. */
+typedef struct {
+    int bits[LCREC_MAX_LEVELS];   /* ceil(log2 K[l]) (0 for K = 1); 0 past L */
+    int total_bits;               /* their sum, at most 128 */
+    int lo_bits;                  /* bits [0, lo_bits) of the low word are sorted first: min(total_bits, 64), 1 for a 0-bit key */
+    int hi_bits;                  /* then bits [0, hi_bits) of the high word: total_bits - 64; 0 = no second pass (<= 64 bits) */
+    int id_bits;                  /* the last sort, by first item id, over bits [0, id_bits): the smallest b >= 1 with 2^b >= n */
+    int64_t stride;               /* bytes from one of the ten n-element arrays to the next: n * 8 rounded up to 256 */
+    int64_t temp_bytes;           /* the sorts' and scans' scratch behind the arrays (what rocPRIM asks for on this device) */
+    int64_t workspace_bytes;      /* 10 * stride + temp_bytes */
+} lcrec_collision_plan;
+int lcrec_debug_collision_plan(int64_t n, int L, const int *K, lcrec_collision_plan *out);
 
 /* Nearest-free-code finishing pass: an opt-in step BEYOND the reference.  index/generate_indices.py:107-136 stops after its 20
  * conflict rounds and writes out whatever still collides; this entry follows on from there and gives every item that still shares

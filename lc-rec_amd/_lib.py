@@ -133,6 +133,7 @@ EncodeChunk = STRUCTS["lcrec_encode_chunk"]
 BnPlan = STRUCTS["lcrec_bn_plan"]
 StepTailPlan = STRUCTS["lcrec_step_tail_plan"]
 OptimPlan = STRUCTS["lcrec_optim_plan"]
+CollisionPlan = STRUCTS["lcrec_collision_plan"]
 GemmLaunch = STRUCTS["lcrec_gemm_launch"]
 TraceEntry = STRUCTS["lcrec_trace_entry"]
 

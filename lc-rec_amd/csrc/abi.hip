@@ -441,6 +441,11 @@ LCREC_API int lcrec_collision_groups(const int64_t *idx, int64_t n, int L, const
                             (hipStream_t)stream);
 }
 
+LCREC_API int lcrec_debug_collision_plan(int64_t n, int L, const int *K, lcrec_collision_plan *out)
+{
+    return debug_collision_plan(n, L, K, out);
+}
+
 LCREC_API int lcrec_finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e,
                                         const float *codebook_last, const int64_t *bucket_members, const int64_t *bucket_offsets,
                                         int64_t n_buckets, int64_t *counters_out, void *stream)

@@ -130,44 +130,71 @@ static size_t prim_temp_bytes(int64_t n)
     return align_up(m, 256) + 256;
 }
 
+// Everything collision_groups decides before it launches (include/lcrec.h, lcrec_collision_plan): collision_groups runs by it,
+// collision_workspace returns its total and lcrec_debug_collision_plan reports it.  K == nullptr: the sizes alone (they do not
+// depend on the key).
+static int collision_plan(int64_t n, int L, const int *K, lcrec_collision_plan *p)
+{
+    *p = lcrec_collision_plan{};
+    if (n < 0 || L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "collision_groups: bad n or L");
+    for (int l = 0; K && l < L; ++l) {
+        if (K[l] < 1) return fail(LCREC_EINVAL, "collision_groups: K[%d]=%d", l, K[l]);
+        int b = 0;
+        while ((1LL << b) < K[l]) ++b;
+        p->bits[l] = b;
+        p->total_bits += b;
+    }
+    if (p->total_bits > 128)
+        return fail(LCREC_EUNSUPPORTED, "collision_groups: tuples need %d bits (> 128)", p->total_bits);
+    p->lo_bits = p->total_bits > 64 ? 64 : (p->total_bits > 0 ? p->total_bits : 1);
+    p->hi_bits = p->total_bits > 64 ? p->total_bits - 64 : 0;
+    const int64_t items = n > 0 ? n : 1;
+    p->id_bits = 1;
+    while ((1LL << p->id_bits) < items) ++p->id_bits;
+    p->stride = (int64_t)align_up((size_t)items * 8, 256);
+    p->temp_bytes = (int64_t)prim_temp_bytes(items);
+    p->workspace_bytes = 10 * p->stride + p->temp_bytes;
+    return LCREC_OK;
+}
+
+int debug_collision_plan(int64_t n, int L, const int *K, lcrec_collision_plan *out)
+{
+    if (!K || !out) return fail(LCREC_EINVAL, "collision_groups: NULL pointer");
+    return collision_plan(n, L, K, out);
+}
+
 size_t collision_workspace(int64_t n, int L)
 {
-    (void)L;
-    const size_t arr = align_up((size_t)(n > 0 ? n : 1) * 8, 256);
-    return 10 * arr + prim_temp_bytes(n > 0 ? n : 1);
+    (void)L;   // the sizes depend on n alone
+    lcrec_collision_plan p;
+    return collision_plan(n > 0 ? n : 1, 1, nullptr, &p) == LCREC_OK ? (size_t)p.workspace_bytes : 0;
 }
 
 int collision_groups(const int64_t *idx, int64_t n, int L, const int *K, int64_t *members_out, int64_t *offsets_out,
                      int64_t *counters_out, void *workspace, size_t workspace_bytes, hipStream_t stream)
 {
     if ((n > 0 && !idx) || !K || !counters_out) return fail(LCREC_EINVAL, "collision_groups: NULL pointer");
-    if (n < 0 || L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "collision_groups: bad n or L");
     if ((members_out == nullptr) != (offsets_out == nullptr))
         return fail(LCREC_EINVAL, "collision_groups: members_out and offsets_out go together");
+    lcrec_collision_plan plan;
+    if (int rc = collision_plan(n, L, K, &plan)) return rc;
+    if (n > 0 && (!workspace || workspace_bytes < (size_t)plan.workspace_bytes))
+        return fail(LCREC_EWORKSPACE, "collision_groups: workspace %zu B < required %zu B", workspace_bytes,
+                    (size_t)plan.workspace_bytes);
     PackDesc d;
     d.L = L;
-    int total_bits = 0;
     for (int l = 0; l < L; ++l) {
-        if (K[l] < 1) return fail(LCREC_EINVAL, "collision_groups: K[%d]=%d", l, K[l]);
-        int b = 0;
-        while ((1LL << b) < K[l]) ++b;
-        d.bits[l] = b;
+        d.bits[l] = plan.bits[l];
         d.K[l] = K[l];
-        total_bits += b;
     }
-    if (total_bits > 128)
-        return fail(LCREC_EUNSUPPORTED, "collision_groups: tuples need %d bits (> 128)", total_bits);
     hipError_t he = hipMemsetAsync(counters_out, 0, 4 * sizeof(int64_t), stream);
     if (he != hipSuccess) return fail(LCREC_EHIP, "collision_groups: %s", hipGetErrorString(he));
     if (n == 0) {
         if (offsets_out) he = hipMemsetAsync(offsets_out, 0, sizeof(int64_t), stream);
         return he == hipSuccess ? LCREC_OK : fail(LCREC_EHIP, "collision_groups: %s", hipGetErrorString(he));
     }
-    const size_t need = collision_workspace(n, L);
-    if (!workspace || workspace_bytes < need)
-        return fail(LCREC_EWORKSPACE, "collision_groups: workspace %zu B < required %zu B", workspace_bytes, need);
 
-    const size_t arr = align_up((size_t)n * 8, 256);
+    const size_t arr = (size_t)plan.stride;
     char *ws = reinterpret_cast<char *>(workspace);
     auto take = [&]() { char *p = ws; ws += arr; return p; };
     uint64_t *klo = (uint64_t *)take(), *khi = (uint64_t *)take();
@@ -175,7 +202,7 @@ int collision_groups(const int64_t *idx, int64_t n, int L, const int *K, int64_t
     int64_t *ia = (int64_t *)take(), *ib = (int64_t *)take();
     int64_t *s0 = (int64_t *)take(), *s1 = (int64_t *)take(), *s2 = (int64_t *)take(), *s3 = (int64_t *)take();
     void *temp = ws;
-    size_t temp_bytes = prim_temp_bytes(n);
+    const size_t temp_bytes = (size_t)plan.temp_bytes;
     unsigned long long *counters = reinterpret_cast<unsigned long long *>(counters_out);
 
     const unsigned grid = (unsigned)((n + 255) / 256);
@@ -183,15 +210,14 @@ int collision_groups(const int64_t *idx, int64_t n, int L, const int *K, int64_t
     hipLaunchKernelGGL(pack_keys_kernel, dim3(grid), dim3(256), 0, stream, idx, n, d, klo, khi, ia);
 
     // stable sort by the low word, then (if the tuple is wider than 64 bits) by the high word
-    const int lo_bits = total_bits > 64 ? 64 : (total_bits > 0 ? total_bits : 1);
     size_t tb = temp_bytes;
-    he = rocprim::radix_sort_pairs(temp, tb, klo, ka, ia, ib, (size_t)n, 0, lo_bits, stream, false);
+    he = rocprim::radix_sort_pairs(temp, tb, klo, ka, ia, ib, (size_t)n, 0, plan.lo_bits, stream, false);
     if (he != hipSuccess) return fail(LCREC_EHIP, "collision_groups: sort: %s", hipGetErrorString(he));
     int64_t *ids = ib, *spare = ia;
-    if (total_bits > 64) {
+    if (plan.hi_bits > 0) {
         hipLaunchKernelGGL(gather_u64_kernel, dim3(grid), dim3(256), 0, stream, khi, ids, n, ka);
         tb = temp_bytes;
-        he = rocprim::radix_sort_pairs(temp, tb, ka, kb, ids, spare, (size_t)n, 0, total_bits - 64, stream, false);
+        he = rocprim::radix_sort_pairs(temp, tb, ka, kb, ids, spare, (size_t)n, 0, plan.hi_bits, stream, false);
         if (he != hipSuccess) return fail(LCREC_EHIP, "collision_groups: sort: %s", hipGetErrorString(he));
         int64_t *t = ids; ids = spare; spare = t;
     }
@@ -202,10 +228,8 @@ int collision_groups(const int64_t *idx, int64_t n, int L, const int *K, int64_t
     if (he != hipSuccess) return fail(LCREC_EHIP, "collision_groups: scan: %s", hipGetErrorString(he));
     hipLaunchKernelGGL(first_ids_kernel, dim3(grid), dim3(256), 0, stream, ids, s1, n, ka);
     // order groups by first occurrence (ids stay ascending inside a group: the sort is stable)
-    int idbits = 1;
-    while ((1LL << idbits) < n) ++idbits;
     tb = temp_bytes;
-    he = rocprim::radix_sort_pairs(temp, tb, ka, kb, ids, spare, (size_t)n, 0, idbits, stream, false);
+    he = rocprim::radix_sort_pairs(temp, tb, ka, kb, ids, spare, (size_t)n, 0, plan.id_bits, stream, false);
     if (he != hipSuccess) return fail(LCREC_EHIP, "collision_groups: sort: %s", hipGetErrorString(he));
     int64_t *ids2 = spare;
     uint64_t *fid2 = kb;

@@ -956,6 +956,17 @@ def collision_groups(idx, ks, want_groups=True):
     return out
 
 
+def collision_plan(n, ks):
+    """What collision_groups decides on the host for n items of len(ks) levels (include/lcrec.h, lcrec_debug_collision_plan), as a
+    dict of the fields of lcrec_collision_plan, `bits` a list of one entry per level.  Host only: no GPU is needed."""
+    plan = _lib.CollisionPlan()
+    rc = _lib.load().lcrec_debug_collision_plan(int(n), len(ks), _ints(ks), ctypes.addressof(plan))
+    _lib.check(rc, "lcrec_debug_collision_plan")
+    out = {name: int(getattr(plan, name)) for name, _ in _lib.CollisionPlan._fields_ if name != "bits"}
+    out["bits"] = list(plan.bits)[:len(ks)]
+    return out
+
+
 def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
     """The nearest-free-code finishing pass (lcrec_finish_nearest_free of include/lcrec.h, which states the rule): every item of
     a bucket -- `members[offsets[b]:offsets[b+1]]`, the items sharing idx[:, :L-1], ids ascending -- that still shares its last

@@ -720,6 +720,50 @@ int lcrec_spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, c
                              const int64_t *super_members, const int64_t *super_offsets, int64_t n_super_buckets,
                              int64_t *counters_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Index audit: GIVEN tuples walked through the residual quantiser.  lcrec_finish_nearest_free, lcrec_extend_nearest_free and
+ * lcrec_spill_nearest_free -- and the reference's own Sinkhorn rounds -- deliberately give some items a code that is not their
+ * nearest one.  This entry says what that cost, per item and level: the distance of the held code, the best distance and the held
+ * code's place in the distance ranking.  Beyond the reference, which reports a collision rate and nothing else.
+ *
+ * The rule.  For item i with latent z_i and held tuple h_i[0 .. L), start with r_0 = z_i and go through the levels l = 0 .. L-1.
+ *   1. Distances.  d_l(k) = (xx + cc_k) - 2*dot_k for every code k of level l, xx, cc_k and dot_k each one fp32 fma chain over the
+ *      dimension ascending from 0: the distance of lcrec_rq_assign and lcrec_finish_nearest_free, bit for bit.  A NaN distance
+ *      counts as +inf wherever distances are compared, and is reported as +inf.
+ *   2. Held code.  h = h_i[l] brought into [0, K[l]) by the rule of lcrec_rq_apply_level, decided on the int64 value: below 0
+ *      counts as 0, K[l] and above as K[l] - 1.  If the code had to be clamped, bit l of flags_out[i] is set.
+ *   3. d_held = d_l(h); best = the first minimum of d_l in code order (what lcrec_rq_assign picks on this residual);
+ *      d_best = d_l(best); rank = #{k : d_l(k) < d_l(h)} + #{k < h : d_l(k) == d_l(h)}.  So rank == 0 <=> h == best, and
+ *      0 <= rank < K[l].
+ *   4. Residual.  It follows the HELD code as lcrec_rq_assign updates it, three fp32 operations per element with c = C_l[h] and
+ *      r = r_l: t = c - r; s = r + t; r_{l+1} = r - s.
+ * After the last level err = the fp32 fma chain of r_L[j] * r_L[j] over j ascending from 0.
+ * Consequences: a tuple written by lcrec_rq_assign / lcrec_encode_assign for the same latent and codebooks has rank 0 and
+ * d_held == d_best at every level, and its r_L is that call's last residual, bit for bit; the first level with rank > 0 is where a
+ * tuple leaves the greedy path; an item that lcrec_finish_nearest_free moved from its greedy code has rank >= 1 at the last level
+ * and rank 0 before it.
+ *
+ *   z, codebooks, K   as lcrec_rq_assign; e in {16, 32, 64}; 1 <= L <= LCREC_MAX_LEVELS.  Every level lcrec_rq_assign takes is
+ *                     taken (the level's rows and cc in LDS: K[l] * (4 e + 20) bytes, less than lcrec_rq_assign needs for it);
+ *                     one it refuses is LCREC_EUNSUPPORTED
+ *   idx               device int64, read only: item i's held code of level l at idx[i*idx_stride + l]; idx_stride >= L, 0 = L
+ *   d_held_out, d_best_out   device [n][L] float
+ *   rank_out          device [n][L] int (32-bit)
+ *   best_out          device [n][L] int64, or NULL
+ *   err_out           device [n] float
+ *   resid_out         device [n][e] float, or NULL: r_L
+ *   flags_out         device [n] uint32
+ *   workspace         device, lcrec_rq_audit_workspace() bytes: the residual between the levels (0 for L == 1)
+ * Every output element of rows [0, n) is written by every call.  The float arrays 16-byte aligned, the int64 arrays 8-byte.
+ * n == 0: no launch.  One launch per level: one item per lane, the lane sweeps the level's codes once.  No allocation, no host
+ * synchronisation, capturable.  Argument errors (LCREC_EINVAL: a NULL pointer, e, L, K[l] < 1, idx_stride < L, misalignment;
+ * LCREC_EWORKSPACE) are reported before the device is touched, with a last-error text that names the argument.  Traced as
+ * "rq_audit", one bracket per call.  lcrec_rq_audit_workspace returns 0 for arguments lcrec_rq_audit refuses. */
+size_t lcrec_rq_audit_workspace(int64_t n, int e, const int *K, int L);
+int lcrec_rq_audit(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L,
+                   const int64_t *idx, int64_t idx_stride, float *d_held_out, float *d_best_out, int *rank_out,
+                   int64_t *best_out, float *err_out, float *resid_out, uint32_t *flags_out,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
 /* Text of the `.index.json` entries for a run of items (host-side; no device work).  Replaces the
  * per-item Python of index/generate_indices.py:83-92 (token strings "<a_{i}>", "<b_{j}>", ...) and the
  * json.dump of :138-145, whose default separators (", " and ": ") every consumer relies on

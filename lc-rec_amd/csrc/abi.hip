@@ -29,7 +29,7 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
                                            "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free",
-                                           "spill_nearest_free", "spill_keepers"};
+                                           "spill_nearest_free", "spill_keepers", "rq_audit"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -473,6 +473,17 @@ LCREC_API int lcrec_spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen
     return spill_nearest_free(idx, n, n_frozen, L, K, resid_prev, resid_last, e, codebook_prev, codebook_last, tuple_members,
                               tuple_offsets, n_tuple_groups, super_members, super_offsets, n_super_buckets, counters_out, workspace,
                               workspace_bytes, (hipStream_t)stream);
+}
+
+LCREC_API size_t lcrec_rq_audit_workspace(int64_t n, int e, const int *K, int L) { return rq_audit_workspace(n, e, K, L); }
+
+LCREC_API int lcrec_rq_audit(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L, const int64_t *idx,
+                             int64_t idx_stride, float *d_held_out, float *d_best_out, int *rank_out, int64_t *best_out,
+                             float *err_out, float *resid_out, uint32_t *flags_out, void *workspace, size_t workspace_bytes,
+                             void *stream)
+{
+    return rq_audit(z, n, e, codebooks, K, L, idx, idx_stride, d_held_out, d_best_out, rank_out, best_out, err_out, resid_out,
+                    flags_out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_bn_relu_forward(const float *t, int64_t n, int features, const float *gamma, const float *beta, float eps,

@@ -32,7 +32,7 @@ enum KernelId { K_LINEAR_128x128 = 0, K_LINEAR_128x64, K_LINEAR_128x32, K_RQ_ASS
                 K_VQ_DISTANCE, K_SINKHORN, K_SINKHORN_SMALL, K_APPLY_LEVEL, K_CODE_STATS, K_EMA_UPDATE, K_COLLISION,
                 K_LINEAR_PP, K_LINEAR_64x64, K_SINKHORN_SLAB, K_SINKHORN_TINY, K_BN_FWD, K_BN_BWD, K_RELU_BIAS_BWD, K_LOSS,
                 K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_FINISH, K_EXTEND, K_SPILL,
-                K_SPILL_KEEPERS, K_COUNT };
+                K_SPILL_KEEPERS, K_RQ_AUDIT, K_COUNT };
 extern const char *const kKernelNames[K_COUNT];
 bool trace_on();
 void trace_begin(int kernel, hipStream_t stream);
@@ -239,6 +239,10 @@ int spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const i
                        int e, const float *codebook_prev, const float *codebook_last, const int64_t *tuple_members,
                        const int64_t *tuple_offsets, int64_t n_tuples, const int64_t *super_members, const int64_t *super_offsets,
                        int64_t n_supers, int64_t *counters_out, void *workspace, size_t workspace_bytes, hipStream_t stream);
+size_t rq_audit_workspace(int64_t n, int e, const int *K, int L);
+int rq_audit(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L, const int64_t *idx, int64_t idx_stride,
+             float *d_held_out, float *d_best_out, int *rank_out, int64_t *best_out, float *err_out, float *resid_out,
+             uint32_t *flags_out, void *workspace, size_t workspace_bytes, hipStream_t stream);
 int ema_update(float *ema_count, float *ema_sum, float *codebook, const float *count, const float *sum, int K, int e,
                float decay, float alpha, float keep, float eps, const unsigned char *skip, hipStream_t stream);
 

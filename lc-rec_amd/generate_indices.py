@@ -23,6 +23,8 @@ Documented divergences from the reference script:
     their tuples byte for byte, and only the new items are indexed, around them (generate_extended);
   * --spill (off by default) follows either of the two: an item they leave colliding, because its bucket holds more items than the
     last level has codes, takes the next-nearest code one level up and the nearest free last-level code there (spill_collisions);
+  * --audit (off by default) goes BEYOND the reference as well: the tuples about to be written are walked through the quantiser again
+    and what the moves above cost -- ranks, distance regret, added quantisation error -- is reported (audit_indices.report_for);
   * it stores tokens in fixed-width numpy unicode arrays (:98-99) which silently truncate a
     replacement longer than anything seen in pass 1; integer tuples are kept here, and a warning is
     logged if a run ever hits that case (the reference's output would be corrupt there).
@@ -82,10 +84,11 @@ def build_model_from_args(args, in_dim):
 
 
 @torch.no_grad()
-def assign_all(model, data, chunk_rows=1 << 20, audit=None, want_prev=False):
+def assign_all(model, data, chunk_rows=1 << 20, audit=None, want_prev=False, latents=None):
     """Pass 1 (:77-95): int64 [N, L] hard indices plus the residual entering the last level.
     audit: optional dict; receives "neartie" (int32 [N], ops.NEARTIE_TAU) -- the near-tie flags of pass 1.
-    want_prev: a fourth value is returned, the residual entering level L-2 (L = 2: the latent; L = 1: None) -- spill_collisions'."""
+    want_prev: a fourth value is returned, the residual entering level L-2 (L = 2: the latent; L = 1: None) -- spill_collisions'.
+    latents: optional list; receives every chunk's latents (float32 [rows, e]) in order -- the index audit's (--audit)."""
     levels = list(model.rq.vq_layers)
     Ws, bs, scs, shs = model.encoder.folded()
     cbs = [q.embedding.weight.detach() for q in levels]
@@ -97,6 +100,8 @@ def assign_all(model, data, chunk_rows=1 << 20, audit=None, want_prev=False):
         idx, latent, _, _ = ops.encode_assign(x, Ws, bs, flat, ks, scs, shs, want_latent=True, audit=a,
                                               tie_tau=ops.NEARTIE_TAU)
         idx_parts.append(idx)
+        if latents is not None:
+            latents.append(latent)
         if a is not None:
             tie_parts.append(a["neartie"])
         if len(levels) > 1:
@@ -323,6 +328,17 @@ def _spill_and_log(model, idx, n_frozen, resid_prev, resid_last, ks, stats):
                     ks[-2], ks[-1], ks[-2] * ks[-1])
 
 
+def _audit_and_log(model, latents, greedy, neartie, held, stats, what="", first_item=0):
+    """--audit: the report of the tuples `held` about to be written (audit_indices.report_for, on pass 1's latents, greedy tuples and
+    near-tie flags of the same items) goes into stats["audit"]; its summary is logged."""
+    from . import audit_indices
+    flat, ks = ops.flatten_codebooks([q.embedding.weight.detach() for q in model.rq.vq_layers])
+    stats["audit"] = audit_indices.report_for(flat, ks, torch.cat(latents), greedy, neartie, held, first_item=first_item)
+    for line in audit_indices.summary(stats["audit"]):
+        log.info("--audit%s: %s", what, line)
+    audit_indices.warn_if_foreign(stats["audit"])
+
+
 def _refuse_one_level(args):
     if len(args.num_emb_list) < 2:
         raise ValueError("--spill moves an item one level above the last: this checkpoint's model has one level "
@@ -335,7 +351,7 @@ def _colliding(rows):
 
 
 def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_path=None, verbose=True, trust_checkpoint=False,
-                      spill=False):
+                      spill=False, audit=False):
     """--extend: the data file holds the whole catalogue, its first N0 rows are the items of `base_file` (keys "0" .. "N0-1") and
     rows N0 .. N-1 are new.  The output holds all N items; the first N0 entries carry exactly the base file's tuples (and, for a
     base written by this project or by the reference, the output's first len(base) - 1 bytes are the base file's without its
@@ -345,7 +361,8 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
     The Sinkhorn conflict rounds are NOT run here: they re-assign within a group of colliding items and know nothing of codes held
     outside it, so beside a frozen catalogue most of their work would be undone again.  The distance rule alone decides.
     --finish is ignored for the same reason.  N == N0 launches nothing and rewrites the base.
-    spill: the new items that extend_collisions leaves unresolved go through spill_collisions."""
+    spill: the new items that extend_collisions leaves unresolved go through spill_collisions.
+    audit: stats["audit"] is the index audit of the NEW rows' tuples (no latents exist for the frozen items); N == N0: no report."""
     ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
     args = ckpt["args"]
     if spill:
@@ -371,9 +388,10 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
     else:
         dev = torch.device(device)
         model = model.to(dev).eval()
-        audit = {}
-        idx_new, resid_new, ks, *prev = assign_all(model, data.to_device(dev, rows=(n0, n)), audit=audit, want_prev=spill)
-        stats["neartie_items"] = int((audit["neartie"] != 0).sum())
+        ties = {}
+        latents = [] if audit else None
+        idx_new, resid_new, ks, *prev = assign_all(model, data.to_device(dev, rows=(n0, n)), audit=ties, want_prev=spill, latents=latents)
+        stats["neartie_items"] = int((ties["neartie"] != 0).sum())
         base_dev = torch.from_numpy(base).to(dev)
         stats["base_colliding"] = n0 - ops.collision_groups(base_dev, ks, want_groups=False)["unique"] if n0 else 0
         idx = torch.cat([base_dev, idx_new])
@@ -390,6 +408,8 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
         if spill:
             _spill_and_log(model, idx, n0, prev[0], resid_new, ks, stats)
         _warn_if_reference_would_truncate(first_pass, idx)
+        if audit:
+            _audit_and_log(model, latents, idx_new, ties["neartie"], idx[n0:], stats, " (new items)", first_item=n0)
         after = ops.collision_groups(idx, ks, want_groups=False)
         stats["collision_rate"] = (n - after["unique"]) / n
         stats["max_conflicts"] = after["max_count"]
@@ -540,7 +560,7 @@ def sharded_assign(ctx, data, assign_fn, device):
 
 
 def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=True, ctx=None, trust_checkpoint=False,
-             recheck=False, finish="none", extend=None, spill=False):
+             recheck=False, finish="none", extend=None, spill=False, audit=False):
     """Whole flow of generate_indices.py:51-145.  Returns a dict of the statistics it prints.
     recheck: re-evaluate the near-tie items of pass 1 in the reference's CPU operation order (recheck_neartie).
     finish: "none" (the reference's bytes) or "nearest_free" (finish_collisions after the rounds; beyond the reference).
@@ -551,6 +571,11 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         (spill_collisions; beyond the reference).  Refused with ValueError before the checkpoint is opened: without one of those two
         passes, with `recheck` (the level L-2 residuals it patches are not kept) and under torchrun; and as soon as the checkpoint's
         arguments are read, before the data or the device are touched, for a one-level model.
+
+    audit: the tuples about to be written are walked through the quantiser again, from the latents and the greedy tuples of pass 1
+        (kept; the encoder does not run twice), and stats["audit"] says what the moves cost (audit_indices.build_report names its
+        keys).  With `extend` it covers the new rows only.  Refused with ValueError, as `spill` is, with `recheck` and under
+        torchrun.  Without it the returned dict and the file are exactly what they were.
 
     Under torchrun (ctx = dist.init_from_env()) pass 1 is item-sharded over the ranks and each conflict round's
     groups are sharded too (resolve_collisions); rank 0 writes the file."""
@@ -564,6 +589,12 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
                              "patches are not kept")
         if ctx.enabled:
             raise ValueError("--spill under torchrun is not supported: run it in a single process")
+    if audit:
+        if recheck:
+            raise ValueError("--audit with --recheck_neartie is not supported: the audit starts from the latents of pass 1, which the "
+                             "re-evaluation does not patch")
+        if ctx.enabled:
+            raise ValueError("--audit under torchrun is not supported: run it in a single process")
     if extend is not None:
         if recheck:
             raise ValueError("--extend with --recheck_neartie is not supported: the re-evaluation works on the reference's 64-row "
@@ -571,7 +602,7 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         if ctx.enabled:
             raise ValueError("--extend under torchrun is not supported: run it in a single process")
         return generate_extended(ckpt_path, output_file, extend, device=device, data_path=data_path, verbose=verbose,
-                                 trust_checkpoint=trust_checkpoint, spill=spill)
+                                 trust_checkpoint=trust_checkpoint, spill=spill, audit=audit)
     lead = ctx.rank == 0
     verbose = verbose and lead
     if finish not in FINISH_MODES:
@@ -586,11 +617,12 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
     model = model.to(torch.device(device)).eval()
     if verbose:
         print(model)
-    audit = {}
+    ties = {}
     prev = []                                              # spill: the residual entering level L-2 (one process: nothing to gather)
+    latents = [] if audit else None                        # audit: pass 1's latents (one process too)
 
     def assign(x):
-        out = assign_all(model, x, audit=audit, want_prev=spill)
+        out = assign_all(model, x, audit=ties, want_prev=spill, latents=latents)
         prev.extend(out[3:])
         return out[:3]
 
@@ -598,10 +630,10 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
     first_pass = idx.clone()
     # near-tie audit of pass 1: items whose two best codes at some level are closer than the rounding noise of
     # vq.py:71-73 -- the only ones a CPU run of the reference could index differently (ops.NEARTIE_TAU)
-    neartie_items = int(ctx.sum_int(int((audit["neartie"] != 0).sum())))
+    neartie_items = int(ctx.sum_int(int((ties["neartie"] != 0).sum())))
     rechecked = (0, 0)
     if recheck:
-        flags = ctx.gather_rows(audit["neartie"]) if ctx.enabled else audit["neartie"]
+        flags = ctx.gather_rows(ties["neartie"]) if ctx.enabled else ties["neartie"]
         if lead:
             rechecked = recheck_neartie(ckpt["state_dict"], args, data, idx, resid_last, flags)
         if ctx.enabled:                                    # rank 0's host decides (ranks on other CPUs could round differently)
@@ -640,6 +672,8 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
              "finish": finish, "finish_moved": finished["moved"], "finish_unresolved": finished["unresolved"]}
     if spill:
         stats.update(spilled)
+    if audit:
+        _audit_and_log(model, latents, first_pass, ties["neartie"], idx, stats)
     if lead:
         log.info("near-tie items in pass 1: %d of %d (top-2 code gap <= %.3g x distance magnitude at some level); only "
                  "these could receive a different tuple from a CPU run of the reference", neartie_items, n, ops.NEARTIE_TAU)
@@ -681,6 +715,11 @@ def parse_args(argv=None):
                          "items than the last level has codes, takes the next-nearest code one level up and the nearest free "
                          "last-level code there (goes beyond the reference; the last two tokens of those items change).  Not with "
                          "--recheck_neartie or torchrun; needs at least two levels")
+    ap.add_argument("--audit", action="store_true",
+                    help="walk the tuples about to be written through the quantiser again and log what the conflict rounds and the "
+                         "passes above cost: how many items hold a code that is not their nearest, at which level and rank, and the "
+                         "quantisation error that added (audit_indices.py does the same for an existing file).  With --extend the "
+                         "new rows only: there are no latents for the frozen items.  Not with --recheck_neartie or torchrun")
     return ap.parse_args(argv)
 
 
@@ -692,7 +731,7 @@ def main(argv=None):
     try:
         return generate(a.ckpt_path, out, device=a.device, data_path=a.data_path, ctx=ctx,
                         trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish, extend=a.extend,
-                        spill=a.spill)
+                        spill=a.spill, audit=a.audit)
     finally:
         ldist.shutdown(ctx)
 

@@ -1086,6 +1086,72 @@ def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, 
     return moved, unresolved
 
 
+def rq_audit(z, codebooks_flat, ks, idx, want_best=False, want_resid=False):
+    """The index audit (lcrec_rq_audit of include/lcrec.h, which states the rule): the GIVEN tuples `idx` walked through the
+    residual quantiser from the latents z.  Per item and level: the distance of the held code, the best distance and the held
+    code's rank in the level's distance order (0 = the code rq_assign picks on that residual); the residual follows the held code.
+
+    z float32 [n, e]; codebooks_flat / ks as rq_assign; idx int64 [n, L], contiguous or a column block of a wider contiguous
+    matrix (matrix[:, c:c + L]); it is only read.  Returns a dict of device tensors: "d_held", "d_best" float32 [n, L], "rank"
+    int32 [n, L], "err" float32 [n] (the squared norm of the residual left after the last level), "flags" int32 [n] (bit l: the
+    code of level l was outside [0, ks[l]) and was clamped), and on request "best" int64 [n, L] and "resid" float32 [n, e]."""
+    z = _dev(z, "z")
+    if z.dim() != 2:
+        raise _lib.LcrecError(f"z must be [n, e], got {tuple(z.shape)}")
+    n, e = z.shape
+    L = len(ks)
+    dev = z.device
+    out = {"d_held": torch.empty((n, L), dtype=torch.float32, device=dev), "d_best": torch.empty((n, L), dtype=torch.float32, device=dev),
+           "rank": torch.empty((n, L), dtype=torch.int32, device=dev), "err": torch.empty(n, dtype=torch.float32, device=dev),
+           "flags": torch.empty(n, dtype=torch.int32, device=dev)}
+    if want_best:
+        out["best"] = torch.empty((n, L), dtype=torch.int64, device=dev)
+    if want_resid:
+        out["resid"] = torch.empty((n, e), dtype=torch.float32, device=dev)
+    rq_audit_into(z, codebooks_flat, ks, idx, out)
+    return out
+
+
+def rq_audit_into(z, codebooks_flat, ks, idx, out):
+    """lcrec_rq_audit into buffers the caller owns, as rq_assign_into does for lcrec_rq_assign: `out` holds "d_held", "d_best"
+    float32, "rank" int32, "err" float32, "flags" int32 and may hold "best" int64 and "resid" float32 (one that is missing is passed
+    as NULL), each contiguous on z's device with at least the elements the call writes -- it may be LARGER, so that a test can look
+    at what lies past the end.  Nothing is returned."""
+    lib = _lib.load()
+    z = _dev(z, "z")
+    cb = _dev(codebooks_flat, "codebooks")
+    if z.dim() != 2:
+        raise _lib.LcrecError(f"z must be [n, e], got {tuple(z.shape)}")
+    n, e = z.shape
+    L = len(ks)
+    dev = z.device
+    if cb.numel() != sum(int(k) for k in ks) * e:
+        raise _lib.LcrecError(f"codebooks hold {cb.numel()} floats, {list(ks)} x {e} need {sum(int(k) for k in ks) * e}")
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 2
+            and tuple(idx.shape) == (n, L) and (n <= 1 or idx.stride(0) >= L) and (L == 1 or idx.stride(1) == 1)):
+        raise _lib.LcrecError(f"idx must be an int64 [{n}, {L}] tensor on z's device, contiguous or a column block of a wider "
+                              "contiguous matrix")
+    idx_stride = int(idx.stride(0)) if n > 1 else L
+    sizes = {"d_held": (torch.float32, n * L), "d_best": (torch.float32, n * L), "rank": (torch.int32, n * L),
+             "err": (torch.float32, n), "flags": (torch.int32, n), "best": (torch.int64, n * L), "resid": (torch.float32, n * e)}
+    if set(sizes) - {"best", "resid"} - set(out) or set(out) - set(sizes):
+        raise _lib.LcrecError(f"out must hold d_held, d_best, rank, err, flags and may hold best, resid; got {sorted(out)}")
+    for name, t in out.items():
+        dtype, need = sizes[name]
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()
+                and t.numel() >= need):
+            raise _lib.LcrecError(f"out[{name!r}] must be a contiguous {dtype} tensor on z's device with at least {need} elements")
+    if n == 0:                                             # (an empty tensor has no address to pass)
+        return
+    karr = _ints(ks)
+    with _on(dev):
+        ws = _workspace(lib.lcrec_rq_audit_workspace(n, e, karr, L), dev)
+        rc = lib.lcrec_rq_audit(_ptr(z), n, e, _ptr(cb), karr, L, _ptr(idx), idx_stride, _ptr(out["d_held"]), _ptr(out["d_best"]),
+                                _ptr(out["rank"]), _ptr(out.get("best")), _ptr(out["err"]), _ptr(out.get("resid")),
+                                _ptr(out["flags"]), _ptr(ws), ws.numel(), _stream_ptr())
+    _lib.check(rc, "lcrec_rq_audit")
+
+
 def index_json_text(idx_rows, first_item=0):
     """bytes of the `.index.json` entries of items first_item.. for a HOST int64 [n, L] array
     (generate_indices.py:83-92,138-145; see lcrec_index_json_format in include/lcrec.h)."""

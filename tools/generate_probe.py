@@ -5,6 +5,7 @@ pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing
     python tools/generate_probe.py [--items 1000000] [--in_dim 768] [--levels 4] [--codes 256]
     python tools/generate_probe.py --extend_new 10000,100000   # then --extend: the finished tuples as base, that many new items
     python tools/generate_probe.py --spill [--extend_new 100000]  # then --spill over what the finishing pass (and --extend) leave
+    python tools/generate_probe.py --audit                     # then the index audit of the tuples about to be written (--audit)
 """
 import argparse
 import os
@@ -16,7 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lcrec_amd  # noqa: E402
-from lcrec_amd import generate_indices as gen, ops  # noqa: E402
+from lcrec_amd import audit_indices, generate_indices as gen, ops  # noqa: E402
 
 
 def spill_line(what, done, t, tr, after):
@@ -72,6 +73,9 @@ def main():
                     "with the run's finished tuples as the base file")
     ap.add_argument("--spill", action="store_true", help="time --spill behind the finishing pass (and behind each --extend run); the "
                     "base file of the --extend runs is then the spilled one")
+    ap.add_argument("--audit", action="store_true", help="time the index audit (generate_indices --audit) of the finished tuples: one "
+                    "warm-up pass, then --audit_runs timed ones, the median reported, with the run's pass 1 and rq_assign as yardsticks")
+    ap.add_argument("--audit_runs", type=int, default=5)
     a = ap.parse_args()
     dev = "cuda:0"
     torch.manual_seed(2024)
@@ -171,6 +175,39 @@ def main():
         ops.trace_enable(False)
         spill_lines = [spill_line("spill", sp, t_spill, strace, ops.collision_groups(idx, ks, want_groups=False)),
                        f"  yardsticks of this run: conflict rounds {t_rounds * 1e3:.1f} ms, finish nearest_free {t_finish * 1e3:.2f} ms"]
+    audit_lines = []
+    if a.audit:
+        # what generate(audit=True) does behind the passes above: pass 1's latents, greedy tuples and near-tie flags are kept, the
+        # tuples about to be written are walked through the quantiser (two rq_audit calls per chunk) and the report is formed on the host
+        ties, lat = {}, []
+        ops.trace_enable(True)
+        (greedy, _, _), t_keep = timed(lambda: gen.assign_all(model, x, audit=ties, latents=lat))
+        tr_keep = ops.trace_collect()
+        ops.trace_enable(False)
+        flat, _ = ops.flatten_codebooks([q.embedding.weight.detach() for q in model.rq.vq_layers])
+        latent = torch.cat(lat)
+        del lat
+        report = lambda: audit_indices.report_for(flat, ks, latent, greedy, ties["neartie"], idx)
+        report()                                           # warm-up
+        walls, kernels, calls = [], [], 0
+        for _ in range(max(a.audit_runs, 1)):
+            ops.trace_enable(True)
+            rep, t_audit = timed(report)
+            tr = ops.trace_collect()
+            ops.trace_enable(False)
+            walls.append(t_audit)
+            calls = tr["rq_audit"][0]
+            kernels.append(tr["rq_audit"][1] / calls)
+        k = lambda name: tr_keep.get(name, (0, 0.0))
+        per_call = float(np.median(kernels))
+        audit_lines = [f"audit (report_for)       {np.median(walls) * 1e3:9.1f} ms   median of {len(walls)} runs after one warm-up (min "
+                       f"{min(walls) * 1e3:.1f}, max {max(walls) * 1e3:.1f}); rq_audit {per_call:.2f} ms per call by the trace brackets, "
+                       f"{calls} calls per run",
+                       f"  yardsticks of this run: pass 1 keeping the latents {t_keep * 1e3:.1f} ms (best pass 1 above {t_pass1 * 1e3:.1f} ms), "
+                       f"rq_assign {k('rq_assign')[1]:.2f} ms/{k('rq_assign')[0]} by the trace brackets"
+                       + ("   ONE rq_audit CALL COSTS MORE THAN THE WHOLE PASS 1" if per_call > t_pass1 * 1e3 else "")]
+        audit_lines += ["  " + line for line in audit_indices.summary(rep)]
+        del latent
     _, t_json = timed(lambda: gen.dump_index_json(idx, a.out))
     size = os.path.getsize(a.out)
     extend_lines = []
@@ -198,7 +235,7 @@ def main():
           f"largest {fin['largest_bucket']} items, moved {fin['moved']}, unresolved {fin['unresolved']}")
     print("  kernels: " + ", ".join(f"{k} {v[1]:.2f} ms/{v[0]}" for k, v in sorted(ftrace.items(), key=lambda kv: -kv[1][1])))
     print(f"  collision rate {final['collision_rate']:.6f} -> {finished['collision_rate']:.6f}")
-    for line in spill_lines:
+    for line in spill_lines + audit_lines:
         print(line)
     print(f".index.json ({size / 1e6:.0f} MB)     {t_json * 1e3:9.1f} ms   {a.items / t_json / 1e6:7.2f} M items/s (D2H + text + write)")
     for line in extend_lines:

@@ -764,6 +764,56 @@ int lcrec_rq_audit(const float *z, int64_t n, int e, const float *codebooks, con
                    int64_t *best_out, float *err_out, float *resid_out, uint32_t *flags_out,
                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* Decode pass: GIVEN tuples back to embeddings, and the reconstruction error of every item.  lcrec_encode_assign goes from an
+ * embedding to a tuple and lcrec_rq_audit prices a tuple in latent space; this entry goes the way back -- codes, their sum, the
+ * decoder MLP (RQVAE.forward's `out = self.decoder(x_q)`, index/models/rqvae.py:57-66, which the reference runs only inside a
+ * training step) -- and compares the result with the item's embedding, which is the quantity the training log prints and a
+ * checkpoint is selected on (rqvae.py:74-85).  Beyond the reference, whose index/ stage never turns a tuple back into a vector.
+ *
+ * The rule.  For item i with held tuple h_i[0 .. L):
+ *   1. Held code.  h = h_i[l] brought into [0, K[l]) by the rule of lcrec_rq_apply_level, decided on the int64 value: below 0
+ *      counts as 0, K[l] and above as K[l] - 1.  If the code had to be clamped, bit l of flags_out[i] is set.
+ *   2. Quantised latent.  q = C_0[h_0], then for l = 1 .. L-1  q = q + C_l[h_l]: one fp32 add per element, levels ascending, and a
+ *      plain copy for L == 1.  This is the sum of the CODES.  It is NOT the straight-through sum that lcrec_rq_assign writes to
+ *      xq_out, which adds r + (c - r) per level (index/models/vq.py:95): the two differ by rounding only -- by at most
+ *      L * 2^-21 * the largest magnitude among residuals, code rows and sums -- but they are not bit-equal: on the greedy tuples of
+ *      the test shapes about a third of the elements (30 to 39 %) differ in the last bits.
+ *   3. Decoder.  y = layer_{n_layers-1}( ... relu(layer_0(q))): each layer exactly lcrec_linear_forward -- folded eval BatchNorm
+ *      where given, ReLU after every layer but the last, the same fp32 fma chains, bit for bit.
+ *   4. Error, only when x is given.  d_j = y_j - x_j, one fp32 subtraction.  l1 == 0: err = the fp32 fma chain fma(d_j, d_j, err)
+ *      over j ascending from 0, starting at 0.  l1 != 0: err = err + |d_j|, one fp32 add each, j ascending.  One chain per row, so
+ *      the result does not depend on any tiling.  The mean of err over all items and columns is the reconstruction loss of
+ *      lcrec_recon_loss_grad (which sums in fp64 in another order).
+ *
+ *   idx         device int64, read only: item i's held code of level l at idx[i*idx_stride + l]; idx_stride >= L, 0 = L
+ *   codebooks, K  as lcrec_rq_assign; 1 <= L <= LCREC_MAX_LEVELS.  Nothing is staged in LDS, so any K[l] >= 1 is admitted
+ *   dims        host [n_layers+1]: e, hidden sizes ..., the embedding width; dims[0] = e must be 16, 32 or 64
+ *   W, b, bn_scale, bn_shift   as lcrec_encode_assign, for the DECODER's layers (b may hold NULL entries: no bias)
+ *   xq_out      device [n][e] or NULL: q
+ *   out         device [n][dims[n_layers]] or NULL: y.  When it is NULL the last layer writes into the workspace
+ *   x           device [n][dims[n_layers]] and err_out device [n]: given together, or both NULL
+ *   flags_out   device [n] uint32, or NULL
+ * At least one of xq_out, out, err_out must be given; with xq_out alone no layer runs and no workspace is needed.  The float
+ * arrays are 16-byte aligned, idx 8-byte, flags_out 4-byte.
+ * Items are walked in chunks of lcrec_decode_tuples_chunk_rows() rows.  One pure host function decides the walk and the layout
+ * of the workspace (lcrec_debug_decode_tuples_plan, below, reports it): two activation buffers of chunk_rows x the widest layer
+ * output -- the last layer's included when want_out == 0 -- and a slab of chunk_rows x e for q, used when xq_out is NULL.  Per
+ * chunk, on `stream` only (no context, no pipelines): the gather, the layers, the error kernel.
+ * Every layer is validated before the first launch: a width lcrec_linear_forward would refuse is refused here with the same code
+ * and a text that names the layer, so no call launches half a pass.  The other argument errors are LCREC_EINVAL / LCREC_EWORKSPACE
+ * with a text naming the argument, before the device is touched.  n == 0: no launch.  No allocation, no host synchronisation,
+ * capturable.  The workspace may hold anything.  Every requested output element of rows [0, n) is written by every call.
+ * Traced as "rq_decode_gather" and "recon_row_error", one bracket per launch (one launch of each per chunk), beside the layers'
+ * own labels.  lcrec_decode_tuples_workspace returns 0 for arguments lcrec_decode_tuples refuses. */
+size_t lcrec_decode_tuples_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out);
+/* rows per chunk of the walk described above (a build constant; results do not depend on it) */
+int64_t lcrec_decode_tuples_chunk_rows(void);
+int lcrec_decode_tuples(const int64_t *idx, int64_t idx_stride, int64_t n, const float *codebooks, const int *K, int L,
+                        const int *dims, int n_layers, const float *const *W, const float *const *b,
+                        const float *const *bn_scale, const float *const *bn_shift,
+                        float *xq_out, float *out, const float *x, int l1, float *err_out, uint32_t *flags_out,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* Text of the `.index.json` entries for a run of items (host-side; no device work).  Replaces the
  * per-item Python of index/generate_indices.py:83-92 (token strings "<a_{i}>", "<b_{j}>", ...) and the
  * json.dump of :138-145, whose default separators (", " and ": ") every consumer relies on
@@ -970,6 +1020,41 @@ int lcrec_debug_encode_assign(const float *x, int64_t n, const int *dims, int n_
                               float *latent_out, float *xq_out, double *sse_out,
                               float *margin_out, uint32_t *neartie_out, float tie_tau,
                               void *workspace, size_t workspace_bytes, lcrec_context *ctx, void *stream, int64_t chunk_rows);
+
+/* lcrec_decode_tuples walks its n rows in chunks; one pure host function decides the walk and the layout of the workspace, and
+ * the workspace queries, the launch code and the export below all go through it:
+ *   - chunk c covers rows c * chunk_rows .. and every chunk but the last has chunk_rows rows (the last: last_chunk_rows);
+ *   - the gather writes the chunk's q to rows c * chunk_rows .. of xq_out or, when that is NULL, to the slab at q_offset;
+ *   - layer l of the chunk writes the activation buffer at act_offset[l & 1], each act_bytes = chunk_rows x `widest` floats rounded
+ *     up to 256 B, `widest` being the widest output of the layers that write there: every layer but the last, and the last one
+ *     too when want_out == 0; with want_out != 0 the last layer writes the chunk's rows of `out`;
+ *   - the error kernel reads the last layer's output where it was written.
+ * The q slab is part of the workspace whether xq_out is given or not, so the size depends on the shapes, want_out and the chunk
+ * size alone.  chunk_rows: 0 = the built-in lcrec_decode_tuples_chunk_rows(); any positive value is admitted (results do not
+ * depend on it); a batch shorter than a chunk is one chunk of n rows. */
+typedef struct {
+    int64_t n;                /* rows of the call */
+    int64_t chunk_rows;       /* the chunk size in effect: min(asked for, max(n, 1)) */
+    int64_t n_chunks;         /* ceil(n / chunk_rows) */
+    int64_t last_chunk_rows;  /* rows of the last chunk (0 for n == 0) */
+    int widest;               /* floats per row of an activation buffer (0: no layer writes there) */
+    int64_t act_bytes;        /* one activation buffer */
+    int64_t act_offset[2];    /* byte offsets into the workspace */
+    int64_t q_offset, q_bytes;   /* the slab for [chunk_rows][e] quantised latents (used when xq_out is NULL) */
+    int64_t total_bytes;      /* = lcrec_decode_tuples_workspace */
+} lcrec_decode_plan;
+/* Host only: nothing is launched, no device is needed.  Returns LCREC_OK or the code lcrec_decode_tuples refuses the shapes with. */
+int lcrec_debug_decode_tuples_plan(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out, int64_t chunk_rows,
+                                   lcrec_decode_plan *plan_out);
+/* lcrec_decode_tuples_workspace for a chunk size (0 for refused arguments, chunk_rows < 0 among them). */
+size_t lcrec_debug_decode_tuples_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out,
+                                           int64_t chunk_rows);
+/* lcrec_decode_tuples with the chunk size as an argument: the same launch code, plan and kernels. */
+int lcrec_debug_decode_tuples(const int64_t *idx, int64_t idx_stride, int64_t n, const float *codebooks, const int *K, int L,
+                              const int *dims, int n_layers, const float *const *W, const float *const *b,
+                              const float *const *bn_scale, const float *const *bn_shift,
+                              float *xq_out, float *out, const float *x, int l1, float *err_out, uint32_t *flags_out,
+                              void *workspace, size_t workspace_bytes, void *stream, int64_t chunk_rows);
 
 /* The BatchNorm strip calls pick a kernel form by shape and alignment; lcrec_debug_bn_plan reports it.  Host only: nothing is
  * launched.  call: LCREC_BN_*; aligned: whether every pointer the call would be given sits on 16 bytes; 1 <= n <= 2^20. */

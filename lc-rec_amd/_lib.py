@@ -130,6 +130,7 @@ SinkhornGroupRoute = STRUCTS["lcrec_sinkhorn_group_route"]
 RqPlan = STRUCTS["lcrec_rq_plan"]
 EncodePlan = STRUCTS["lcrec_encode_plan"]
 EncodeChunk = STRUCTS["lcrec_encode_chunk"]
+DecodePlan = STRUCTS["lcrec_decode_plan"]
 BnPlan = STRUCTS["lcrec_bn_plan"]
 StepTailPlan = STRUCTS["lcrec_step_tail_plan"]
 OptimPlan = STRUCTS["lcrec_optim_plan"]

@@ -150,10 +150,11 @@ def report_for(flat, ks, latent, greedy, neartie, held, first_item=0):
 
 
 @torch.no_grad()
-def audit(ckpt_path, index_file, device="cuda:0", data_path=None, trust_checkpoint=False):
+def audit(ckpt_path, index_file, device="cuda:0", data_path=None, trust_checkpoint=False, recon=False):
     """The report dict (build_report names its keys) of `index_file` against the checkpoint and its data file.  ValueError: under
     torchrun; a file the reader refuses (a level count or a code that does not go with the checkpoint); a file whose item count
-    is not the data's row count."""
+    is not the data's row count.  recon: the report also holds, under the key "recon", what the tuples cost in reconstruction loss
+    (decode_indices.recon_for: the file's and the greedy tuples through the decoder, against the embeddings)."""
     _refuse_torchrun()
     ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
     args = ckpt["args"]
@@ -187,6 +188,9 @@ def audit(ckpt_path, index_file, device="cuda:0", data_path=None, trust_checkpoi
     found = ops.collision_groups(held, ks, want_groups=False) if n else {"unique": 0, "max_count": 0}
     rep = build_report(per, ks, held_host, greedy_host, neartie, found["unique"], found["max_count"])
     warn_if_foreign(rep)
+    if recon:
+        from . import decode_indices
+        rep["recon"] = decode_indices.recon_for(model, data, held_host, dev)
     return rep
 
 
@@ -197,6 +201,8 @@ def parse_args(argv=None):
     ap.add_argument("--data_path", type=str, default=None, help="override the data path stored in the checkpoint")
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--report", type=str, default=None, metavar="OUT.json", help="write the report as JSON")
+    ap.add_argument("--recon", action="store_true",
+                    help="also report what the tuples cost in reconstruction loss (the decode pass), under the key `recon`")
     ap.add_argument("--trust_checkpoint", action="store_true",
                     help="load the checkpoint with the unrestricted unpickler (executes code from the file)")
     return ap.parse_args(argv)
@@ -204,9 +210,13 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    rep = audit(a.ckpt_path, a.index_file, device=a.device, data_path=a.data_path, trust_checkpoint=a.trust_checkpoint)
+    rep = audit(a.ckpt_path, a.index_file, device=a.device, data_path=a.data_path, trust_checkpoint=a.trust_checkpoint, recon=a.recon)
     for line in summary(rep):
         print(line)
+    if a.recon:
+        from . import decode_indices
+        for line in decode_indices.summary(rep["recon"]):
+            print(line)
     if a.report:
         os.makedirs(os.path.dirname(os.path.abspath(a.report)), exist_ok=True)
         with open(a.report, "w") as fp:

@@ -29,7 +29,8 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "sinkhorn_tiny", "bn_relu_forward", "bn_relu_backward", "relu_bias_backward",
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
                                            "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free",
-                                           "spill_nearest_free", "spill_keepers", "rq_audit"};
+                                           "spill_nearest_free", "spill_keepers", "rq_audit", "rq_decode_gather",
+                                           "recon_row_error"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -107,6 +108,64 @@ static lcrec_encode_chunk enc_chunk(const lcrec_encode_plan &p, int64_t c)
     k.pipeline = (int)(c % p.pipelines);
     k.first_act = 2 * k.pipeline;
     return k;
+}
+
+// Items per pass of the decode chain (lcrec_decode_tuples): the encode pass's value -- the decoder's layers are the encoder's
+// mirrored, so the same reasoning bounds the activation scratch and keeps every GEMM launch >> 256 tiles.  Not measured for this
+// pass on its own.  Results do not depend on it (every output is one chain per element or per row).
+#ifndef LCREC_DEC_CHUNK
+#define LCREC_DEC_CHUNK 524288
+#endif
+constexpr int64_t DEC_CHUNK = LCREC_DEC_CHUNK;
+
+// ---- the decode pass as a pure function of (n, dims, K, L, want_out, chunk_rows): every check that needs shapes alone, how the
+// rows are cut into chunks and where everything lies in the workspace (include/lcrec.h, lcrec_decode_plan).  lcrec_decode_tuples /
+// lcrec_debug_decode_tuples launch by dec_plan(), the workspace queries return its total and lcrec_debug_decode_tuples_plan
+// reports it; none restates the other.  chunk_rows: 0 = DEC_CHUNK.
+static int dec_plan(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out, int64_t chunk_rows,
+                    lcrec_decode_plan *o)
+{
+    const char *who = "decode_tuples";
+    if (!K) return fail(LCREC_EINVAL, "%s: K is NULL", who);
+    if (!dims) return fail(LCREC_EINVAL, "%s: dims is NULL", who);
+    if (L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "%s: L=%d (1 .. %d)", who, L, LCREC_MAX_LEVELS);
+    if (n_layers < 1 || n_layers > LCREC_MAX_LAYERS)
+        return fail(LCREC_EINVAL, "%s: n_layers=%d (1 .. %d)", who, n_layers, LCREC_MAX_LAYERS);
+    if (n < 0) return fail(LCREC_EINVAL, "%s: n=%lld", who, (long long)n);
+    if (chunk_rows < 0) return fail(LCREC_EINVAL, "%s: chunk_rows=%lld < 0", who, (long long)chunk_rows);
+    const int e = dims[0];
+    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EINVAL, "%s: e_dim=%d (dims[0]; supported: 16, 32, 64)", who, e);
+    for (int l = 0; l < L; ++l)
+        if (K[l] < 1) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, l, K[l]);
+    for (int l = 1; l <= n_layers; ++l)
+        if (dims[l] < 1) return fail(LCREC_EINVAL, "%s: layer %d: dims[%d]=%d", who, l - 1, l, dims[l]);
+    const int64_t rows = n > 0 ? n : 1, want = chunk_rows ? chunk_rows : DEC_CHUNK;
+    o->n = n;
+    o->chunk_rows = rows < want ? rows : want;
+    o->n_chunks = (n + o->chunk_rows - 1) / o->chunk_rows;
+    o->last_chunk_rows = n > 0 ? n - (o->n_chunks - 1) * o->chunk_rows : 0;
+    // every layer, at the row counts it will be launched with, through the function lcrec_linear_forward launches by
+    for (int l = 0; l < n_layers; ++l) {
+        const int64_t counts[2] = {o->chunk_rows, o->last_chunk_rows ? o->last_chunk_rows : o->chunk_rows};
+        for (int64_t m : counts) {
+            lcrec_gemm_launch steps[4];
+            const int rc = lcrec_debug_linear_forward_plan(m, dims[l], dims[l + 1], 256, steps, 4);
+            if (rc < 0)
+                return fail(rc, "%s: layer %d (in_dim=%d, out_dim=%d, %lld rows): lcrec_linear_forward refuses it%s", who, l, dims[l],
+                            dims[l + 1], (long long)m, dims[l] % 8 ? " (in_dim is not a multiple of 8)" : "");
+        }
+    }
+    int widest = 0;
+    for (int l = 1; l <= n_layers; ++l)
+        if ((l < n_layers || !want_out) && dims[l] > widest) widest = dims[l];
+    o->widest = widest;
+    o->act_bytes = (int64_t)align_up((size_t)o->chunk_rows * widest * sizeof(float), 256);
+    o->act_offset[0] = 0;
+    o->act_offset[1] = o->act_bytes;
+    o->q_offset = 2 * o->act_bytes;
+    o->q_bytes = (int64_t)align_up((size_t)o->chunk_rows * e * sizeof(float), 256);
+    o->total_bytes = o->q_offset + o->q_bytes;
+    return LCREC_OK;
 }
 
 int check_context(const lcrec_context *ctx, const char *who)
@@ -348,6 +407,117 @@ LCREC_API int lcrec_debug_encode_assign(const float *x, int64_t n, const int *di
 {
     return encode_assign(x, n, dims, n_layers, W, b, bn_scale, bn_shift, codebooks, K, L, idx_out, latent_out, xq_out, sse_out,
                          margin_out, neartie_out, tie_tau, workspace, workspace_bytes, ctx, (hipStream_t)stream, chunk_rows);
+}
+
+static size_t decode_tuples_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out, int64_t chunk_rows)
+{
+    lcrec_decode_plan p;
+    return dec_plan(n, dims, n_layers, K, L, want_out, chunk_rows, &p) ? 0 : (size_t)p.total_bytes;
+}
+
+LCREC_API size_t lcrec_decode_tuples_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out)
+{
+    return decode_tuples_workspace(n, dims, n_layers, K, L, want_out, 0);
+}
+
+LCREC_API size_t lcrec_debug_decode_tuples_workspace(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out,
+                                                     int64_t chunk_rows)
+{
+    return decode_tuples_workspace(n, dims, n_layers, K, L, want_out, chunk_rows);
+}
+
+LCREC_API int64_t lcrec_decode_tuples_chunk_rows(void) { return DEC_CHUNK; }
+
+LCREC_API int lcrec_debug_decode_tuples_plan(int64_t n, const int *dims, int n_layers, const int *K, int L, int want_out,
+                                             int64_t chunk_rows, lcrec_decode_plan *plan_out)
+{
+    if (!plan_out) return fail(LCREC_EINVAL, "decode_tuples_plan: NULL plan_out");
+    lcrec_decode_plan p;
+    if (int rc = dec_plan(n, dims, n_layers, K, L, want_out, chunk_rows, &p)) return rc;
+    *plan_out = p;
+    return LCREC_OK;
+}
+
+// lcrec_decode_tuples (chunk_rows = 0) and lcrec_debug_decode_tuples: every check, then per chunk the gather, the layers and the
+// error kernel, all on `s`
+static int decode_tuples(const int64_t *idx, int64_t idx_stride, int64_t n, const float *codebooks, const int *K, int L,
+                         const int *dims, int n_layers, const float *const *W, const float *const *b, const float *const *bn_scale,
+                         const float *const *bn_shift, float *xq_out, float *out, const float *x, int l1, float *err_out,
+                         uint32_t *flags_out, void *workspace, size_t workspace_bytes, hipStream_t s, int64_t chunk_rows)
+{
+    const char *who = "decode_tuples";
+    lcrec_decode_plan p;
+    if (int rc = dec_plan(n, dims, n_layers, K, L, out != nullptr, chunk_rows, &p)) return rc;
+    if (idx_stride == 0) idx_stride = L;
+    if (idx_stride < L) return fail(LCREC_EINVAL, "%s: idx_stride=%lld < L=%d", who, (long long)idx_stride, L);
+    if (!idx) return fail(LCREC_EINVAL, "%s: idx is NULL", who);
+    if (!codebooks) return fail(LCREC_EINVAL, "%s: codebooks is NULL", who);
+    if (!xq_out && !out && !err_out) return fail(LCREC_EINVAL, "%s: no output asked for (xq_out, out and err_out are all NULL)", who);
+    if ((x == nullptr) != (err_out == nullptr)) return fail(LCREC_EINVAL, "%s: x and err_out are given together, or both NULL", who);
+    const bool layers = out || err_out;
+    if (layers) {
+        if (!W) return fail(LCREC_EINVAL, "%s: W is NULL", who);
+        if (!b) return fail(LCREC_EINVAL, "%s: b is NULL", who);
+        for (int l = 0; l < n_layers; ++l) {
+            if (!W[l]) return fail(LCREC_EINVAL, "%s: layer %d: W[%d] is NULL", who, l, l);
+            const float *sc = bn_scale ? bn_scale[l] : nullptr, *sh = bn_shift ? bn_shift[l] : nullptr;
+            if ((sc == nullptr) != (sh == nullptr))
+                return fail(LCREC_EINVAL, "%s: layer %d: bn_scale and bn_shift must both be given or both NULL", who, l);
+            if ((uintptr_t)W[l] & 15) return fail(LCREC_EINVAL, "%s: layer %d: W[%d] must be 16-byte aligned", who, l, l);
+        }
+    }
+    if (((uintptr_t)codebooks | (uintptr_t)xq_out | (uintptr_t)out | (uintptr_t)x | (uintptr_t)err_out | (uintptr_t)workspace) & 15)
+        return fail(LCREC_EINVAL, "%s: codebooks, xq_out, out, x, err_out and workspace must be 16-byte aligned", who);
+    if ((uintptr_t)idx & 7) return fail(LCREC_EINVAL, "%s: idx must be 8-byte aligned", who);
+    if ((uintptr_t)flags_out & 3) return fail(LCREC_EINVAL, "%s: flags_out must be 4-byte aligned", who);
+    // with xq_out alone nothing of the workspace is used: the gather writes the caller's rows and no layer runs
+    const size_t need = layers || !xq_out ? (size_t)p.total_bytes : 0;
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(LCREC_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (lcrec_decode_tuples_workspace)", who,
+                    workspace ? workspace_bytes : (size_t)0, need);
+    if (n == 0) return LCREC_OK;
+
+    char *ws = reinterpret_cast<char *>(workspace);
+    const int e = dims[0], w = dims[n_layers];
+    for (int64_t c = 0; c < p.n_chunks; ++c) {
+        const int64_t row0 = c * p.chunk_rows, rows = c == p.n_chunks - 1 ? p.last_chunk_rows : p.chunk_rows;
+        float *q = xq_out ? xq_out + row0 * e : reinterpret_cast<float *>(ws + p.q_offset);
+        if (int rc = rq_decode_gather(idx + row0 * idx_stride, idx_stride, rows, e, codebooks, K, L, q, flags_out ? flags_out + row0 : nullptr, s))
+            return rc;
+        if (!layers) continue;
+        const float *src = q;
+        for (int l = 0; l < n_layers; ++l) {
+            const bool last = l == n_layers - 1;
+            float *dst = last && out ? out + row0 * w : reinterpret_cast<float *>(ws + p.act_offset[l & 1]);
+            if (int rc = linear_forward(src, rows, dims[l], W[l], b[l], bn_scale ? bn_scale[l] : nullptr, bn_shift ? bn_shift[l] : nullptr,
+                                        last ? 0 : 1, dims[l + 1], dst, s))
+                return rc;
+            src = dst;
+        }
+        if (err_out)
+            if (int rc = recon_row_error(src, x + row0 * w, rows, w, l1, err_out + row0, s)) return rc;
+    }
+    return LCREC_OK;
+}
+
+LCREC_API int lcrec_decode_tuples(const int64_t *idx, int64_t idx_stride, int64_t n, const float *codebooks, const int *K, int L,
+                                  const int *dims, int n_layers, const float *const *W, const float *const *b,
+                                  const float *const *bn_scale, const float *const *bn_shift,
+                                  float *xq_out, float *out, const float *x, int l1, float *err_out, uint32_t *flags_out,
+                                  void *workspace, size_t workspace_bytes, void *stream)
+{
+    return decode_tuples(idx, idx_stride, n, codebooks, K, L, dims, n_layers, W, b, bn_scale, bn_shift, xq_out, out, x, l1, err_out,
+                         flags_out, workspace, workspace_bytes, (hipStream_t)stream, 0);
+}
+
+LCREC_API int lcrec_debug_decode_tuples(const int64_t *idx, int64_t idx_stride, int64_t n, const float *codebooks, const int *K, int L,
+                                        const int *dims, int n_layers, const float *const *W, const float *const *b,
+                                        const float *const *bn_scale, const float *const *bn_shift,
+                                        float *xq_out, float *out, const float *x, int l1, float *err_out, uint32_t *flags_out,
+                                        void *workspace, size_t workspace_bytes, void *stream, int64_t chunk_rows)
+{
+    return decode_tuples(idx, idx_stride, n, codebooks, K, L, dims, n_layers, W, b, bn_scale, bn_shift, xq_out, out, x, l1, err_out,
+                         flags_out, workspace, workspace_bytes, (hipStream_t)stream, chunk_rows);
 }
 
 LCREC_API int lcrec_trace_enable(int on)

@@ -1152,6 +1152,106 @@ def rq_audit_into(z, codebooks_flat, ks, idx, out):
     _lib.check(rc, "lcrec_rq_audit")
 
 
+def decode_plan(n, dims, ks, want_out=True, chunk_rows=0):
+    """How decode_tuples walks n rows through a decoder of widths `dims` (e_dim, hidden sizes ..., the embedding width) and where
+    everything lies in its workspace (include/lcrec.h, lcrec_debug_decode_tuples_plan): dict of the fields of lcrec_decode_plan.
+    chunk_rows: 0 = the built-in chunk.  Host only: no GPU is needed.  LcrecError for shapes lcrec_decode_tuples refuses."""
+    lib = _lib.load()
+    plan = _lib.DecodePlan()
+    rc = lib.lcrec_debug_decode_tuples_plan(int(n), _ints(dims), len(dims) - 1, _ints(ks), len(ks), int(bool(want_out)),
+                                            int(chunk_rows), ctypes.addressof(plan))
+    _lib.check(rc, "lcrec_debug_decode_tuples_plan")
+    out = {}
+    for name, _ in _lib.DecodePlan._fields_:
+        value = getattr(plan, name)
+        out[name] = [int(v) for v in value] if name == "act_offset" else int(value)
+    return out
+
+
+def decode_tuples(idx, codebooks_flat, ks, weights, biases, bn_scales=None, bn_shifts=None, x=None, l1=False, want_out=True,
+                  want_xq=False, chunk_rows=0, into=None, workspace=None):
+    """The decode pass (lcrec_decode_tuples of include/lcrec.h, which states the rule): the GIVEN tuples `idx` back to embeddings --
+    the sum of their code rows, then the decoder MLP -- and, with x, every item's reconstruction error against its row of x.
+
+    idx int64 [n, L], contiguous or a column block of a wider contiguous matrix (matrix[:, c:c + L]); it is only read.
+    codebooks_flat / ks as rq_assign.  weights[l] is nn.Linear.weight of DECODER layer l ([out_l, in_l]), biases[l] its bias or
+    None; bn_scales / bn_shifts per-layer folded eval-mode BatchNorm affines or None (the whole list, or single entries) -- what
+    MLPLayers.folded() returns.  x float32 [n, w] or None; l1: the L1 loss's error (sum |d|) instead of the squared one.
+    chunk_rows: 0 = the built-in chunk, any other size gives the same bits (lcrec_debug_decode_tuples).
+    into: a dict of buffers the caller owns, written instead of fresh ones -- "xq", "out", "err" float32, "flags" int32, each
+    contiguous on idx's device with at least the elements the call writes (it may be LARGER, so that a test can look at what lies
+    past the end); an output that is not in the dict is passed as NULL, and want_out / want_xq are not read.  workspace: a uint8
+    device tensor passed as the workspace as it is, its size included.
+    Returns a dict of device tensors "out" float32 [n, w], "xq" float32 [n, e], "err" float32 [n], "flags" int32 [n] (bit l: the
+    code of level l was outside [0, ks[l]) and was clamped); what was not asked for is None."""
+    lib = _lib.load()
+    cb = _dev(codebooks_flat, "codebooks")
+    nl, L, dev = len(weights), len(ks), cb.device
+    if nl < 1 or len(biases) != nl:
+        raise _lib.LcrecError(f"decoder: {nl} weights and {len(biases)} biases")
+    ws_ = [_dev(w, "weight") for w in weights]
+    bs_ = [None if b is None else _dev(b, "bias") for b in biases]
+    scs = [None] * nl if bn_scales is None else [None if s is None else _dev(s, "bn_scale") for s in bn_scales]
+    shs = [None] * nl if bn_shifts is None else [None if s is None else _dev(s, "bn_shift") for s in bn_shifts]
+    dims = [int(ws_[0].shape[1])] + [int(w.shape[0]) for w in ws_]
+    for l in range(nl):
+        if ws_[l].dim() != 2 or ws_[l].shape[1] != dims[l]:
+            raise _lib.LcrecError(f"decoder layer {l}: weight {tuple(ws_[l].shape)} does not chain")
+    e, w = dims[0], dims[-1]
+    if cb.numel() != sum(int(k) for k in ks) * e:
+        raise _lib.LcrecError(f"codebooks hold {cb.numel()} floats, {list(ks)} x {e} need {sum(int(k) for k in ks) * e}")
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 2
+            and idx.shape[1] == L and (idx.shape[0] <= 1 or idx.stride(0) >= L) and (L == 1 or idx.stride(1) == 1)):
+        raise _lib.LcrecError(f"idx must be an int64 [n, {L}] tensor on the codebooks' device, contiguous or a column block of a "
+                              "wider contiguous matrix")
+    n = int(idx.shape[0])
+    idx_stride = int(idx.stride(0)) if n > 1 else L
+    if x is not None:
+        x = _dev(x, "x")
+        if tuple(x.shape) != (n, w):
+            raise _lib.LcrecError(f"x is {tuple(x.shape)}, the decoder writes [{n}, {w}]")
+    sizes = {"xq": (torch.float32, n * e), "out": (torch.float32, n * w), "err": (torch.float32, n), "flags": (torch.int32, n)}
+    if into is None:
+        res = {"out": torch.empty((n, w), dtype=torch.float32, device=dev) if want_out else None,
+               "xq": torch.empty((n, e), dtype=torch.float32, device=dev) if want_xq else None,
+               "err": torch.empty(n, dtype=torch.float32, device=dev) if x is not None else None,
+               "flags": torch.empty(n, dtype=torch.int32, device=dev)}
+    else:
+        if set(into) - set(sizes):
+            raise _lib.LcrecError(f"into may hold {sorted(sizes)}, got {sorted(into)}")
+        for name, t in into.items():
+            dtype, need = sizes[name]
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()
+                    and t.numel() >= need):
+                raise _lib.LcrecError(f"into[{name!r}] must be a contiguous {dtype} tensor on idx's device with at least {need} elements")
+        res = {name: into.get(name) for name in sizes}
+    if workspace is not None and not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == dev
+                                      and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise _lib.LcrecError("workspace must be a contiguous uint8 tensor on idx's device")
+    if n == 0 and workspace is None:                       # (an empty tensor has no address to pass)
+        return res
+    PA = ctypes.c_void_p * nl
+    wp = PA(*[t.data_ptr() for t in ws_])
+    bp = PA(*[0 if t is None else t.data_ptr() for t in bs_])
+    scp = None if bn_scales is None else PA(*[0 if t is None else t.data_ptr() for t in scs])    # (no list: the NULL array)
+    shp = None if bn_shifts is None else PA(*[0 if t is None else t.data_ptr() for t in shs])
+    darr, karr = _ints(dims), _ints(ks)
+    with _on(dev):
+        if workspace is not None:
+            ws = workspace
+        else:
+            ws = _workspace(lib.lcrec_debug_decode_tuples_workspace(n, darr, nl, karr, L, int(res["out"] is not None), int(chunk_rows)),
+                            dev)
+        args = (_ptr(idx), idx_stride, n, _ptr(cb), karr, L, darr, nl, wp, bp, scp, shp, _ptr(res["xq"]), _ptr(res["out"]), _ptr(x),
+                int(bool(l1)), _ptr(res["err"]), _ptr(res["flags"]), _ptr(ws), ws.numel(), _stream_ptr())
+        if chunk_rows:
+            rc, what = lib.lcrec_debug_decode_tuples(*args, int(chunk_rows)), "lcrec_debug_decode_tuples"
+        else:
+            rc, what = lib.lcrec_decode_tuples(*args), "lcrec_decode_tuples"
+    _lib.check(rc, what)
+    return res
+
+
 def index_json_text(idx_rows, first_item=0):
     """bytes of the `.index.json` entries of items first_item.. for a HOST int64 [n, L] array
     (generate_indices.py:83-92,138-145; see lcrec_index_json_format in include/lcrec.h)."""

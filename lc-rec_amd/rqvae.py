@@ -91,6 +91,23 @@ class RQVAE(nn.Module):
                                 tie_tau=ops.NEARTIE_TAU if tie_tau is None else tie_tau)[0]
         return idx, audit["neartie"], audit["margin"]
 
+    @torch.no_grad()
+    def decode_indices(self, idx, xs=None):
+        """The way back from get_indices: index tuples int64 [n, L] -> reconstructed embeddings float32 [n, in_dim], the sum of the
+        tuples' code rows through the decoder in ONE library call (lcrec_decode_tuples of include/lcrec.h states the rule).  With
+        xs [n, in_dim] it returns (out, err): err float32 [n] is every item's reconstruction error under this model's loss_type
+        (the sum over the columns of (out - xs)^2 or of |out - xs|; its mean over items and columns is compute_loss's loss_recon).
+        Beyond the reference, whose decoder runs only inside forward.  Eval mode, ReLU decoder."""
+        self._check_shape()
+        if self.training or idx.dim() != 2 or not self.decoder.fusable():
+            raise ops._lib.LcrecError("decode_indices: eval mode, an [n, L] index matrix and a ReLU decoder are required")
+        if self.loss_type not in ("mse", "l1"):
+            raise ValueError("incompatible loss type")
+        Ws, bs, scs, shs = self.decoder.folded()
+        flat, ks = ops.flatten_codebooks([q.embedding.weight.detach() for q in self.rq.vq_layers])
+        res = ops.decode_tuples(idx, flat, ks, Ws, bs, scs, shs, x=xs, l1=self.loss_type == "l1")
+        return res["out"] if xs is None else (res["out"], res["err"])
+
     def compute_loss(self, out, quant_loss, xs=None):
         if self.loss_type == "mse":
             loss_recon = F.mse_loss(out, xs, reduction="mean")

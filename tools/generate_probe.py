@@ -6,6 +6,7 @@ pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing
     python tools/generate_probe.py --extend_new 10000,100000   # then --extend: the finished tuples as base, that many new items
     python tools/generate_probe.py --spill [--extend_new 100000]  # then --spill over what the finishing pass (and --extend) leave
     python tools/generate_probe.py --audit                     # then the index audit of the tuples about to be written (--audit)
+    python tools/generate_probe.py --decode                    # then the decode pass over them: tuples -> embeddings -> error per item
 """
 import argparse
 import os
@@ -76,6 +77,10 @@ def main():
     ap.add_argument("--audit", action="store_true", help="time the index audit (generate_indices --audit) of the finished tuples: one "
                     "warm-up pass, then --audit_runs timed ones, the median reported, with the run's pass 1 and rq_assign as yardsticks")
     ap.add_argument("--audit_runs", type=int, default=5)
+    ap.add_argument("--decode", action="store_true", help="time the decode pass (ops.decode_tuples with the items as x, no `out`) over "
+                    "the finished tuples: one warm-up pass, then --audit_runs timed ones, the median reported; the two new kernels' "
+                    "achieved bytes/s against the HBM peak, the decoder layers beside the encoder's, and the reconstruction loss of "
+                    "the finished tuples against the greedy ones")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.manual_seed(2024)
@@ -208,6 +213,52 @@ def main():
                        + ("   ONE rq_audit CALL COSTS MORE THAN THE WHOLE PASS 1" if per_call > t_pass1 * 1e3 else "")]
         audit_lines += ["  " + line for line in audit_indices.summary(rep)]
         del latent
+    decode_lines = []
+    if a.decode:
+        HBM_PEAK = 8.0e12                                  # bytes/s, the part's specified peak (a float4 copy measures 6.29e12)
+        CH = 1 << 20                                       # the host chunk of decode_indices
+        ops.set_pipelines(1)                               # one stream, as the decode pass runs: the brackets then add up to the wall time
+        ops.trace_enable(True)
+        (greedy, _, _), t_enc = timed(lambda: gen.assign_all(model, x))
+        tr_enc = ops.trace_collect()
+        ops.trace_enable(False)
+        ops.set_pipelines(2)
+        dW, db, dsc, dsh = model.decoder.folded()
+        flat, _ = ops.flatten_codebooks([q.embedding.weight.detach() for q in model.rq.vq_layers])
+
+        def decode(tuples):
+            return torch.cat([ops.decode_tuples(tuples[lo:lo + CH], flat, ks, dW, db, dsc, dsh, x=x[lo:lo + CH], want_out=False)["err"]
+                              for lo in range(0, a.items, CH)])
+        decode(idx)                                        # warm-up
+        walls, runs = [], []
+        for _ in range(max(a.audit_runs, 1)):
+            ops.trace_enable(True)
+            err_file, t_dec = timed(lambda: decode(idx))
+            runs.append(ops.trace_collect())
+            ops.trace_enable(False)
+            walls.append(t_dec)
+        err_greedy = decode(greedy)
+        med = lambda name: float(np.median([r.get(name, (0, 0.0))[1] for r in runs]))
+        layers = lambda tr: sum(v[1] for k, v in tr.items() if k.startswith("linear_fwd"))
+        t_gather, t_err = med("rq_decode_gather"), med("recon_row_error")
+        b_gather = a.items * (32 * 4 + a.levels * 8)       # q written once, the tuples read once (the code rows come from L2)
+        b_err = 2 * a.items * a.in_dim * 4 + a.items * 4   # y and x read once, err written
+        count = float(a.items) * a.in_dim
+        rf = float(err_file.cpu().numpy().astype(np.float64).sum() / count)
+        rg = float(err_greedy.cpu().numpy().astype(np.float64).sum() / count)
+        rate = lambda b, ms: b / (ms * 1e-3) if ms > 0 else 0.0
+        decode_lines = [
+            f"decode (decode_tuples)   {np.median(walls) * 1e3:9.1f} ms   median of {len(walls)} runs after one warm-up (min {min(walls) * 1e3:.1f}, "
+            f"max {max(walls) * 1e3:.1f}); {runs[-1]['rq_decode_gather'][0]} chunks per run",
+            f"  rq_decode_gather {t_gather:.3f} ms per run by the trace brackets: {rate(b_gather, t_gather) / 1e12:.2f} TB/s = "
+            f"{100 * rate(b_gather, t_gather) / HBM_PEAK:.1f} % of the 8.0 TB/s HBM peak (memory-bound: q written once)",
+            f"  recon_row_error  {t_err:.3f} ms per run by the trace brackets: {rate(b_err, t_err) / 1e12:.2f} TB/s = "
+            f"{100 * rate(b_err, t_err) / HBM_PEAK:.1f} % of the 8.0 TB/s HBM peak (memory-bound: y and x read once)",
+            f"  decoder layers {float(np.median([layers(r) for r in runs])):.1f} ms per run by the trace brackets; the encoder's in this run "
+            f"{layers(tr_enc):.1f} ms (pass 1 {t_enc * 1e3:.1f} ms wall)",
+            f"  reconstruction loss (mse): finished tuples {rf:.6g}, greedy tuples {rg:.6g} ({100.0 * (rf / rg - 1.0):+.4g} %); "
+            f"{int((idx != greedy).any(1).sum())} items hold another tuple than their greedy one"]
+        del err_file, err_greedy
     _, t_json = timed(lambda: gen.dump_index_json(idx, a.out))
     size = os.path.getsize(a.out)
     extend_lines = []
@@ -235,7 +286,7 @@ def main():
           f"largest {fin['largest_bucket']} items, moved {fin['moved']}, unresolved {fin['unresolved']}")
     print("  kernels: " + ", ".join(f"{k} {v[1]:.2f} ms/{v[0]}" for k, v in sorted(ftrace.items(), key=lambda kv: -kv[1][1])))
     print(f"  collision rate {final['collision_rate']:.6f} -> {finished['collision_rate']:.6f}")
-    for line in spill_lines + audit_lines:
+    for line in spill_lines + audit_lines + decode_lines:
         print(line)
     print(f".index.json ({size / 1e6:.0f} MB)     {t_json * 1e3:9.1f} ms   {a.items / t_json / 1e6:7.2f} M items/s (D2H + text + write)")
     for line in extend_lines:

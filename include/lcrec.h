@@ -764,6 +764,50 @@ int lcrec_rq_audit(const float *z, int64_t n, int e, const float *codebooks, con
                    int64_t *best_out, float *err_out, float *resid_out, uint32_t *flags_out,
                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* Beam-search quantiser: the `width` best whole tuples of every item.  lcrec_rq_assign walks the levels greedily -- the nearest
+ * code, subtract, move on -- and the finishing, extending and spilling passes only ever move an item off that one tuple.  This
+ * entry keeps `width` partial tuples per item, each with its own residual, scores all their children at a level and keeps the
+ * `width` best.  Beyond the reference, which is greedy throughout.
+ *
+ * The rule.  d(r, c_k) = (xx + cc_k) - 2*dot_k, xx, cc_k and dot_k each one fp32 fma chain over the dimension ascending from 0:
+ * the distance of lcrec_rq_assign, lcrec_finish_nearest_free and lcrec_rq_audit, bit for bit.  A NaN distance counts as +inf
+ * wherever distances are compared, and is reported as +inf.  For item i with latent z_i, width W, levels l = 0 .. L-1:
+ *   1. Start with one live beam: residual r = z_i, the empty tuple.  P = 1.
+ *   2. At level l every live beam p (in its current order, p = 0 .. P-1) and every code k < K[l] is a candidate with score
+ *      s(p, k) = d(r_p, C_l[k]).  The first P' = min(W, P * K[l]) candidates in the order (score ascending, then p ascending,
+ *      then k ascending) are the new beams 0 .. P'-1.
+ *   3. New beam b from candidate (p, k): its tuple is beam p's tuple with k appended; its residual follows lcrec_rq_assign's three
+ *      fp32 operations per element with c = C_l[k] and r = r_p: t = c - r; s = r + t; r' = r - s.
+ *   4. After the last level score[b] is the candidate's score at level L-1, err[b] the fp32 fma chain of r_L[j] * r_L[j] over j
+ *      ascending from 0 (lcrec_rq_audit's err), and the beams stay in the order of step 2.
+ * Consequences: for W = 1 beam 0 is lcrec_rq_assign's tuple, and its err and score are lcrec_rq_audit's err and d_held[:, L-1] of
+ * that tuple, bit for bit; for any W, walking beam b's tuple through lcrec_rq_audit reproduces err[b] and score[b] bit for bit; the
+ * live beams of an item are pairwise distinct tuples; score is non-decreasing in b; the live count, min(W, K[0] * K[1] * ...) with
+ * the product capped at W after every level, depends on W and K alone, and rows b >= live hold -1 in every tuple column and +inf
+ * in score, err and resid.  Nothing else is promised: in particular beam 0's err may EXCEED the greedy tuple's (a beam is not
+ * monotone; RQVAE.get_indices_beam keeps the greedy tuple for such an item).
+ *
+ *   z, codebooks, K   as lcrec_rq_assign; e in {16, 32, 64}; 1 <= L <= LCREC_MAX_LEVELS.  Every level lcrec_rq_assign takes is
+ *                     taken (the level's rows and cc in LDS: K[l] * (4 e + 20) bytes); one it refuses is LCREC_EUNSUPPORTED
+ *   width             1, 2, 4 or 8
+ *   tuples_out        device [n][width][L] int64
+ *   score_out, err_out   device [n][width] float
+ *   resid_out         device [n][width][e] float, or NULL: r_L of every beam
+ *   workspace         device, lcrec_rq_beam_workspace() bytes: 0 for L == 1; else the residuals of all beams between the levels,
+ *                     [n][width][e] floats rounded up to 256 bytes, once for L == 2 and twice (the levels alternate) for L > 2,
+ *                     then the (parent, code) links of the levels before the last, (L-1) * n * width ints rounded up to 256 bytes
+ * Every output element of rows [0, n) is written by every call, dead beams included; the workspace may hold anything.  z,
+ * codebooks, resid_out and workspace 16-byte aligned, tuples_out 8-byte, score_out and err_out 4-byte.  n == 0: no launch.  One
+ * launch per level: an item owns `width` consecutive lanes, one per parent beam; the lane sweeps the level's codes once and keeps
+ * its `width` best, the item's lanes merge their lists by lane shuffles, and the last level walks the links back to write the
+ * tuples.  No allocation, no host synchronisation, capturable.  Argument errors (LCREC_EINVAL: a NULL pointer, e, L, width,
+ * K[l] < 1, misalignment; LCREC_EWORKSPACE) are reported before the device is touched, with a last-error text that names the
+ * argument.  Traced as "rq_beam", one bracket per call.  lcrec_rq_beam_workspace returns 0 for arguments lcrec_rq_beam refuses. */
+size_t lcrec_rq_beam_workspace(int64_t n, int e, const int *K, int L, int width);
+int lcrec_rq_beam(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L, int width,
+                  int64_t *tuples_out, float *score_out, float *err_out, float *resid_out,
+                  void *workspace, size_t workspace_bytes, void *stream);
+
 /* Decode pass: GIVEN tuples back to embeddings, and the reconstruction error of every item.  lcrec_encode_assign goes from an
  * embedding to a tuple and lcrec_rq_audit prices a tuple in latent space; this entry goes the way back -- codes, their sum, the
  * decoder MLP (RQVAE.forward's `out = self.decoder(x_q)`, index/models/rqvae.py:57-66, which the reference runs only inside a

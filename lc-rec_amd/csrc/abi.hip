@@ -30,7 +30,7 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
                                            "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free",
                                            "spill_nearest_free", "spill_keepers", "rq_audit", "rq_decode_gather",
-                                           "recon_row_error"};
+                                           "recon_row_error", "rq_beam"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -654,6 +654,19 @@ LCREC_API int lcrec_rq_audit(const float *z, int64_t n, int e, const float *code
 {
     return rq_audit(z, n, e, codebooks, K, L, idx, idx_stride, d_held_out, d_best_out, rank_out, best_out, err_out, resid_out,
                     flags_out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+LCREC_API size_t lcrec_rq_beam_workspace(int64_t n, int e, const int *K, int L, int width)
+{
+    return rq_beam_workspace(n, e, K, L, width);
+}
+
+LCREC_API int lcrec_rq_beam(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L, int width,
+                            int64_t *tuples_out, float *score_out, float *err_out, float *resid_out, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    return rq_beam(z, n, e, codebooks, K, L, width, tuples_out, score_out, err_out, resid_out, workspace, workspace_bytes,
+                   (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_bn_relu_forward(const float *t, int64_t n, int features, const float *gamma, const float *beta, float eps,

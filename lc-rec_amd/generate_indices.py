@@ -25,6 +25,9 @@ Documented divergences from the reference script:
     last level has codes, takes the next-nearest code one level up and the nearest free last-level code there (spill_collisions);
   * --audit (off by default) goes BEYOND the reference as well: the tuples about to be written are walked through the quantiser again
     and what the moves above cost -- ranks, distance regret, added quantisation error -- is reported (audit_indices.report_for);
+  * --beam W (off by default: W = 1) goes BEYOND the reference, which is greedy throughout: pass 1 walks the quantiser with a beam of
+    W partial tuples per item (ops.rq_beam) and every item gets the best whole tuple found, or its greedy one where that is better;
+    the rounds and the passes above then run on those tuples and their residuals (assign_all);
   * it stores tokens in fixed-width numpy unicode arrays (:98-99) which silently truncate a
     replacement longer than anything seen in pass 1; integer tuples are kept here, and a warning is
     logged if a run ever hits that case (the reference's output would be corrupt there).
@@ -84,11 +87,21 @@ def build_model_from_args(args, in_dim):
 
 
 @torch.no_grad()
-def assign_all(model, data, chunk_rows=1 << 20, audit=None, want_prev=False, latents=None):
+def assign_all(model, data, chunk_rows=1 << 20, audit=None, want_prev=False, latents=None, beam=1, beam_info=None):
     """Pass 1 (:77-95): int64 [N, L] hard indices plus the residual entering the last level.
     audit: optional dict; receives "neartie" (int32 [N], ops.NEARTIE_TAU) -- the near-tie flags of pass 1.
     want_prev: a fourth value is returned, the residual entering level L-2 (L = 2: the latent; L = 1: None) -- spill_collisions'.
-    latents: optional list; receives every chunk's latents (float32 [rows, e]) in order -- the index audit's (--audit)."""
+    latents: optional list; receives every chunk's latents (float32 [rows, e]) in order -- the index audit's (--audit).
+    beam: 1 = the greedy walk, and nothing of the beam path is called.  2, 4 or 8: the returned tuples are the CHOSEN tuples of a beam
+    of that width (ops.beam_choose: beam 0's tuple, or the greedy one where it leaves the smaller residual), chunk by chunk on the
+    latents the one encoder run produced, and the residuals returned are those of the chosen tuples -- ops.rq_audit walks their
+    prefixes idx[:, :L-1] / idx[:, :L-2] as tuples of a shorter quantiser.  beam_info: optional dict; receives "greedy" (a list
+    of every chunk's greedy tuples), "changed", "kept_greedy" (item counts) and "err_chosen", "err_greedy" (float64 sums over
+    the items on which both errors are finite)."""
+    if beam not in ops.BEAM_WIDTHS:
+        raise ValueError(f"beam={beam!r}: one of {ops.BEAM_WIDTHS}")
+    if beam_info is not None:
+        beam_info.update(greedy=[], changed=0, kept_greedy=0, err_chosen=0.0, err_greedy=0.0)
     levels = list(model.rq.vq_layers)
     Ws, bs, scs, shs = model.encoder.folded()
     cbs = [q.embedding.weight.detach() for q in levels]
@@ -99,11 +112,31 @@ def assign_all(model, data, chunk_rows=1 << 20, audit=None, want_prev=False, lat
         a = {} if audit is not None else None
         idx, latent, _, _ = ops.encode_assign(x, Ws, bs, flat, ks, scs, shs, want_latent=True, audit=a,
                                               tie_tau=ops.NEARTIE_TAU)
-        idx_parts.append(idx)
         if latents is not None:
             latents.append(latent)
         if a is not None:
             tie_parts.append(a["neartie"])
+        if beam > 1:
+            chosen, info = ops.beam_choose(latent, flat, ks, idx, beam)
+            if beam_info is not None:
+                both = torch.isfinite(info["err_chosen"]) & torch.isfinite(info["err_greedy"])
+                beam_info["greedy"].append(idx)
+                beam_info["changed"] += int((chosen != idx).any(1).sum())
+                beam_info["kept_greedy"] += int(info["kept_greedy"].sum())
+                beam_info["err_chosen"] += float(info["err_chosen"][both].double().sum())
+                beam_info["err_greedy"] += float(info["err_greedy"][both].double().sum())
+            idx_parts.append(chosen)
+            L = len(levels)
+            for depth, parts in ((L - 1, last_parts), (L - 2, prev_parts if want_prev else None)):
+                if parts is None or depth < 0:
+                    continue
+                if depth == 0:
+                    parts.append(latent)
+                else:
+                    pflat, pks = ops.flatten_codebooks(cbs[:depth])
+                    parts.append(ops.rq_audit(latent, pflat, pks, chosen[:, :depth], want_resid=True)["resid"])
+            continue
+        idx_parts.append(idx)
         if len(levels) > 1:
             pflat, pks = ops.flatten_codebooks(cbs[:-1])
             _, _, _, resid = ops.rq_assign(latent, pflat, pks, want_resid=True)
@@ -328,15 +361,17 @@ def _spill_and_log(model, idx, n_frozen, resid_prev, resid_last, ks, stats):
                     ks[-2], ks[-1], ks[-2] * ks[-1])
 
 
-def _audit_and_log(model, latents, greedy, neartie, held, stats, what="", first_item=0):
+def _audit_and_log(model, latents, greedy, neartie, held, stats, what="", first_item=0, foreign_check=True):
     """--audit: the report of the tuples `held` about to be written (audit_indices.report_for, on pass 1's latents, greedy tuples and
-    near-tie flags of the same items) goes into stats["audit"]; its summary is logged."""
+    near-tie flags of the same items) goes into stats["audit"]; its summary is logged.  foreign_check=False (--beam: such a
+    file leaves the greedy path early by design) skips the warning about a file that was not written from this checkpoint."""
     from . import audit_indices
     flat, ks = ops.flatten_codebooks([q.embedding.weight.detach() for q in model.rq.vq_layers])
     stats["audit"] = audit_indices.report_for(flat, ks, torch.cat(latents), greedy, neartie, held, first_item=first_item)
     for line in audit_indices.summary(stats["audit"]):
         log.info("--audit%s: %s", what, line)
-    audit_indices.warn_if_foreign(stats["audit"])
+    if foreign_check:
+        audit_indices.warn_if_foreign(stats["audit"])
 
 
 def _refuse_one_level(args):
@@ -560,7 +595,7 @@ def sharded_assign(ctx, data, assign_fn, device):
 
 
 def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=True, ctx=None, trust_checkpoint=False,
-             recheck=False, finish="none", extend=None, spill=False, audit=False):
+             recheck=False, finish="none", extend=None, spill=False, audit=False, beam=1):
     """Whole flow of generate_indices.py:51-145.  Returns a dict of the statistics it prints.
     recheck: re-evaluate the near-tie items of pass 1 in the reference's CPU operation order (recheck_neartie).
     finish: "none" (the reference's bytes) or "nearest_free" (finish_collisions after the rounds; beyond the reference).
@@ -577,10 +612,29 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         keys).  With `extend` it covers the new rows only.  Refused with ValueError, as `spill` is, with `recheck` and under
         torchrun.  Without it the returned dict and the file are exactly what they were.
 
+    beam: 1 (the default) is the code path above, untouched: lcrec_rq_beam is not even called.  2, 4 or 8: pass 1's tuples are the
+        chosen tuples of a beam of that width (assign_all); the conflict rounds, `finish`, `spill` and the writer then run as they do
+        on those tuples and their residuals, and the statistics gain beam_width, beam_changed (items whose chosen tuple is not the
+        greedy one), beam_kept_greedy (items where beam 0 lost to the greedy tuple), beam_err_ratio (the sum of the chosen tuples'
+        quantisation errors over the greedy tuples', in float64 over the items where both are finite; at most 1 by construction)
+        and collision_rate_pass1 (of the chosen tuples, before the rounds).  With `audit` the report's greedy side stays pass 1's
+        greedy tuples, so err_file_mean against err_greedy_mean shows what the beam bought net of the collision moves.  Refused
+        with ValueError, as `spill` is, with `extend`, `recheck` and under torchrun.
+
     Under torchrun (ctx = dist.init_from_env()) pass 1 is item-sharded over the ranks and each conflict round's
     groups are sharded too (resolve_collisions); rank 0 writes the file."""
     from . import dist as ldist
     ctx = ctx or ldist.current()
+    if beam not in ops.BEAM_WIDTHS:
+        raise ValueError(f"--beam {beam!r}: one of {ops.BEAM_WIDTHS}")
+    if beam > 1:
+        if extend is not None:
+            raise ValueError("--beam with --extend is not supported: the new items are indexed around frozen tuples by the distance "
+                             "rule alone")
+        if recheck:
+            raise ValueError("--beam with --recheck_neartie is not supported: the re-evaluation reproduces the reference's greedy walk")
+        if ctx.enabled:
+            raise ValueError("--beam under torchrun is not supported: run it in a single process")
     if spill:
         if extend is None and finish != "nearest_free":
             raise ValueError("--spill runs over what --finish nearest_free or --extend leave unresolved: give one of them")
@@ -620,14 +674,25 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
     ties = {}
     prev = []                                              # spill: the residual entering level L-2 (one process: nothing to gather)
     latents = [] if audit else None                        # audit: pass 1's latents (one process too)
+    beamed = {} if beam > 1 else None                      # beam: pass 1's greedy tuples and what the beam changed (one process too)
 
     def assign(x):
-        out = assign_all(model, x, audit=ties, want_prev=spill, latents=latents)
+        out = assign_all(model, x, audit=ties, want_prev=spill, latents=latents, beam=beam, beam_info=beamed)
         prev.extend(out[3:])
         return out[:3]
 
     idx, resid_last, ks = sharded_assign(ctx, data, assign, device)
     first_pass = idx.clone()
+    beam_stats = {}
+    if beam > 1:
+        n1 = idx.shape[0]
+        pass1 = ops.collision_groups(idx, ks, want_groups=False)
+        beam_stats = {"beam_width": beam, "beam_changed": beamed["changed"], "beam_kept_greedy": beamed["kept_greedy"],
+                      "beam_err_ratio": beamed["err_chosen"] / beamed["err_greedy"] if beamed["err_greedy"] else 1.0,
+                      "collision_rate_pass1": (n1 - pass1["unique"]) / n1 if n1 else 0.0}
+        log.info("--beam %d: %d of %d items leave their greedy tuple, %d keep it because beam 0 was worse; quantisation error "
+                 "%.4f x the greedy tuples'; collision rate of pass 1 %.6f", beam, beam_stats["beam_changed"], n1,
+                 beam_stats["beam_kept_greedy"], beam_stats["beam_err_ratio"], beam_stats["collision_rate_pass1"])
     # near-tie audit of pass 1: items whose two best codes at some level are closer than the rounding noise of
     # vq.py:71-73 -- the only ones a CPU run of the reference could index differently (ops.NEARTIE_TAU)
     neartie_items = int(ctx.sum_int(int((ties["neartie"] != 0).sum())))
@@ -672,8 +737,10 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
              "finish": finish, "finish_moved": finished["moved"], "finish_unresolved": finished["unresolved"]}
     if spill:
         stats.update(spilled)
+    stats.update(beam_stats)
     if audit:
-        _audit_and_log(model, latents, first_pass, ties["neartie"], idx, stats)
+        greedy = torch.cat(beamed["greedy"]) if beam > 1 else first_pass
+        _audit_and_log(model, latents, greedy, ties["neartie"], idx, stats, foreign_check=beam == 1)
     if lead:
         log.info("near-tie items in pass 1: %d of %d (top-2 code gap <= %.3g x distance magnitude at some level); only "
                  "these could receive a different tuple from a CPU run of the reference", neartie_items, n, ops.NEARTIE_TAU)
@@ -720,6 +787,11 @@ def parse_args(argv=None):
                          "passes above cost: how many items hold a code that is not their nearest, at which level and rank, and the "
                          "quantisation error that added (audit_indices.py does the same for an existing file).  With --extend the "
                          "new rows only: there are no latents for the frozen items.  Not with --recheck_neartie or torchrun")
+    ap.add_argument("--beam", type=int, choices=ops.BEAM_WIDTHS, default=1, metavar="W",
+                    help="walk the quantiser's levels in pass 1 with a beam of W partial tuples per item (1, 2, 4 or 8) instead of the "
+                         "greedy walk, and give every item the best whole tuple found -- or its greedy one where that leaves the "
+                         "smaller residual (goes beyond the reference; 1 = the greedy walk, the default, and the reference's bytes). "
+                         "Not with --extend, --recheck_neartie or torchrun")
     return ap.parse_args(argv)
 
 
@@ -731,7 +803,7 @@ def main(argv=None):
     try:
         return generate(a.ckpt_path, out, device=a.device, data_path=a.data_path, ctx=ctx,
                         trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish, extend=a.extend,
-                        spill=a.spill, audit=a.audit)
+                        spill=a.spill, audit=a.audit, beam=a.beam)
     finally:
         ldist.shutdown(ctx)
 

@@ -1152,6 +1152,106 @@ def rq_audit_into(z, codebooks_flat, ks, idx, out):
     _lib.check(rc, "lcrec_rq_audit")
 
 
+BEAM_WIDTHS = (1, 2, 4, 8)
+BEAM_WORKSPACE_BOUND = 256 << 20   # bytes of lcrec_rq_beam workspace that rq_beam's chunk walk stays within
+
+
+def rq_beam(z, codebooks_flat, ks, width, want_resid=False):
+    """The beam-search quantiser (lcrec_rq_beam of include/lcrec.h, which states the rule): the `width` best whole tuples of every
+    item, best first, each with the score of its last candidate and the squared norm of the residual it leaves.
+
+    z float32 [n, e]; codebooks_flat / ks as rq_assign; width in BEAM_WIDTHS.  Returns a dict of device tensors: "tuples" int64
+    [n, width, L], "score", "err" float32 [n, width] and on request "resid" float32 [n, width, e].  Rows past the live count (which
+    depends on width and ks alone) hold -1 / +inf.  n is walked in chunks of whole items sized so that the library's workspace (the
+    residuals of all beams between the levels and their links) stays within BEAM_WORKSPACE_BOUND = 256 MiB -- 125 202 items per
+    chunk at width 8, e = 32, four levels; a single item always goes, whatever it needs."""
+    z = _dev(z, "z")
+    if z.dim() != 2:
+        raise _lib.LcrecError(f"z must be [n, e], got {tuple(z.shape)}")
+    if width not in BEAM_WIDTHS:
+        raise _lib.LcrecError(f"width={width!r} (supported: 1, 2, 4, 8)")
+    n, e = z.shape
+    L = len(ks)
+    dev = z.device
+    out = {"tuples": torch.empty((n, width, L), dtype=torch.int64, device=dev),
+           "score": torch.empty((n, width), dtype=torch.float32, device=dev),
+           "err": torch.empty((n, width), dtype=torch.float32, device=dev)}
+    if want_resid:
+        out["resid"] = torch.empty((n, width, e), dtype=torch.float32, device=dev)
+    rq_beam_into(z, codebooks_flat, ks, width, out)
+    return out
+
+
+def beam_chunk_rows(e, L, width, bound=None):
+    """Items per lcrec_rq_beam call such that its workspace stays within `bound` bytes (None: BEAM_WORKSPACE_BOUND; at least one
+    item).  Host only."""
+    bound = BEAM_WORKSPACE_BOUND if bound is None else bound
+    halves = 0 if L < 2 else (1 if L == 2 else 2)
+    per_item = halves * width * e * 4 + max(L - 1, 0) * width * 4
+    slack = 256 * (halves + 1)                              # each part is rounded up to 256 bytes
+    return max((bound - slack) // per_item, 1) if per_item else 1 << 62
+
+
+def rq_beam_into(z, codebooks_flat, ks, width, out, workspace=None):
+    """lcrec_rq_beam into buffers the caller owns: `out` holds "tuples" int64, "score", "err" float32 and may hold "resid" float32
+    (missing: passed as NULL), each contiguous on z's device with at least the elements the call writes -- it may be LARGER, so
+    that a test can look at what lies past the end.  workspace: a uint8 device tensor passed as the workspace as it is, its size
+    included, for ONE call over all rows; None: the binding's own, and the chunk walk of rq_beam.  Nothing is returned."""
+    lib = _lib.load()
+    z = _dev(z, "z")
+    cb = _dev(codebooks_flat, "codebooks")
+    if z.dim() != 2:
+        raise _lib.LcrecError(f"z must be [n, e], got {tuple(z.shape)}")
+    n, e = z.shape
+    L = len(ks)
+    dev = z.device
+    width = int(width)
+    if cb.numel() != sum(int(k) for k in ks) * e:
+        raise _lib.LcrecError(f"codebooks hold {cb.numel()} floats, {list(ks)} x {e} need {sum(int(k) for k in ks) * e}")
+    sizes = {"tuples": (torch.int64, width * L), "score": (torch.float32, width), "err": (torch.float32, width),
+             "resid": (torch.float32, width * e)}
+    if set(sizes) - {"resid"} - set(out) or set(out) - set(sizes):
+        raise _lib.LcrecError(f"out must hold tuples, score, err and may hold resid; got {sorted(out)}")
+    for name, t in out.items():
+        dtype, per = sizes[name]
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()
+                and t.numel() >= n * per):
+            raise _lib.LcrecError(f"out[{name!r}] must be a contiguous {dtype} tensor on z's device with at least {n * per} elements")
+    if workspace is not None and not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == dev
+                                      and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise _lib.LcrecError("workspace must be a contiguous uint8 tensor on z's device")
+    if n == 0:                                             # (an empty tensor has no address to pass)
+        return
+    karr = _ints(ks)
+    step = n if workspace is not None else min(n, beam_chunk_rows(e, L, width))
+    flat = {name: t.view(-1) for name, t in out.items()}
+    with _on(dev):
+        for a in range(0, n, step):
+            rows = min(step, n - a)
+            ws = workspace if workspace is not None else _workspace(lib.lcrec_rq_beam_workspace(rows, e, karr, L, width), dev)
+            part = {name: flat[name][a * sizes[name][1]:] for name in flat}
+            rc = lib.lcrec_rq_beam(_ptr(z[a:a + rows]), rows, e, _ptr(cb), karr, L, width, _ptr(part["tuples"]), _ptr(part["score"]),
+                                   _ptr(part["err"]), _ptr(part.get("resid")), _ptr(ws) if ws.numel() else _ptr(None), ws.numel(),
+                                   _stream_ptr())
+            _lib.check(rc, "lcrec_rq_beam")
+
+
+def beam_choose(z, codebooks_flat, ks, greedy, width):
+    """The chosen tuples of a beam of `width` over the latents z, given their greedy tuples `greedy` int64 [n, L] (rq_assign's /
+    encode_assign's): item i gets beam 0's tuple unless err_greedy[i] < err_beam0[i] (strict; a NaN counts as +inf), in which case it
+    keeps the greedy one -- a beam is not monotone, and this way no item's final error exceeds its greedy error.  err_greedy is
+    rq_audit's err of the greedy tuples: the same fma chain as the beam's, so at width 1 nothing is ever replaced.
+    Returns (chosen int64 [n, L], dict of "err_greedy", "err_chosen" float32 [n], "kept_greedy" bool [n], "beams": rq_beam's dict)."""
+    beams = rq_beam(z, codebooks_flat, ks, width)
+    err_g = rq_audit(z, codebooks_flat, ks, greedy)["err"]
+    err_b = beams["err"][:, 0]
+    inf = torch.full_like(err_g, float("inf"))
+    eg, eb = torch.where(torch.isnan(err_g), inf, err_g), torch.where(torch.isnan(err_b), inf, err_b)
+    keep = eg < eb
+    chosen = torch.where(keep[:, None], greedy, beams["tuples"][:, 0, :])
+    return chosen, {"err_greedy": err_g, "err_chosen": torch.where(keep, err_g, err_b), "kept_greedy": keep, "beams": beams}
+
+
 def decode_plan(n, dims, ks, want_out=True, chunk_rows=0):
     """How decode_tuples walks n rows through a decoder of widths `dims` (e_dim, hidden sizes ..., the embedding width) and where
     everything lies in its workspace (include/lcrec.h, lcrec_debug_decode_tuples_plan): dict of the fields of lcrec_decode_plan.

@@ -92,6 +92,25 @@ class RQVAE(nn.Module):
         return idx, audit["neartie"], audit["margin"]
 
     @torch.no_grad()
+    def get_indices_beam(self, xs, width, return_all=False):
+        """get_indices(xs, use_sk=False) with a beam of `width` (1, 2, 4 or 8) through the quantiser's levels instead of the greedy
+        walk (include/lcrec.h, lcrec_rq_beam, states the rule): the encoder runs once, then ops.rq_beam on its latents.  Returns
+        the CHOSEN tuples int64 [n, L]: beam 0's, except where the greedy tuple leaves a strictly smaller residual -- a beam is
+        not monotone -- so no item's quantisation error exceeds its greedy error, and at width 1 the result is get_indices's bit
+        for bit (ops.beam_choose).  return_all: also the dict of all beams ("tuples" [n, width, L], "score", "err" [n, width]).
+        Beyond the reference, which is greedy throughout.  Eval mode, 2-d input, ReLU encoder."""
+        self._check_shape()
+        if self.training or xs.dim() != 2 or not self.encoder.fusable():
+            raise ops._lib.LcrecError("get_indices_beam: eval mode, a 2-d batch and a ReLU encoder are required")
+        if width not in ops.BEAM_WIDTHS:
+            raise ValueError(f"get_indices_beam: width={width!r} (supported: 1, 2, 4, 8)")
+        Ws, bs, scs, shs = self.encoder.folded()
+        flat, ks = ops.flatten_codebooks([q.embedding.weight.detach() for q in self.rq.vq_layers])
+        greedy, latent, _, _ = ops.encode_assign(xs, Ws, bs, flat, ks, scs, shs, want_latent=True)
+        chosen, info = ops.beam_choose(latent, flat, ks, greedy, width)
+        return (chosen, info["beams"]) if return_all else chosen
+
+    @torch.no_grad()
     def decode_indices(self, idx, xs=None):
         """The way back from get_indices: index tuples int64 [n, L] -> reconstructed embeddings float32 [n, in_dim], the sum of the
         tuples' code rows through the decoder in ONE library call (lcrec_decode_tuples of include/lcrec.h states the rule).  With

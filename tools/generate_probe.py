@@ -7,6 +7,7 @@ pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing
     python tools/generate_probe.py --spill [--extend_new 100000]  # then --spill over what the finishing pass (and --extend) leave
     python tools/generate_probe.py --audit                     # then the index audit of the tuples about to be written (--audit)
     python tools/generate_probe.py --decode                    # then the decode pass over them: tuples -> embeddings -> error per item
+    python tools/generate_probe.py --beam 2,4,8                # then the beam-search quantiser (--beam W) at each width over pass 1's latents
 """
 import argparse
 import os
@@ -81,6 +82,10 @@ def main():
                     "the finished tuples: one warm-up pass, then --audit_runs timed ones, the median reported; the two new kernels' "
                     "achieved bytes/s against the HBM peak, the decoder layers beside the encoder's, and the reconstruction loss of "
                     "the finished tuples against the greedy ones")
+    ap.add_argument("--beam", type=str, default="", metavar="W[,W...]", help="time the beam-search quantiser (ops.rq_beam, generate "
+                    "--beam W) over pass 1's latents at each width given: one warm-up call, then --audit_runs timed ones, the median "
+                    "of the rq_beam trace brackets reported beside pass 1's rq_assign and one rq_audit over the same rows in the same "
+                    "run, the achieved fma rate against the fp32 vector peak, and what the chosen tuples change")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.manual_seed(2024)
@@ -259,6 +264,56 @@ def main():
             f"  reconstruction loss (mse): finished tuples {rf:.6g}, greedy tuples {rg:.6g} ({100.0 * (rf / rg - 1.0):+.4g} %); "
             f"{int((idx != greedy).any(1).sum())} items hold another tuple than their greedy one"]
         del err_file, err_greedy
+    beam_lines = []
+    if a.beam:
+        FMA_PEAK = 157.3e12 / 2                            # fp32 fma/s of the vector units (157.3 TFLOPS specified)
+        lat = []
+        ops.trace_enable(True)
+        (greedy, _, _), _ = timed(lambda: gen.assign_all(model, x, latents=lat))
+        tr_p1 = ops.trace_collect()
+        ops.trace_enable(False)
+        flat, _ = ops.flatten_codebooks([q.embedding.weight.detach() for q in model.rq.vq_layers])
+        latent = torch.cat(lat)
+        del lat
+        ops.rq_audit(latent, flat, ks, greedy)             # warm-up
+        t_aud = []
+        for _ in range(max(a.audit_runs, 1)):
+            ops.trace_enable(True)
+            aud, _ = timed(lambda: ops.rq_audit(latent, flat, ks, greedy))
+            t_aud.append(ops.trace_collect()["rq_audit"][1])
+            ops.trace_enable(False)
+        t_aud = float(np.median(t_aud))
+        t_asg = tr_p1.get("rq_assign", (0, 0.0))
+        rate0 = ops.collision_groups(greedy, ks, want_groups=False)["collision_rate"]
+        beam_lines = [f"beam: yardsticks of this run over the same {a.items} rows: rq_audit {t_aud:.2f} ms per call (median of "
+                      f"{max(a.audit_runs, 1)}), pass 1's rq_assign {t_asg[1]:.2f} ms/{t_asg[0]} by the trace brackets; greedy collision "
+                      f"rate {rate0:.6f}"]
+        for W in [int(w) for w in a.beam.split(",") if w]:
+            ops.rq_beam(latent, flat, ks, W)               # warm-up
+            ms, calls = [], 0
+            for _ in range(max(a.audit_runs, 1)):
+                ops.trace_enable(True)
+                _, _ = timed(lambda: ops.rq_beam(latent, flat, ks, W))
+                calls, t = ops.trace_collect()["rq_beam"]
+                ops.trace_enable(False)
+                ms.append(t)
+            t_beam = float(np.median(ms))
+            fmas, live = 0.0, 1
+            for k in ks:                                   # the sweep's dot products: live parents x codes x e per item and level
+                fmas += float(a.items) * live * k * 32
+                live = min(W, live * k)
+            chosen, info = ops.beam_choose(latent, flat, ks, greedy, W)
+            both = torch.isfinite(info["err_chosen"]) & torch.isfinite(info["err_greedy"])
+            ratio = float(info["err_chosen"][both].double().sum() / info["err_greedy"][both].double().sum())
+            rate1 = ops.collision_groups(chosen, ks, want_groups=False)["collision_rate"]
+            beam_lines.append(
+                f"  rq_beam W={W}: {t_beam:.2f} ms per run over {calls} chunk calls (median of {len(ms)}, min {min(ms):.2f}, max "
+                f"{max(ms):.2f}) = {t_beam / t_aud:.2f} x rq_audit, {t_beam / (W * t_aud):.2f} x W x rq_audit; {fmas / 1e12:.3f} T fma -> "
+                f"{fmas / (t_beam * 1e-3) / 1e12:.2f} T fma/s = {100 * fmas / (t_beam * 1e-3) / FMA_PEAK:.1f} % of the fp32 vector peak; "
+                f"beam_err_ratio {ratio:.4f}, changed {int((chosen != greedy).any(1).sum())}, kept greedy "
+                f"{int(info['kept_greedy'].sum())}, collision rate of the chosen tuples {rate1:.6f}")
+            del chosen, info
+        del latent
     _, t_json = timed(lambda: gen.dump_index_json(idx, a.out))
     size = os.path.getsize(a.out)
     extend_lines = []
@@ -286,7 +341,7 @@ def main():
           f"largest {fin['largest_bucket']} items, moved {fin['moved']}, unresolved {fin['unresolved']}")
     print("  kernels: " + ", ".join(f"{k} {v[1]:.2f} ms/{v[0]}" for k, v in sorted(ftrace.items(), key=lambda kv: -kv[1][1])))
     print(f"  collision rate {final['collision_rate']:.6f} -> {finished['collision_rate']:.6f}")
-    for line in spill_lines + audit_lines + decode_lines:
+    for line in spill_lines + audit_lines + decode_lines + beam_lines:
         print(line)
     print(f".index.json ({size / 1e6:.0f} MB)     {t_json * 1e3:9.1f} ms   {a.items / t_json / 1e6:7.2f} M items/s (D2H + text + write)")
     for line in extend_lines:

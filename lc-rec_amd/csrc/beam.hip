@@ -3,13 +3,12 @@
 // lcrec_rq_assign walks the levels greedily: nearest code, subtract, move on.  This pass keeps W partial tuples per item, each with
 // its own residual, scores all W * K children at a level and keeps the W best.  Beyond the reference, which is greedy throughout.
 //
-// The rule (include/lcrec.h, lcrec_rq_beam, is the contract; tests/beam_ref.py restates it in numpy).  One live beam to start with:
-// r = z_i, the empty tuple.  Per level l with P live beams:
-//   s(p, k) = d(r_p, C_l[k]) = (xx + cc_k) - 2*dot_k, xx / cc / dot each one fp32 fma chain over the dimension ascending --
-//             audit.hip's, rq_assign.hip's and finish.hip's bits.  A NaN counts as +inf and is reported as +inf.
+// The rule: rq_walk.h states the quantiser's arithmetic; include/lcrec.h, lcrec_rq_beam, is this pass's contract and
+// tests/beam_ref.py restates it in numpy.  One live beam to start with: r = z_i, the empty tuple.  Per level l with P live beams:
+//   s(p, k) = d(r_p, C_l[k]); a NaN counts as +inf and is reported as +inf
 //   keep      the first min(W, P * K) candidates by (s ascending, p ascending, k ascending): the new beams, in that order
-//   residual  of the new beam from (p, k): t = c - r; s = r + t; r' = r - s on r = r_p, c = C_l[k]
-// and after the last level score = s of the last candidate, err = the fma chain of r_L[j]^2.
+//   residual  of the new beam from (p, k): the residual of r_p behind C_l[k]
+// and after the last level score = s of the last candidate, err = the chain of squares of r_L.
 //
 // Shape: one launch per level.  An item owns W consecutive lanes, one per parent beam, so 256 / W items per workgroup and an item
 // never straddles a wave.  The level's codebook (row stride E + 4 floats) and its cc go to LDS once per workgroup as in audit.hip.
@@ -22,15 +21,13 @@
 // the code row from LDS, takes the three operations and writes its residual and its (parent, code) link; the last level walks the
 // links back to write the tuple.  No atomic, no barrier after the staging.  The grid is the number of workgroups resident at once,
 // a grid-stride loop over blocks of 256 / W items does the rest.
-#include "common.h"
+#include "rq_walk.h"
 
 namespace lcrec {
 
 constexpr int BEAM_THREADS = 256;
-constexpr int BEAM_CUS = 256;
 constexpr int BEAM_MAX_PER_CU = 4;     // the register bound at e = 64 (112 .. 125 VGPRs for W > 1) and at e = 32, W = 8 (101); the
                                        // staged level's LDS may allow fewer.  (e = 64, W = 1: 136 VGPRs, 3 fit and the rest queue.)
-constexpr size_t BEAM_LDS_PER_CU = 160 * 1024;
 constexpr int BEAM_CODE_BITS = 20;     // a link is parent << 20 | code: a level that fits in LDS has far fewer than 2^20 codes
 constexpr int BEAM_NO_ENTRY = 0x7FFFFFFF;
 
@@ -47,35 +44,6 @@ struct BeamParams {
     float *score, *err;      // [n][W], written by the last level
 };
 
-template <int E>
-__device__ __forceinline__ float beam_distance(const float (&x)[E], float xx, const float *crow, float cc)
-{
-    const f32x4 *c4 = reinterpret_cast<const f32x4 *>(crow);
-    float dot = 0.f;
-#pragma unroll
-    for (int q = 0; q < E / 4; ++q) {
-        const f32x4 c = c4[q];
-        dot = __builtin_fmaf(x[4 * q], c[0], dot);
-        dot = __builtin_fmaf(x[4 * q + 1], c[1], dot);
-        dot = __builtin_fmaf(x[4 * q + 2], c[2], dot);
-        dot = __builtin_fmaf(x[4 * q + 3], c[3], dot);
-    }
-    const float t = xx + cc;
-    const float d = t - 2.0f * dot;
-    return d == d ? d : __builtin_inff();   // a NaN counts as +inf
-}
-
-template <int E>
-__device__ __forceinline__ void beam_load_row(float (&x)[E], const float *src)
-{
-    const f32x4 *s = reinterpret_cast<const f32x4 *>(src);
-#pragma unroll
-    for (int q = 0; q < E / 4; ++q) {
-        const f32x4 v = s[q];
-        x[4 * q] = v[0]; x[4 * q + 1] = v[1]; x[4 * q + 2] = v[2]; x[4 * q + 3] = v[3];
-    }
-}
-
 // (score, key) before (score', key'): score ascending, then the key, which is parent << 20 | code, or BEAM_NO_ENTRY behind everything
 __device__ __forceinline__ bool beam_before(float s, int key, float s2, int key2) { return s < s2 || (s == s2 && key < key2); }
 
@@ -89,19 +57,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void rq_beam_level_kernel(BeamParams 
     float *ccs = cbs + (size_t)K * S;                    // [K]
     const int tid = threadIdx.x;
 
-    for (int q = tid; q < K * (E / 4); q += BEAM_THREADS) {
-        const int row = q / (E / 4), g = q % (E / 4);
-        *reinterpret_cast<f32x4 *>(cbs + row * S + 4 * g) = *reinterpret_cast<const f32x4 *>(p.cb + (size_t)row * E + 4 * g);
-    }
-    __syncthreads();
-    for (int k = tid; k < K; k += BEAM_THREADS) {
-        const float *cr = cbs + k * S;
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < E; ++j) a = __builtin_fmaf(cr[j], cr[j], a);
-        ccs[k] = a;
-    }
-    __syncthreads();
+    stage_level<E, S, BEAM_THREADS>(p.cb, K, cbs, ccs);
 
     constexpr int ITEMS = BEAM_THREADS / W;
     const int L = p.L, l = p.l;
@@ -118,12 +74,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void rq_beam_level_kernel(BeamParams 
         for (int j = 0; j < W; ++j) { s[j] = inf; kk[j] = -1; }
         float x[E];
         if (slot < p.P_in) {
-            beam_load_row<E>(x, p.r_in + i * p.in_stride + (int64_t)slot * E);
-            float xx = 0.f;
-#pragma unroll
-            for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
+            load_row<E>(p.r_in + i * p.in_stride + (int64_t)slot * E, x);
+            const float xx = sq_chain<E>(x);
             for (int k = 0; k < K; ++k) {
-                const float d = beam_distance<E>(x, xx, cbs + k * S, ccs[k]);
+                const float d = nan_as_inf(code_distance<E, f32x4>(x, xx, cbs + k * S, ccs[k]));
                 if (d < s[W - 1] || kk[W - 1] < 0) {
 #pragma unroll
                     for (int j = W - 1; j >= 1; --j) {
@@ -178,41 +132,22 @@ __global__ __launch_bounds__(BEAM_THREADS) void rq_beam_level_kernel(BeamParams 
                 p.score[o] = inf;
                 p.err[o] = inf;
                 if (p.r_out) {
-                    f32x4 v;
-                    v[0] = inf; v[1] = inf; v[2] = inf; v[3] = inf;
-                    f32x4 *dst = reinterpret_cast<f32x4 *>(p.r_out + o * E);
 #pragma unroll
-                    for (int q = 0; q < E / 4; ++q) dst[q] = v;
+                    for (int j = 0; j < E; ++j) x[j] = inf;
+                    store_row<E>(p.r_out + o * E, x);
                 }
             }
             continue;
         }
         const int parent = my_key >> BEAM_CODE_BITS, code = my_key & ((1 << BEAM_CODE_BITS) - 1);
-        beam_load_row<E>(x, p.r_in + i * p.in_stride + (int64_t)parent * E);
-        const float *crow = cbs + code * S;
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            const float t = crow[j] - x[j];
-            const float u = x[j] + t;
-            x[j] = x[j] - u;
-        }
-        if (p.r_out) {
-            f32x4 *dst = reinterpret_cast<f32x4 *>(p.r_out + o * E);
-#pragma unroll
-            for (int q = 0; q < E / 4; ++q) {
-                f32x4 v;
-                v[0] = x[4 * q]; v[1] = x[4 * q + 1]; v[2] = x[4 * q + 2]; v[3] = x[4 * q + 3];
-                dst[q] = v;
-            }
-        }
+        load_row<E>(p.r_in + i * p.in_stride + (int64_t)parent * E, x);
+        residual_behind<E>(x, cbs + code * S);
+        if (p.r_out) store_row<E>(p.r_out + o * E, x);
         if (!last) {
             p.links[((int64_t)l * p.n + i) * W + slot] = my_key;
             continue;
         }
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < E; ++j) a = __builtin_fmaf(x[j], x[j], a);
-        p.err[o] = a;
+        p.err[o] = sq_chain<E>(x);
         p.score[o] = my_s;
         p.tuples[o * L + l] = (int64_t)code;
         int at = parent;                                                      // back along the links of the earlier launches
@@ -222,15 +157,6 @@ __global__ __launch_bounds__(BEAM_THREADS) void rq_beam_level_kernel(BeamParams 
             at = link >> BEAM_CODE_BITS;
         }
     }
-}
-
-// include/lcrec.h states these formulas
-static size_t beam_lds_bytes(int K, int e) { return (size_t)K * ((size_t)(e + 4) * 4 + 4); }
-
-static int beam_per_cu(size_t lds)
-{
-    const size_t fit = BEAM_LDS_PER_CU / (lds ? lds : 1);
-    return fit < 1 ? 1 : (fit > (size_t)BEAM_MAX_PER_CU ? BEAM_MAX_PER_CU : (int)fit);
 }
 
 // Two halves of residuals [n][W][e] that the levels alternate between (one for L == 2, none for L == 1), then the links of the
@@ -246,31 +172,10 @@ static bool beam_width_ok(int width) { return width == 1 || width == 2 || width 
 
 size_t rq_beam_workspace(int64_t n, int e, const int *K, int L, int width)
 {
-    if (!K || n < 0 || L < 1 || L > LCREC_MAX_LEVELS || (e != 16 && e != 32 && e != 64) || !beam_width_ok(width)) return 0;
+    if (!K || n < 0 || L < 1 || L > LCREC_MAX_LEVELS || !e_supported(e) || !beam_width_ok(width)) return 0;
     for (int l = 0; l < L; ++l)
         if (K[l] < 1 || !rq_level_fits(K[l], e, L)) return 0;
     return beam_workspace_bytes(n, e, L, width);
-}
-
-template <int E, int W>
-static int beam_launch(const BeamParams &p, int grid, size_t lds, hipStream_t stream)
-{
-    auto kern = rq_beam_level_kernel<E, W>;
-    hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (he != hipSuccess) return fail(LCREC_EHIP, "rq_beam: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(he));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BEAM_THREADS), lds, stream, p);
-    return check_launch("rq_beam_level_kernel");
-}
-
-template <int E>
-static int beam_launch_width(const BeamParams &p, int width, int grid, size_t lds, hipStream_t stream)
-{
-    switch (width) {
-    case 1: return beam_launch<E, 1>(p, grid, lds, stream);
-    case 2: return beam_launch<E, 2>(p, grid, lds, stream);
-    case 4: return beam_launch<E, 4>(p, grid, lds, stream);
-    default: return beam_launch<E, 8>(p, grid, lds, stream);
-    }
 }
 
 int rq_beam(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L, int width, int64_t *tuples_out,
@@ -280,14 +185,13 @@ int rq_beam(const float *z, int64_t n, int e, const float *codebooks, const int 
     if (!K) return fail(LCREC_EINVAL, "%s: K is NULL", who);
     if (L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "%s: L=%d (1 .. %d)", who, L, LCREC_MAX_LEVELS);
     if (n < 0) return fail(LCREC_EINVAL, "%s: n=%lld", who, (long long)n);
-    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EINVAL, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
+    if (!e_supported(e)) return fail(LCREC_EINVAL, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
     if (!beam_width_ok(width)) return fail(LCREC_EINVAL, "%s: width=%d (supported: 1, 2, 4, 8)", who, width);
     for (int l = 0; l < L; ++l)
         if (K[l] < 1) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, l, K[l]);
-    const struct { const void *ptr; const char *name; } required[] = {
-        {z, "z"}, {codebooks, "codebooks"}, {tuples_out, "tuples_out"}, {score_out, "score_out"}, {err_out, "err_out"}};
-    for (const auto &r : required)
-        if (!r.ptr) return fail(LCREC_EINVAL, "%s: %s is NULL", who, r.name);
+    if (int rc = first_null(who, {{z, "z"}, {codebooks, "codebooks"}, {tuples_out, "tuples_out"}, {score_out, "score_out"},
+                                  {err_out, "err_out"}}))
+        return rc;
     if (((uintptr_t)z | (uintptr_t)codebooks | (uintptr_t)resid_out | (uintptr_t)workspace) & 15)
         return fail(LCREC_EINVAL, "%s: z, codebooks, resid_out and workspace must be 16-byte aligned", who);
     if ((uintptr_t)tuples_out & 7) return fail(LCREC_EINVAL, "%s: tuples_out must be 8-byte aligned", who);
@@ -324,13 +228,19 @@ int rq_beam(const float *z, int64_t n, int e, const float *codebooks, const int 
         p.P_out = live;
         p.links = links;
         p.tuples = tuples_out; p.score = score_out; p.err = err_out;
-        const size_t lds = beam_lds_bytes(K[l], e);
-        const int64_t resident = (int64_t)BEAM_CUS * beam_per_cu(lds);
-        const int grid = (int)(blocks < resident ? blocks : resident);
-        int rc;
-        if (e == 16) rc = beam_launch_width<16>(p, width, grid, lds, stream);
-        else if (e == 32) rc = beam_launch_width<32>(p, width, grid, lds, stream);
-        else rc = beam_launch_width<64>(p, width, grid, lds, stream);
+        const size_t lds = level_lds_bytes(K[l], e);
+        const int64_t resident = (int64_t)CUS * resident_per_cu(lds, BEAM_MAX_PER_CU);
+        const unsigned grid = (unsigned)(blocks < resident ? blocks : resident);
+        const int rc = with_e(e, [&](auto ec) {
+            constexpr int E = decltype(ec)::value;
+            auto go = [&](auto kernel) { return launch_with_lds(kernel, grid, BEAM_THREADS, lds, stream, who, "rq_beam_level_kernel", p); };
+            switch (width) {
+            case 1: return go(rq_beam_level_kernel<E, 1>);
+            case 2: return go(rq_beam_level_kernel<E, 2>);
+            case 4: return go(rq_beam_level_kernel<E, 4>);
+            default: return go(rq_beam_level_kernel<E, 8>);
+            }
+        });
         if (rc) return rc;
         cb_off += (int64_t)K[l] * e;
     }

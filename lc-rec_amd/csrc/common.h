@@ -2,6 +2,7 @@
 // gfx950 (MI355X / CDNA4) only: 64-lane wavefronts, fp32 MFMA, 160 KB LDS per CU.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -51,6 +52,52 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // an int as a type: how a dispatch hands a runtime choice to a generic lambda as a template argument
 template <int N>
 struct IntC { static constexpr int value = N; };
+
+// ---- what the launchers of the quantiser's passes share (rq_assign.hip, finish.hip, audit.hip, beam.hip, decode.hip) ----
+constexpr size_t LDS_PER_CU = 160 * 1024;
+constexpr int CUS = 256;              // a grid of resident workgroups covers them; an item loop does the rest
+
+inline bool e_supported(int e) { return e == 16 || e == 32 || e == 64; }
+
+// the one place a supported e becomes a template argument: f(IntC<E>{})
+template <class Fn>
+static auto with_e(int e, Fn &&f) { return e == 16 ? f(IntC<16>{}) : e == 32 ? f(IntC<32>{}) : f(IntC<64>{}); }
+
+// a level staged at row stride e + 4 floats plus its cc (include/lcrec.h states this formula for lcrec_rq_audit and lcrec_rq_beam)
+inline size_t level_lds_bytes(int K, int e) { return (size_t)K * ((size_t)(e + 4) * 4 + 4); }
+
+// workgroups of `lds` bytes that one CU holds at a time: what its LDS allows, at most the kernel's register bound
+inline int resident_per_cu(size_t lds, int register_bound)
+{
+    const size_t fit = LDS_PER_CU / (lds ? lds : 1);
+    return fit < 1 ? 1 : (fit > (size_t)register_bound ? register_bound : (int)fit);
+}
+
+// A kernel with `lds` bytes of dynamic LDS: allow them, launch, check.  A caller that brackets the launch alone, or has work to
+// enqueue between the two, calls allow_lds first and launches itself.
+template <class Kernel>
+static int allow_lds(Kernel kernel, size_t lds, const char *who)
+{
+    hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (he != hipSuccess) return fail(LCREC_EHIP, "%s: hipFuncSetAttribute(%zu B LDS): %s", who, lds, hipGetErrorString(he));
+    return LCREC_OK;
+}
+template <class Kernel, class Params>
+static int launch_with_lds(Kernel kernel, unsigned grid, int threads, size_t lds, hipStream_t stream, const char *who,
+                           const char *kernel_name, const Params &params)
+{
+    if (int rc = allow_lds(kernel, lds, who)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3((unsigned)threads), lds, stream, params);
+    return check_launch(kernel_name);
+}
+
+struct NamedPtr { const void *ptr; const char *name; };
+inline int first_null(const char *who, std::initializer_list<NamedPtr> required)
+{
+    for (const NamedPtr &r : required)
+        if (!r.ptr) return fail(LCREC_EINVAL, "%s: %s is NULL", who, r.name);
+    return LCREC_OK;
+}
 
 }  // namespace lcrec
 

@@ -97,9 +97,7 @@ int rq_decode_gather(const int64_t *idx, int64_t idx_stride, int64_t n, int e, c
         if (l < L) off += (int64_t)K[l] * e;
     }
     TraceScope trace(K_RQ_DECODE_GATHER, stream);
-    if (e == 16) return gather_launch<16>(p, stream);
-    if (e == 32) return gather_launch<32>(p, stream);
-    return gather_launch<64>(p, stream);
+    return with_e(e, [&](auto ec) { return gather_launch<decltype(ec)::value>(p, stream); });
 }
 
 // VEC: w % 4 == 0 and both arrays on 16 bytes: every row starts on 16 bytes

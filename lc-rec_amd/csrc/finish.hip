@@ -5,10 +5,8 @@
 // its tuple with another is given a free code of the LAST level, chosen by the quantiser's own distance.  Nothing above the last
 // level moves, and no item that collides with nobody moves.
 //
-// The rule (include/lcrec.h, lcrec_finish_nearest_free, is the contract; tests/finish_ref.py restates it in numpy):
-//   d(i,k) = (xx_i + cc_k) - 2*dot(i,k), xx / cc / dot each one fp32 fma chain over the dimension ascending -- rq_assign.hip's
-//   bits, oracle/lcrec_oracle.c's lcrec_oracle_distances.  Wherever distances are compared a NaN counts as +inf, so it never
-//   beats anything (rq_assign's `d < best` from best = +inf).
+// The rule: rq_walk.h states the quantiser's arithmetic (the distance d, a NaN as +inf, ties); include/lcrec.h,
+// lcrec_finish_nearest_free, is this pass's contract and tests/finish_ref.py restates it in numpy:
 //   bucket   = the items sharing idx[:, :L-1]; the caller lists the buckets as (members, offsets), ids ascending in a bucket
 //   keepers  : for every last code held by >= 2 items of the bucket the holder with the smallest d keeps it (tie: lowest id);
 //              the other holders are movers
@@ -24,9 +22,7 @@
 //      LDS step across the four waves pick (distance, lowest code); the code's owner thread marks it occupied.
 // The mover loop stops evaluating when the free count reaches zero -- the rest is counted -- so no bucket takes more than K
 // sequential steps whatever its size.  Nothing crosses workgroups: no flag, no spin; the only global atomics are the two counters.
-#include "common.h"
-
-#include <type_traits>
+#include "rq_walk.h"
 
 namespace lcrec {
 
@@ -48,36 +44,6 @@ struct ExtendParams : FinishParams {
     int64_t n_frozen;
 };
 
-// unsigned order of the result == float order of d; NaN -> +inf, -0 -> +0
-__device__ __forceinline__ uint32_t ordered_bits(float d)
-{
-    if (!(d == d)) d = __builtin_inff();
-    if (d == 0.f) d = 0.f;
-    const uint32_t u = __float_as_uint(d);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-template <int E>
-__device__ __forceinline__ void load_row(const float *__restrict__ src, float (&x)[E])
-{
-    const f32x4 *s = reinterpret_cast<const f32x4 *>(src);
-#pragma unroll
-    for (int q = 0; q < E / 4; ++q) {
-        const f32x4 v = s[q];
-        x[4 * q] = v[0]; x[4 * q + 1] = v[1]; x[4 * q + 2] = v[2]; x[4 * q + 3] = v[3];
-    }
-}
-
-template <int E>
-__device__ __forceinline__ float distance(const float (&x)[E], float xx, const float *crow, float cc)
-{
-    float dot = 0.f;
-#pragma unroll
-    for (int k = 0; k < E; ++k) dot = __builtin_fmaf(x[k], crow[k], dot);
-    const float t = xx + cc;
-    return t - 2.0f * dot;
-}
-
 // FROZEN = false is lcrec_finish_nearest_free (every `if constexpr (FROZEN)` drops out); FROZEN = true adds the frozen holders of
 // lcrec_extend_nearest_free: fro[k] counts them per code, a code with one has no keeper, and no row of a frozen id is ever read.
 template <int E, bool FROZEN>
@@ -91,7 +57,6 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(std::c
     float *ccs = cbs + (size_t)K * S;                                             // [K]
     int *cnt = reinterpret_cast<int *>(ccs + K);                                  // [K] holders, then 1 for a code a mover took
     int *fro = cnt + K;                                                           // [K] frozen holders (FROZEN only: not allocated otherwise)
-    __shared__ unsigned long long wmask[FIN_WAVES];
     __shared__ float red_d[2][FIN_WAVES];
     __shared__ int red_k[2][FIN_WAVES];
     __shared__ int sum_sh[FIN_WAVES];
@@ -139,29 +104,16 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(std::c
     }
     if (!__syncthreads_or(twice)) return;                                         // untouched bucket (the whole workgroup leaves)
 
-    // ---- 2. codebook and cc
-    for (int q = tid; q < K * (E / 4); q += FIN_THREADS) {
-        const int row = q / (E / 4), g = q % (E / 4);
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(p.cb + (size_t)row * E + 4 * g);
-        float *dst = cbs + row * S + 4 * g;
-        dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
-    }
+    // ---- 2. codebook and cc; the count of the free codes rides on the staging's first barrier
+    stage_level<E, S, FIN_THREADS>(p.cb, K, cbs, ccs, [&] {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) used += __shfl_xor(used, o, 64);
-    if (lane == 0) sum_sh[wave] = used;
-    __syncthreads();
+        for (int o = 32; o > 0; o >>= 1) used += __shfl_xor(used, o, 64);
+        if (lane == 0) sum_sh[wave] = used;
+    });
     int free_codes = K;
 #pragma unroll
     for (int w = 0; w < FIN_WAVES; ++w) free_codes -= sum_sh[w];
     free_codes = __builtin_amdgcn_readfirstlane(free_codes);                      // (the same in every lane: say so, for scalar branches)
-    for (int k = tid; k < K; k += FIN_THREADS) {
-        const float *cr = cbs + k * S;
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < E; ++j) a = __builtin_fmaf(cr[j], cr[j], a);
-        ccs[k] = a;
-    }
-    __syncthreads();
 
     // ---- 3. keepers
     for (int64_t pos = tid; pos < m; pos += FIN_THREADS) {
@@ -171,117 +123,39 @@ __global__ __launch_bounds__(FIN_THREADS) void finish_nearest_free_kernel(std::c
         if constexpr (FROZEN) { if (fro[c] > 0 || id < nf) continue; }           // a frozen holder keeps the code: no keeper among the new
         float x[E];
         load_row<E>(p.resid + (id - nf) * E, x);
-        float xx = 0.f;
-#pragma unroll
-        for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
-        const float d = distance<E>(x, xx, cbs + c * S, ccs[c]);
+        const float d = code_distance<E, float>(x, sq_chain<E>(x), cbs + c * S, ccs[c]);
         atomicMin(&key[c], ((unsigned long long)ordered_bits(d) << 32) | (unsigned long long)(uint32_t)pos);
     }
     __syncthreads();
 
-    // ---- 4. movers, in position (= id) order, a chunk of 256 positions at a time
-    // free_codes, moved, late and step are the same in every thread: each derives them from the same LDS values.
-    unsigned long long moved = 0, late = 0;   // late: movers met after the last free code went, counted one by one
-    unsigned my_late = 0;                      // ... and those of whole chunks after that, counted in parallel
+    // ---- 4. movers, in position (= id) order: thread t evaluates the free codes t, t + 256, ...; the code's owner marks it occupied
     unsigned step = 0;
-    for (int64_t base = 0; base < m; base += FIN_THREADS) {
-        const int64_t pos = base + tid;
-        bool mover = false;
-        if (pos < m) {
+    movers_walk<FIN_THREADS>(
+        m, free_codes,
+        [&](int64_t pos) -> bool {
             int64_t id;
             const int c = code_of(pos, id);
-            if constexpr (FROZEN) mover = c >= 0 && id >= nf && cnt[c] >= 2 && (fro[c] > 0 || (uint32_t)key[c] != (uint32_t)pos);
-            else mover = c >= 0 && cnt[c] >= 2 && (uint32_t)key[c] != (uint32_t)pos;
-        }
-        if (free_codes == 0) { my_late += mover; continue; }
-        const unsigned long long mine = __ballot(mover);
-        if (lane == 0) wmask[wave] = mine;
-        __syncthreads();
-        unsigned long long masks[FIN_WAVES];
-#pragma unroll
-        for (int w = 0; w < FIN_WAVES; ++w) {
-            const unsigned long long v = wmask[w];
-            masks[w] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
-                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);   // (it returns int)
-        }
-#pragma unroll
-        for (int w = 0; w < FIN_WAVES; ++w) {
-            unsigned long long mask = masks[w];
-            while (mask) {
-                if (free_codes == 0) { late += __builtin_popcountll(mask); break; }
-                const int bit = __builtin_ctzll(mask);
-                mask &= mask - 1;
-                const int64_t id = mem[base + w * 64 + bit];                      // in range: it was found a mover above
-                float x[E];
-                load_row<E>(p.resid + (id - nf) * E, x);                          // a mover is never frozen: id >= nf
-                float xx = 0.f;
-#pragma unroll
-                for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
-                float best = __builtin_inff();
-                int bk = 0x7fffffff;
-                for (int k = tid; k < K; k += FIN_THREADS) {
-                    if (cnt[k] != 0) continue;
-                    float d = distance<E>(x, xx, cbs + k * S, ccs[k]);
-                    if (!(d == d)) d = __builtin_inff();
-                    if (bk == 0x7fffffff || d < best) { best = d; bk = k; }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const float od = __shfl_xor(best, o, 64);
-                    const int ok = __shfl_xor(bk, o, 64);
-                    if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
-                }
-                const int par = step & 1;   // two hand-over buffers: a wave can be one step ahead of another, never two
-                ++step;
-                if (lane == 0) { red_d[par][wave] = best; red_k[par][wave] = bk; }
-                __syncthreads();
-                best = red_d[par][0]; bk = red_k[par][0];
-#pragma unroll
-                for (int v = 1; v < FIN_WAVES; ++v) {
-                    const float od = red_d[par][v];
-                    const int ok = red_k[par][v];
-                    if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
-                }
-                bk = __builtin_amdgcn_readfirstlane(bk);
-                // free_codes > 0, so bk is a code; its owner is the only thread that reads cnt[bk] in this loop
-                if (tid == (bk & (FIN_THREADS - 1))) {
-                    cnt[bk] = 1;
-                    p.idx[id * L + (L - 1)] = (int64_t)bk;
-                }
-                ++moved;
-                --free_codes;
+            if constexpr (FROZEN) return c >= 0 && id >= nf && cnt[c] >= 2 && (fro[c] > 0 || (uint32_t)key[c] != (uint32_t)pos);
+            else return c >= 0 && cnt[c] >= 2 && (uint32_t)key[c] != (uint32_t)pos;
+        },
+        [&](int64_t pos) {
+            const int64_t id = mem[pos];                                          // in range: it was found a mover
+            float x[E];
+            load_row<E>(p.resid + (id - nf) * E, x);                              // a mover is never frozen: id >= nf
+            const int bk = wg_nearest_free<E, S, FIN_THREADS>(x, sq_chain<E>(x), cbs, ccs, K, [&](int k) { return cnt[k] == 0; }, red_d,
+                                                              red_k, step, lane, wave);
+            // a code was free, so bk is one; its owner is the only thread that reads cnt[bk] in this walk
+            if (tid == (bk & (FIN_THREADS - 1))) {
+                cnt[bk] = 1;
+                p.idx[id * L + (L - 1)] = (int64_t)bk;
             }
-        }
-        __syncthreads();   // wmask is rewritten by the next chunk
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) my_late += __shfl_xor(my_late, o, 64);
-    __syncthreads();
-    if (lane == 0) sum_sh[wave] = (int)my_late;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 0; w < FIN_WAVES; ++w) late += (unsigned)sum_sh[w];
-        if (moved) atomicAdd(&p.counters[0], moved);
-        if (late) atomicAdd(&p.counters[1], late);
-    }
+        },
+        sum_sh, p.counters);
 }
 
 static size_t finish_lds_bytes(int K, int e, bool frozen)
 {
     return (size_t)K * (8 + (size_t)(e + 1) * 4 + 4 + 4 + (frozen ? 4 : 0));   // key, codebook row, cc, cnt, (fro)
-}
-
-template <int E, bool FROZEN>
-static int finish_launch(const ExtendParams &p, int64_t n_buckets, size_t lds, hipStream_t stream)
-{
-    const char *who = FROZEN ? "extend_nearest_free" : "finish_nearest_free";
-    auto kern = finish_nearest_free_kernel<E, FROZEN>;
-    hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (he != hipSuccess)
-        return fail(LCREC_EHIP, "%s: hipFuncSetAttribute(%zu B LDS): %s", who, lds, hipGetErrorString(he));
-    TraceScope trace(FROZEN ? K_EXTEND : K_FINISH, stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_buckets), dim3(FIN_THREADS), lds, stream, p);   // (FROZEN = false: sliced to FinishParams)
-    return check_launch(FROZEN ? "extend_nearest_free_kernel" : "finish_nearest_free_kernel");
 }
 
 // Both entries: `frozen` selects lcrec_extend_nearest_free's checks, texts, LDS need and kernel.
@@ -298,11 +172,11 @@ static int nearest_free(bool frozen, int64_t *idx, int64_t n, int64_t n_frozen, 
         return fail(LCREC_EINVAL, "%s: n_frozen=%lld (0 .. n=%lld)", who, (long long)n_frozen, (long long)n);
     if (n_buckets < 0 || n_buckets > 0x7fffffffLL)
         return fail(LCREC_EINVAL, "%s: n_buckets=%lld (0 .. 2^31 - 1)", who, (long long)n_buckets);
-    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
+    if (!e_supported(e)) return fail(LCREC_EUNSUPPORTED, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
     const int Kl = K[L - 1];
     if (Kl <= 0) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, L - 1, Kl);
     const size_t lds = finish_lds_bytes(Kl, e, frozen);
-    if (!rq_level_fits(Kl, e, L) || lds + 512 > 160 * 1024) {
+    if (!rq_level_fits(Kl, e, L) || lds + 512 > LDS_PER_CU) {
         if (frozen)
             return fail(LCREC_EUNSUPPORTED, "%s: level %d (K=%d, e=%d) does not fit in 160 KB of LDS with the frozen-holder counts "
                         "(%zu B: 4 more per code than finish_nearest_free)", who, L - 1, Kl, e, lds);
@@ -326,14 +200,17 @@ static int nearest_free(bool frozen, int64_t *idx, int64_t n, int64_t n_frozen, 
     p.members = bucket_members; p.offsets = bucket_offsets;
     p.counters = reinterpret_cast<unsigned long long *>(counters_out);
     p.n_frozen = n_frozen;
-    if (frozen) {
-        if (e == 16) return finish_launch<16, true>(p, n_buckets, lds, stream);
-        if (e == 32) return finish_launch<32, true>(p, n_buckets, lds, stream);
-        return finish_launch<64, true>(p, n_buckets, lds, stream);
-    }
-    if (e == 16) return finish_launch<16, false>(p, n_buckets, lds, stream);
-    if (e == 32) return finish_launch<32, false>(p, n_buckets, lds, stream);
-    return finish_launch<64, false>(p, n_buckets, lds, stream);
+    return with_e(e, [&](auto ec) {
+        constexpr int E = decltype(ec)::value;
+        auto launch = [&](auto kernel, int trace_id, const char *kernel_name) {
+            if (int rc = allow_lds(kernel, lds, who)) return rc;
+            TraceScope trace(trace_id, stream);                                   // (the launch alone)
+            hipLaunchKernelGGL(kernel, dim3((unsigned)n_buckets), dim3(FIN_THREADS), lds, stream, p);
+            return check_launch(kernel_name);
+        };
+        if (frozen) return launch(finish_nearest_free_kernel<E, true>, K_EXTEND, "extend_nearest_free_kernel");
+        return launch(finish_nearest_free_kernel<E, false>, K_FINISH, "finish_nearest_free_kernel");   // (p sliced to FinishParams)
+    });
 }
 
 int finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, const float *resid_last, int e, const float *codebook_last,
@@ -361,8 +238,8 @@ int extend_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const 
 //   movers       : of every full tuple held by >= 2 items -- a frozen holder: every new holder; else all new holders but the one
 //                  nearest to the shared last code (tie: lowest id)
 //   super-bucket : the items sharing idx[:, :L-2]; cell (a, k) is occupied when any of them holds it
-//   serving      : movers in ascending id; a' = nearest code (r2, C2) among the rows with a free cell, r' = r2 after C2[a'] by the
-//                  quantiser's three-op update, k = nearest free cell of row a' (r', C1); no free cell anywhere: unresolved
+//   serving      : movers in ascending id; a' = nearest code (r2, C2) among the rows with a free cell, r' = the residual of r2
+//                  behind C2[a'], k = nearest free cell of row a' (r', C1); no free cell anywhere: unresolved
 //
 // Two kernels.
 //   1. spill_keepers_kernel: one wave per shared tuple (a handful of items): the holders are counted, the keeper is a wave
@@ -422,13 +299,14 @@ __global__ __launch_bounds__(FIN_THREADS) void spill_keepers_kernel(SpillParams 
             int64_t id;
             const int c = holder(pos, id);
             if (c < 0) continue;
+            const float *cr = p.cb1 + (size_t)c * E;
             float x[E];
             load_row<E>(p.r1 + (id - nf) * E, x);
-            const float *cr = p.cb1 + (size_t)c * E;
+            // sq_chain's two chains in one loop: taken one after the other they cost the e = 32 form two more VGPRs
             float xx = 0.f, cc = 0.f;
 #pragma unroll
             for (int j = 0; j < E; ++j) { xx = __builtin_fmaf(x[j], x[j], xx); cc = __builtin_fmaf(cr[j], cr[j], cc); }
-            const uint32_t d = ordered_bits(distance<E>(x, xx, cr, cc));
+            const uint32_t d = ordered_bits(code_distance<E, float>(x, xx, cr, cc));
             if (d < kd || (d == kd && (uint32_t)id < ki)) { kd = d; ki = (uint32_t)id; }
         }
 #pragma unroll
@@ -444,30 +322,6 @@ __global__ __launch_bounds__(FIN_THREADS) void spill_keepers_kernel(SpillParams 
     }
 }
 
-// (best, bk) of the whole workgroup, the same in every thread: smallest distance, lowest code on a tie; bk = 0x7fffffff: no candidate
-__device__ __forceinline__ int spill_argmin(float best, int bk, float (*red_d)[FIN_WAVES], int (*red_k)[FIN_WAVES], unsigned &step,
-                                            int lane, int wave)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float od = __shfl_xor(best, o, 64);
-        const int ok = __shfl_xor(bk, o, 64);
-        if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
-    }
-    const int par = step & 1;   // two hand-over buffers: a wave can be one reduction ahead of another, never two
-    ++step;
-    if (lane == 0) { red_d[par][wave] = best; red_k[par][wave] = bk; }
-    __syncthreads();
-    best = red_d[par][0]; bk = red_k[par][0];
-#pragma unroll
-    for (int v = 1; v < FIN_WAVES; ++v) {
-        const float od = red_d[par][v];
-        const int ok = red_k[par][v];
-        if (od < best || (od == best && ok < bk)) { best = od; bk = ok; }
-    }
-    return __builtin_amdgcn_readfirstlane(bk);
-}
-
 template <int E>
 __global__ __launch_bounds__(FIN_THREADS) void spill_movers_kernel(SpillParams p)
 {
@@ -480,7 +334,6 @@ __global__ __launch_bounds__(FIN_THREADS) void spill_movers_kernel(SpillParams p
     float *cc1s = cc2s + K2;                                                      // [K1]
     uint32_t *occ = reinterpret_cast<uint32_t *>(cc1s + K1);                      // [K2][W] bit k & 31 of word k >> 5: cell (a, k)
     int *fre = reinterpret_cast<int *>(occ + (size_t)K2 * W);                     // [K2] free cells of the row
-    __shared__ unsigned long long wmask[FIN_WAVES];
     __shared__ float red_d[2][FIN_WAVES];
     __shared__ int red_k[2][FIN_WAVES];
     __shared__ int sum_sh[FIN_WAVES];
@@ -504,23 +357,12 @@ __global__ __launch_bounds__(FIN_THREADS) void spill_movers_kernel(SpillParams p
     if (!__syncthreads_or(any)) return;
 
     // ---- 2. codebooks, cc, and the occupied cells
-    for (int q = tid; q < (K2 + K1) * (E / 4); q += FIN_THREADS) {
-        const int row = q / (E / 4), g = q % (E / 4);
-        const float *src = row < K2 ? p.cb2 + (size_t)row * E : p.cb1 + (size_t)(row - K2) * E;
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(src + 4 * g);
-        float *dst = cb2s + row * S + 4 * g;                                      // (cb1s follows cb2s: one array of K2 + K1 rows)
-        dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
-    }
+    stage_rows<E, S, FIN_THREADS>(p.cb2, K2, cb2s);
+    stage_rows<E, S, FIN_THREADS>(p.cb1, K1, cb1s);
     for (int q = tid; q < K2 * W; q += FIN_THREADS)
         occ[q] = ((q % W) == W - 1 && (K1 & 31)) ? ~0u << (K1 & 31) : 0u;        // cells past K1 never become free
     __syncthreads();
-    for (int k = tid; k < K2 + K1; k += FIN_THREADS) {
-        const float *cr = cb2s + k * S;
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < E; ++j) a = __builtin_fmaf(cr[j], cr[j], a);
-        cc2s[k] = a;                                                              // (cc1s follows cc2s)
-    }
+    stage_cc<E, S, FIN_THREADS>(cb2s, K2 + K1, cc2s);                             // (cb1s follows cb2s, cc1s follows cc2s)
     for (int64_t pos = tid; pos < m; pos += FIN_THREADS) {
         const int64_t id = mem[pos];
         if (id < 0 || id >= p.n) continue;
@@ -544,92 +386,31 @@ __global__ __launch_bounds__(FIN_THREADS) void spill_movers_kernel(SpillParams p
 #pragma unroll
     for (int w = 0; w < FIN_WAVES; ++w) free_cells += sum_sh[w];
 
-    // ---- 3. movers, in position (= id) order, a chunk of 256 positions at a time
-    // free_cells, moved, late and step are the same in every thread: each derives them from the same LDS values.
-    unsigned long long moved = 0, late = 0;
-    unsigned my_late = 0;
+    // ---- 3. movers, in position (= id) order
     unsigned step = 0;
-    for (int64_t base = 0; base < m; base += FIN_THREADS) {
-        const int64_t pos = base + tid;
-        const bool mover = pos < m && is_mover(pos);
-        if (free_cells == 0) { my_late += mover; continue; }
-        const unsigned long long own = __ballot(mover);
-        if (lane == 0) wmask[wave] = own;
-        __syncthreads();
-        unsigned long long masks[FIN_WAVES];
-#pragma unroll
-        for (int w = 0; w < FIN_WAVES; ++w) {
-            const unsigned long long v = wmask[w];
-            masks[w] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
-                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
-        }
-#pragma unroll
-        for (int w = 0; w < FIN_WAVES; ++w) {
-            unsigned long long mask = masks[w];
-            while (mask) {
-                if (free_cells == 0) { late += __builtin_popcountll(mask); break; }
-                const int bit = __builtin_ctzll(mask);
-                mask &= mask - 1;
-                const int64_t id = mem[base + w * 64 + bit];                      // in range and new: it was found a mover above
-                float x[E];
-                load_row<E>(p.r2 + (id - nf) * E, x);
-                float xx = 0.f;
-#pragma unroll
-                for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
-                // round 1: the nearest code of level L-2 among the rows with a free cell
-                float best = __builtin_inff();
-                int ba = 0x7fffffff;
-                for (int a = tid; a < K2; a += FIN_THREADS) {
-                    if (fre[a] <= 0) continue;
-                    float d = distance<E>(x, xx, cb2s + a * S, cc2s[a]);
-                    if (!(d == d)) d = __builtin_inff();
-                    if (ba == 0x7fffffff || d < best) { best = d; ba = a; }
-                }
-                ba = spill_argmin(best, ba, red_d, red_k, step, lane, wave);      // free_cells > 0, so ba is a row
-                // the residual entering the last level behind code ba: t = c - r; s = r + t; r' = r - s
-                const float *c2 = cb2s + ba * S;
-                xx = 0.f;
-#pragma unroll
-                for (int j = 0; j < E; ++j) {
-                    const float t = c2[j] - x[j];
-                    const float s = x[j] + t;
-                    x[j] = x[j] - s;
-                }
-#pragma unroll
-                for (int j = 0; j < E; ++j) xx = __builtin_fmaf(x[j], x[j], xx);
-                // round 2: the nearest free cell of that row
-                best = __builtin_inff();
-                int bk = 0x7fffffff;
-                const uint32_t *row = occ + ba * W;
-                for (int k = tid; k < K1; k += FIN_THREADS) {
-                    if ((row[k >> 5] >> (k & 31)) & 1u) continue;
-                    float d = distance<E>(x, xx, cb1s + k * S, cc1s[k]);
-                    if (!(d == d)) d = __builtin_inff();
-                    if (bk == 0x7fffffff || d < best) { best = d; bk = k; }
-                }
-                bk = spill_argmin(best, bk, red_d, red_k, step, lane, wave);      // fre[ba] > 0, so bk is a cell
-                if (tid == (bk & (FIN_THREADS - 1))) {
-                    atomicOr(&occ[ba * W + (bk >> 5)], 1u << (bk & 31));
-                    p.idx[id * L + (L - 2)] = (int64_t)ba;
-                    p.idx[id * L + (L - 1)] = (int64_t)bk;
-                }
-                if (tid == (ba & (FIN_THREADS - 1))) fre[ba] -= 1;                // its owner: the only thread that reads it
-                ++moved;
-                --free_cells;
+    movers_walk<FIN_THREADS>(
+        m, free_cells, is_mover,
+        [&](int64_t pos) {
+            const int64_t id = mem[pos];                                          // in range and new: it was found a mover
+            float x[E];
+            load_row<E>(p.r2 + (id - nf) * E, x);
+            // round 1: the nearest code of level L-2 among the rows with a free cell (there is a free cell, so ba is a row)
+            const int ba = wg_nearest_free<E, S, FIN_THREADS>(x, sq_chain<E>(x), cb2s, cc2s, K2, [&](int a) { return fre[a] > 0; }, red_d,
+                                                              red_k, step, lane, wave);
+            residual_behind<E>(x, cb2s + ba * S);
+            // round 2: the nearest free cell of that row (fre[ba] > 0, so bk is a cell)
+            const uint32_t *row = occ + ba * W;
+            const int bk = wg_nearest_free<E, S, FIN_THREADS>(x, sq_chain<E>(x), cb1s, cc1s, K1,
+                                                              [&](int k) { return !((row[k >> 5] >> (k & 31)) & 1u); }, red_d, red_k, step,
+                                                              lane, wave);
+            if (tid == (bk & (FIN_THREADS - 1))) {
+                atomicOr(&occ[ba * W + (bk >> 5)], 1u << (bk & 31));
+                p.idx[id * L + (L - 2)] = (int64_t)ba;
+                p.idx[id * L + (L - 1)] = (int64_t)bk;
             }
-        }
-        __syncthreads();   // wmask is rewritten by the next chunk
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) my_late += __shfl_xor(my_late, o, 64);
-    __syncthreads();
-    if (lane == 0) sum_sh[wave] = (int)my_late;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 0; w < FIN_WAVES; ++w) late += (unsigned)sum_sh[w];
-        if (moved) atomicAdd(&p.counters[0], moved);
-        if (late) atomicAdd(&p.counters[1], late);
-    }
+            if (tid == (ba & (FIN_THREADS - 1))) fre[ba] -= 1;                    // its owner: the only thread that reads it
+        },
+        sum_sh, p.counters);
 }
 
 // include/lcrec.h states this formula
@@ -640,27 +421,6 @@ static size_t spill_lds_bytes(int K2, int K1, int e)
 }
 
 size_t spill_workspace(int64_t n) { return align_up((size_t)(n > 0 ? n : 1), 256); }
-
-template <int E>
-static int spill_launch(const SpillParams &p, int64_t n_tuples, int64_t n_supers, size_t lds, hipStream_t stream)
-{
-    auto kern = spill_movers_kernel<E>;
-    hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (he != hipSuccess)
-        return fail(LCREC_EHIP, "spill_nearest_free: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(he));
-    he = hipMemsetAsync(p.flag, 0, (size_t)p.n, stream);
-    if (he != hipSuccess) return fail(LCREC_EHIP, "spill_nearest_free: %s", hipGetErrorString(he));
-    {
-        TraceScope trace(K_SPILL_KEEPERS, stream);
-        const int64_t blocks = (n_tuples + FIN_WAVES - 1) / FIN_WAVES;
-        hipLaunchKernelGGL(spill_keepers_kernel<E>, dim3((unsigned)blocks), dim3(FIN_THREADS), 0, stream, p, n_tuples);
-        const int rc = check_launch("spill_keepers_kernel");
-        if (rc != LCREC_OK) return rc;
-    }
-    TraceScope trace(K_SPILL, stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_supers), dim3(FIN_THREADS), lds, stream, p);
-    return check_launch("spill_movers_kernel");
-}
 
 int spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const float *resid_prev, const float *resid_last,
                        int e, const float *codebook_prev, const float *codebook_last, const int64_t *tuple_members,
@@ -679,12 +439,12 @@ int spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const i
         return fail(LCREC_EINVAL, "%s: n_tuple_groups=%lld (0 .. 2^31 - 1)", who, (long long)n_tuples);
     if (n_supers < 0 || n_supers > 0x7fffffffLL)
         return fail(LCREC_EINVAL, "%s: n_super_buckets=%lld (0 .. 2^31 - 1)", who, (long long)n_supers);
-    if (e != 16 && e != 32 && e != 64) return fail(LCREC_EUNSUPPORTED, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
+    if (!e_supported(e)) return fail(LCREC_EUNSUPPORTED, "%s: e_dim=%d (supported: 16, 32, 64)", who, e);
     const int K2 = K[L - 2], K1 = K[L - 1];
     if (K2 <= 0) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, L - 2, K2);
     if (K1 <= 0) return fail(LCREC_EINVAL, "%s: K[%d]=%d", who, L - 1, K1);
     const size_t lds = spill_lds_bytes(K2, K1, e);
-    if (lds + 512 > 160 * 1024)
+    if (lds + 512 > LDS_PER_CU)
         return fail(LCREC_EUNSUPPORTED, "%s: levels %d and %d (K=%d and K=%d, e=%d) need %zu B of LDS together: more than 160 KB", who,
                     L - 2, L - 1, K2, K1, e, lds + 512);
     if (((uintptr_t)resid_prev | (uintptr_t)resid_last | (uintptr_t)codebook_prev | (uintptr_t)codebook_last) & 15)
@@ -710,9 +470,22 @@ int spill_nearest_free(int64_t *idx, int64_t n, int64_t n_frozen, int L, const i
     p.tmem = tuple_members; p.toff = tuple_offsets; p.smem = super_members; p.soff = super_offsets;
     p.flag = static_cast<unsigned char *>(workspace);
     p.counters = reinterpret_cast<unsigned long long *>(counters_out);
-    if (e == 16) return spill_launch<16>(p, n_tuples, n_supers, lds, stream);
-    if (e == 32) return spill_launch<32>(p, n_tuples, n_supers, lds, stream);
-    return spill_launch<64>(p, n_tuples, n_supers, lds, stream);
+    return with_e(e, [&](auto ec) {
+        constexpr int E = decltype(ec)::value;
+        if (int rc = allow_lds(spill_movers_kernel<E>, lds, who)) return rc;
+        const hipError_t hm = hipMemsetAsync(p.flag, 0, (size_t)n, stream);
+        if (hm != hipSuccess) return fail(LCREC_EHIP, "%s: %s", who, hipGetErrorString(hm));
+        {
+            TraceScope trace(K_SPILL_KEEPERS, stream);
+            const int64_t blocks = (n_tuples + FIN_WAVES - 1) / FIN_WAVES;
+            hipLaunchKernelGGL(spill_keepers_kernel<E>, dim3((unsigned)blocks), dim3(FIN_THREADS), 0, stream, p, n_tuples);
+            const int rc = check_launch("spill_keepers_kernel");
+            if (rc != LCREC_OK) return rc;
+        }
+        TraceScope trace(K_SPILL, stream);
+        hipLaunchKernelGGL(spill_movers_kernel<E>, dim3((unsigned)n_supers), dim3(FIN_THREADS), lds, stream, p);
+        return check_launch("spill_movers_kernel");
+    });
 }
 
 }  // namespace lcrec

@@ -412,7 +412,6 @@ __global__ void rq_sse_finalize_kernel(const double *partial, int blocks, int L,
 
 // ---------------------------------------------------------------- host side
 
-constexpr size_t LDS_BUDGET = 160 * 1024;
 constexpr int MAX_GRID = 256;   // one persistent workgroup per CU
 
 static size_t lds_bytes(int rows, int E, int L, int waves, bool split = false)
@@ -421,7 +420,7 @@ static size_t lds_bytes(int rows, int E, int L, int waves, bool split = false)
            (split ? (size_t)2 * waves * 64 * 3 * sizeof(float) : 0);      // the split form's hand-over buffers
 }
 
-bool rq_level_fits(int K, int e, int L) { return K > 0 && lds_bytes((K + 31) & ~31, e, L, 4) <= LDS_BUDGET; }
+bool rq_level_fits(int K, int e, int L) { return K > 0 && lds_bytes((K + 31) & ~31, e, L, 4) <= LDS_PER_CU; }
 
 static int threads_for(int e, int64_t n)
 {
@@ -515,7 +514,7 @@ static int rq_plan(int64_t n, int e, const int *K, int L, const RqKnobs &kn, con
     for (int l = 0; l < L; ++l) max_k = K[l] > max_k ? K[l] : max_k;
     bool split = kn.allow_split && tiles <= kn.split_tiles && max_k >= 128;
     for (int l = 0; split && l < L; ++l)       // (its hand-over buffers must not push a level out of LDS that fits without them)
-        if (K[l] > 0 && lds_bytes((K[l] + 31) & ~31, e, L, 4, true) > LDS_BUDGET) split = false;
+        if (K[l] > 0 && lds_bytes((K[l] + 31) & ~31, e, L, 4, true) > LDS_PER_CU) split = false;
     if (f.split >= 0) split = f.split != 0;
     int threads = split ? 256 : threads_for(e, n);
     if (f.threads) {
@@ -526,8 +525,8 @@ static int rq_plan(int64_t n, int e, const int *K, int L, const RqKnobs &kn, con
     const int waves = threads / 64;
     for (int l = 0; l < L; ++l) {
         if (K[l] <= 0) return fail(LCREC_EINVAL, "rq_assign: K[%d]=%d", l, K[l]);
-        if (lds_bytes((K[l] + 31) & ~31, e, L, waves, split) > LDS_BUDGET) {
-            if (split && lds_bytes((K[l] + 31) & ~31, e, L, waves, false) <= LDS_BUDGET)
+        if (lds_bytes((K[l] + 31) & ~31, e, L, waves, split) > LDS_PER_CU) {
+            if (split && lds_bytes((K[l] + 31) & ~31, e, L, waves, false) <= LDS_PER_CU)
                 return fail(LCREC_EUNSUPPORTED, "rq_assign: the split form cannot take level %d (K=%d, e=%d): its hand-over buffers push it "
                             "out of 160 KB of LDS", l, K[l], e);
             return fail(LCREC_EUNSUPPORTED, "rq_assign: level %d (K=%d, e=%d) does not fit in 160 KB of LDS", l, K[l], e);
@@ -552,7 +551,7 @@ static int rq_plan(int64_t n, int e, const int *K, int L, const RqKnobs &kn, con
     bool odd_run = false;
     for (int l0 = 0; l0 < L;) {
         int rows = 0, l1 = l0;
-        while (l1 < L && lds_bytes(rows + ((K[l1] + 31) & ~31), e, L, waves, split) <= LDS_BUDGET) {
+        while (l1 < L && lds_bytes(rows + ((K[l1] + 31) & ~31), e, L, waves, split) <= LDS_PER_CU) {
             o->row_off[l1] = rows;
             rows += (K[l1] + 31) & ~31;
             ++l1;

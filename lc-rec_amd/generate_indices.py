@@ -202,6 +202,18 @@ def resolve_collisions(model, idx, resid_last, ks, max_rounds=MAX_ROUNDS, on_rou
     return idx, history
 
 
+def _prefix_groups(idx, ks, depth):
+    """The buckets of items sharing idx[:, :depth], in collision_groups' "device" layout: (members, offsets, count, largest).
+    depth == 0 is one bucket of all items (none when there are no items)."""
+    n = idx.shape[0]
+    if depth == 0:
+        members = torch.arange(n, dtype=torch.int64, device=idx.device)
+        offsets = torch.tensor([0, n] if n else [0], dtype=torch.int64, device=idx.device)
+        return members, offsets, (1 if n else 0), n
+    found = ops.collision_groups(idx[:, :depth].contiguous(), ks[:depth], want_groups="device")
+    return found["members"], found["offsets"], found["n_groups"], found["max_count"] if found["n_groups"] else 0
+
+
 # ---- opt-in: what the rounds leave colliding gets the nearest free last-level code (--finish nearest_free) ------------------------
 @torch.no_grad()
 def finish_collisions(model, idx, resid_last, ks):
@@ -212,18 +224,8 @@ def finish_collisions(model, idx, resid_last, ks):
     A function of its inputs alone: under torchrun every rank runs it on its identical copy, with no collective."""
     levels = list(model.rq.vq_layers)
     cb_last = levels[-1].embedding.weight.detach().contiguous()
-    n, L = idx.shape
-    dev = idx.device
-    if L == 1:                                             # one bucket of all items
-        members = torch.arange(n, dtype=torch.int64, device=dev)
-        offsets = torch.tensor([0, n], dtype=torch.int64, device=dev)
-        buckets, largest = (1, n) if n else (0, 0)
-        if not n:
-            offsets = offsets[:1]
-    else:
-        found = ops.collision_groups(idx[:, :L - 1].contiguous(), ks[:-1], want_groups="device")
-        members, offsets = found["members"], found["offsets"]
-        buckets, largest = found["n_groups"], found["max_count"] if found["n_groups"] else 0
+    L = idx.shape[1]
+    members, offsets, buckets, largest = _prefix_groups(idx, ks, L - 1)
     moved, unresolved = ops.finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets)
     return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
 
@@ -295,16 +297,8 @@ def extend_collisions(model, idx, n_frozen, resid_new, ks):
     returns dict(moved, unresolved, buckets, largest_bucket)."""
     levels = list(model.rq.vq_layers)
     cb_last = levels[-1].embedding.weight.detach().contiguous()
-    n, L = idx.shape
-    dev = idx.device
-    if L == 1:                                             # one bucket of all items, as finish_collisions
-        members = torch.arange(n, dtype=torch.int64, device=dev)
-        offsets = torch.tensor([0, n], dtype=torch.int64, device=dev)
-        buckets, largest = 1, n
-    else:
-        found = ops.collision_groups(idx[:, :L - 1].contiguous(), ks[:-1], want_groups="device")
-        members, offsets = found["members"], found["offsets"]
-        buckets, largest = found["n_groups"], found["max_count"] if found["n_groups"] else 0
+    L = idx.shape[1]
+    members, offsets, buckets, largest = _prefix_groups(idx, ks, L - 1)
     moved, unresolved = ops.extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets)
     return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
 
@@ -324,18 +318,8 @@ def spill_collisions(model, idx, n_frozen, resid_prev, resid_last, ks):
         raise ValueError("--spill moves an item one level above the last: a one-level model has none")
     cb_prev = levels[-2].embedding.weight.detach().contiguous()
     cb_last = levels[-1].embedding.weight.detach().contiguous()
-    dev = idx.device
     shared = ops.collision_groups(idx, ks, want_groups="device")
-    if L == 2:                                             # one super-bucket of all items
-        members = torch.arange(n, dtype=torch.int64, device=dev)
-        offsets = torch.tensor([0, n], dtype=torch.int64, device=dev)
-        supers, largest = (1, n) if n else (0, 0)
-        if not n:
-            offsets = offsets[:1]
-    else:
-        found = ops.collision_groups(idx[:, :L - 2].contiguous(), ks[:-2], want_groups="device")
-        members, offsets = found["members"], found["offsets"]
-        supers, largest = found["n_groups"], found["max_count"] if found["n_groups"] else 0
+    members, offsets, supers, largest = _prefix_groups(idx, ks, L - 2)
     moved, unresolved = ops.spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, ks,
                                                (shared["members"], shared["offsets"]), (members, offsets))
     return {"moved": moved, "unresolved": unresolved, "super_buckets": supers, "largest_super_bucket": largest}

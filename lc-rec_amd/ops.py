@@ -967,6 +967,28 @@ def collision_plan(n, ks):
     return out
 
 
+def _inplace_idx(idx):
+    """(n, L) of an idx that a pass updates in place."""
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2 and idx.is_contiguous()):
+        raise _lib.LcrecError("idx must be a contiguous int64 [n, L] device tensor (it is updated in place)")
+    return idx.shape
+
+
+def _frozen_count(n_frozen, n, L):
+    n_frozen = int(n_frozen)
+    if not 0 <= n_frozen <= n:
+        raise _lib.LcrecError(f"n_frozen={n_frozen} does not go with idx {(n, L)} (0 .. {n})")
+    return n_frozen
+
+
+def _group_table(members, offsets, what=""):
+    """A (members, offsets) table in collision_groups' "device" layout, both contiguous; `what` names the table in the message."""
+    for name, t in (("members", members), ("offsets", offsets)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
+            raise _lib.LcrecError(f"{what}{name} must be an int64 [*] device tensor")
+    return members.contiguous(), offsets.contiguous()
+
+
 def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
     """The nearest-free-code finishing pass (lcrec_finish_nearest_free of include/lcrec.h, which states the rule): every item of
     a bucket -- `members[offsets[b]:offsets[b+1]]`, the items sharing idx[:, :L-1], ids ascending -- that still shares its last
@@ -977,14 +999,9 @@ def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
     level, cb_last float32 [K_last, e]; members / offsets are int64 device tensors in collision_groups' "device" layout.
     Returns (moved, unresolved); afterwards exactly `unresolved` items of the listed buckets still collide."""
     lib = _lib.load()
-    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2 and idx.is_contiguous()):
-        raise _lib.LcrecError("idx must be a contiguous int64 [n, L] device tensor (it is updated in place)")
-    n, L = idx.shape
+    n, L = _inplace_idx(idx)
     resid_last, cb_last = _dev(resid_last, "resid_last"), _dev(cb_last, "cb_last")
-    for name, t in (("members", members), ("offsets", offsets)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
-            raise _lib.LcrecError(f"{name} must be an int64 [*] device tensor")
-    members, offsets = members.contiguous(), offsets.contiguous()
+    members, offsets = _group_table(members, offsets)
     if resid_last.dim() != 2 or cb_last.dim() != 2 or resid_last.shape[0] != n or resid_last.shape[1] != cb_last.shape[1]:
         raise _lib.LcrecError(f"resid_last {tuple(resid_last.shape)} and cb_last {tuple(cb_last.shape)} do not go with idx {(n, L)}")
     if len(ks) != L or int(ks[-1]) != cb_last.shape[0]:
@@ -1009,17 +1026,10 @@ def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets)
     entering the last level of the NEW items only (row i - n_frozen for item i); cb_last float32 [K_last, e]; members / offsets
     are int64 device tensors in collision_groups' "device" layout over all n items.  Returns (moved, unresolved)."""
     lib = _lib.load()
-    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2 and idx.is_contiguous()):
-        raise _lib.LcrecError("idx must be a contiguous int64 [n, L] device tensor (it is updated in place)")
-    n, L = idx.shape
-    n_frozen = int(n_frozen)
-    if not 0 <= n_frozen <= n:
-        raise _lib.LcrecError(f"n_frozen={n_frozen} does not go with idx {(n, L)} (0 .. {n})")
+    n, L = _inplace_idx(idx)
+    n_frozen = _frozen_count(n_frozen, n, L)
     resid_new, cb_last = _dev(resid_new, "resid_new"), _dev(cb_last, "cb_last")
-    for name, t in (("members", members), ("offsets", offsets)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
-            raise _lib.LcrecError(f"{name} must be an int64 [*] device tensor")
-    members, offsets = members.contiguous(), offsets.contiguous()
+    members, offsets = _group_table(members, offsets)
     if resid_new.dim() != 2 or cb_last.dim() != 2 or resid_new.shape[0] != n - n_frozen or resid_new.shape[1] != cb_last.shape[1]:
         raise _lib.LcrecError(f"resid_new {tuple(resid_new.shape)} and cb_last {tuple(cb_last.shape)} do not go with idx {(n, L)} "
                               f"and n_frozen={n_frozen}: one row per new item")
@@ -1047,22 +1057,15 @@ def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, 
     [ks[L-2], e], cb_last [ks[L-1], e]; tuple_groups / super_groups are (members, offsets) pairs of int64 device tensors in
     collision_groups' "device" layout: the groups of the full idx, and of idx[:, :L-2].  Returns (moved, unresolved)."""
     lib = _lib.load()
-    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2 and idx.is_contiguous()):
-        raise _lib.LcrecError("idx must be a contiguous int64 [n, L] device tensor (it is updated in place)")
-    n, L = idx.shape
-    n_frozen = int(n_frozen)
-    if not 0 <= n_frozen <= n:
-        raise _lib.LcrecError(f"n_frozen={n_frozen} does not go with idx {(n, L)} (0 .. {n})")
+    n, L = _inplace_idx(idx)
+    n_frozen = _frozen_count(n_frozen, n, L)
     resid_prev, resid_last = _dev(resid_prev, "resid_prev"), _dev(resid_last, "resid_last")
     cb_prev, cb_last = _dev(cb_prev, "cb_prev"), _dev(cb_last, "cb_last")
     tables = []
     for what, pair in (("tuple_groups", tuple_groups), ("super_groups", super_groups)):
         if not (isinstance(pair, (tuple, list)) and len(pair) == 2):
             raise _lib.LcrecError(f"{what} must be a (members, offsets) pair")
-        for name, t in zip(("members", "offsets"), pair):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1):
-                raise _lib.LcrecError(f"{what}: {name} must be an int64 [*] device tensor")
-        tables.append((pair[0].contiguous(), pair[1].contiguous()))
+        tables.append(_group_table(*pair, what=f"{what}: "))
     e = cb_last.shape[1] if cb_last.dim() == 2 else -1
     for name, t in (("resid_prev", resid_prev), ("resid_last", resid_last)):
         if t.dim() != 2 or t.shape[0] != n - n_frozen or t.shape[1] != e:

@@ -126,6 +126,19 @@ def test_one_two_and_three_levels(hip, oracle, ks, n):
     assert np.array_equal(want[:, :-1], idx[:, :-1])
 
 
+def test_free_codes_run_out_in_a_later_chunk(hip, oracle):
+    """One bucket of 600 items on codes 0 .. 39 of 320: 280 free codes for about 560 movers.  The walk takes 256 positions at a
+    time, so the last free code goes in the second or third chunk, the movers behind it in that chunk are counted one by one, and
+    at least one whole chunk starts with none left and is counted in parallel."""
+    K, e, n = 320, 16, 600
+    r = gi.rs(29)
+    idx = r.randint(0, 40, size=(n, 1)).astype(np.int64)
+    resid = gi.f32(r.standard_normal((n, e)))
+    cb = gi.f32(r.standard_normal((K, e)))
+    want, movers, unres = _check(hip, idx, resid, cb, [K])
+    assert unres > 0 and len(movers) - unres == 280                                  # the case does run out of free codes
+
+
 def test_300_touched_buckets_among_5000_items(hip, oracle):
     """400 prefixes, about 12 items each on 32 codes: more workgroups than the device has CUs, most of them touched, some not."""
     ks = [20, 20, 32]

@@ -146,6 +146,30 @@ def test_a_super_bucket_of_exactly_all_cells_and_one_of_three_more(hip, oracle):
     assert np.array_equal(want[served[-3:]], _after_first(idx, r1, cb1)[served[-3:]])   # the last three served stay where they were
 
 
+def test_free_cells_run_out_in_a_later_chunk(hip, oracle):
+    """One super-bucket of 600 items on 40 cells (rows 0 .. 3, codes 0 .. 9) of 4 x 80 = 320, given to the pass as it stands --
+    a first pass would fill every row: 280 free cells for about 560 movers.  The walk takes 256 positions at a time, so the last
+    free cell goes in the second or third chunk, the movers behind it in that chunk are counted one by one, and at least one
+    whole chunk starts with none left and is counted in parallel."""
+    ks, e, n = [4, 80], 16, 600
+    r = gi.rs(600)
+    idx = np.stack([r.randint(0, 4, size=n), r.randint(0, 10, size=n)], axis=1).astype(np.int64)
+    r2 = gi.f32(r.standard_normal((n, e)))
+    cb2, cb1 = gi.f32(r.standard_normal((ks[0], e))), gi.f32(r.standard_normal((ks[1], e)))
+    r1 = three_op(r2, cb2[idx[:, 0]])
+    want, served, unres = spill_ref(idx, 0, r2, r1, cb2, cb1)
+    assert unres > 0 and len(served) - unres == 280                                # the case does run out of free cells
+    d_idx = torch.from_numpy(idx).to(DEV)
+    moved, unresolved = hip.ops.spill_nearest_free(d_idx, 0, torch.from_numpy(r2).to(DEV), torch.from_numpy(r1).to(DEV),
+                                                   torch.from_numpy(cb2).to(DEV), torch.from_numpy(cb1).to(DEV), ks,
+                                                   _listed(hip, d_idx, ks, 2), _listed(hip, d_idx, ks, 0))
+    print("served", len(served), "moved", moved, "unresolved", unresolved, "(reference:", len(served) - unres, unres, ")")
+    assert (moved, unresolved) == (len(served) - unres, unres)
+    got = d_idx.cpu().numpy()
+    bad = np.flatnonzero((got != want).any(1))
+    assert bad.size == 0, (bad[:8], got[bad[:8]], want[bad[:8]], idx[bad[:8]])
+
+
 def _after_first(idx, r1, cb1):
     return finish_ref(idx, r1, cb1)[0]
 

@@ -649,7 +649,7 @@ int lcrec_finish_nearest_free(int64_t *idx, int64_t n, int L, const int *K, cons
  *   resid_last      device [n - n_frozen][e] float: the row of item i is i - n_frozen.  Nothing is read for a frozen id.  May be
  *                   NULL when n_frozen == n.
  *   codebook_last   as there, with 4 more bytes of LDS per code (the frozen holders per code): K[L-1] * (4 e + 24) + 512 bytes
- *                   must fit in 160 KB, which refuses K[L-1] = 1856 .. 1920 at e = 16 and 1075 .. 1088 at e = 32 that
+ *                   must fit in 160 KB, which refuses K[L-1] = 1857 .. 1920 at e = 16 and 1075 .. 1088 at e = 32 that
  *                   lcrec_finish_nearest_free takes
  *   bucket_members  item ids ascending inside a bucket (the layout lcrec_collision_groups emits): a bucket whose LAST member is
  *                   frozen holds no new item and is left at once

@@ -6,17 +6,22 @@ import numpy as np
 from oracle import cpu_oracle
 
 
-def finish_ref(idx, resid_last, cb_last):
+def finish_ref(idx, resid_last, cb_last, buckets=None):
     """idx int [N, L], resid_last [N, e], cb_last [K, e] -> (new idx int64 [N, L], mover ids in the order they were served,
-    unresolved).  len(movers) - unresolved items moved."""
+    unresolved).  len(movers) - unresolved items moved.
+    buckets: None = the items sharing idx[:, :L-1]; or lists of item ids as a caller would pass them to the entry -- a member whose
+    id is outside [0, N) or whose last code is outside [0, K) takes no part."""
     idx = np.array(idx, dtype=np.int64)
     n, L = idx.shape
     K = cb_last.shape[0]
-    buckets = {}
-    for i in range(n):                                                      # 1. buckets: items sharing idx[:, :L-1]
-        buckets.setdefault(tuple(idx[i, :L - 1]), []).append(i)
+    if buckets is None:
+        found = {}
+        for i in range(n):                                                  # 1. buckets: items sharing idx[:, :L-1]
+            found.setdefault(tuple(idx[i, :L - 1]), []).append(i)
+        buckets = list(found.values())
     movers_all, unresolved = [], 0
-    for items in buckets.values():                                          # (ids ascend inside a bucket)
+    for listed in buckets:                                                  # (ids ascend inside a bucket)
+        items = sorted(int(i) for i in listed if 0 <= i < n and 0 <= idx[i, L - 1] < K)
         holders = {}
         for i in items:
             holders.setdefault(int(idx[i, L - 1]), []).append(i)

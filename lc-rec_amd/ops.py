@@ -989,7 +989,28 @@ def _group_table(members, offsets, what=""):
     return members.contiguous(), offsets.contiguous()
 
 
-def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
+def _counters_out(counters_out, device):
+    """The (moved, unresolved) pair of a nearest-free pass as the caller's own int64 [2] tensor on `device`, or (None) a fresh one."""
+    if counters_out is None:
+        return torch.empty(2, dtype=torch.int64, device=device)
+    if not (isinstance(counters_out, torch.Tensor) and counters_out.device == device and counters_out.dtype == torch.int64
+            and tuple(counters_out.shape) == (2,) and counters_out.is_contiguous()):
+        raise _lib.LcrecError(f"counters_out must be a contiguous int64 [2] tensor on idx's device ({device})")
+    return counters_out
+
+
+def _own_workspace(workspace, device, need, query):
+    """A workspace the caller owns, passed to the library as it is: a contiguous uint8 tensor on `device` of at least the `need`
+    bytes that `query` (the entry's workspace function) states for this call."""
+    if not (isinstance(workspace, torch.Tensor) and workspace.device == device and workspace.dtype == torch.uint8
+            and workspace.is_contiguous()):
+        raise _lib.LcrecError(f"workspace must be a contiguous uint8 tensor on the call's device ({device})")
+    if workspace.numel() < need:
+        raise _lib.LcrecError(f"workspace of {workspace.numel()} bytes, {int(need)} needed ({query})")
+    return workspace
+
+
+def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets, counters_out=None):
     """The nearest-free-code finishing pass (lcrec_finish_nearest_free of include/lcrec.h, which states the rule): every item of
     a bucket -- `members[offsets[b]:offsets[b+1]]`, the items sharing idx[:, :L-1], ids ascending -- that still shares its last
     code with another gets the nearest free last-level code; the holder nearest to a shared code keeps it.  Beyond the reference,
@@ -997,7 +1018,9 @@ def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
 
     idx int64 [n, L] is updated IN PLACE (last column, movers only); resid_last float32 [n, e] is the residual entering the last
     level, cb_last float32 [K_last, e]; members / offsets are int64 device tensors in collision_groups' "device" layout.
-    Returns (moved, unresolved); afterwards exactly `unresolved` items of the listed buckets still collide."""
+    Returns (moved, unresolved); afterwards exactly `unresolved` items of the listed buckets still collide.
+    counters_out: an int64 [2] tensor on idx's device that receives (moved, unresolved) instead; the binding then reads nothing
+    back and returns None -- the form of the call that a graph capture can record (it allocates nothing and never waits)."""
     lib = _lib.load()
     n, L = _inplace_idx(idx)
     resid_last, cb_last = _dev(resid_last, "resid_last"), _dev(cb_last, "cb_last")
@@ -1008,23 +1031,26 @@ def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets):
         raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}] and cb_last [{cb_last.shape[0]}, *]")
     n_buckets = max(offsets.numel() - 1, 0)
     dev = idx.device
-    counters = torch.empty(2, dtype=torch.int64, device=dev)
+    counters = _counters_out(counters_out, dev)
     with _on(dev):
         rc = lib.lcrec_finish_nearest_free(_ptr(idx), n, L, _ints(ks), _ptr(resid_last), resid_last.shape[1], _ptr(cb_last),
                                            _ptr(members), _ptr(offsets), n_buckets, _ptr(counters), _stream_ptr())
     _lib.check(rc, "lcrec_finish_nearest_free")
+    if counters_out is not None:
+        return None
     moved, unresolved = counters.tolist()
     return moved, unresolved
 
 
-def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets):
+def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets, counters_out=None):
     """The frozen-aware nearest-free-code pass (lcrec_extend_nearest_free of include/lcrec.h, which states the rule): items
     0 .. n_frozen-1 of idx never change; a new item that shares its tuple with a frozen one moves to the nearest free last-level
     code of its bucket, and among new items only the holder nearest to a shared code keeps it.
 
     idx int64 [n, L] is updated IN PLACE (last column, new movers only); resid_new float32 [n - n_frozen, e] holds the residual
     entering the last level of the NEW items only (row i - n_frozen for item i); cb_last float32 [K_last, e]; members / offsets
-    are int64 device tensors in collision_groups' "device" layout over all n items.  Returns (moved, unresolved)."""
+    are int64 device tensors in collision_groups' "device" layout over all n items.  Returns (moved, unresolved).
+    counters_out: as finish_nearest_free -- an int64 [2] device tensor that receives the pair; nothing is read back, None is returned."""
     lib = _lib.load()
     n, L = _inplace_idx(idx)
     n_frozen = _frozen_count(n_frozen, n, L)
@@ -1037,16 +1063,19 @@ def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets)
         raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}] and cb_last [{cb_last.shape[0]}, *]")
     n_buckets = max(offsets.numel() - 1, 0)
     dev = idx.device
-    counters = torch.empty(2, dtype=torch.int64, device=dev)
+    counters = _counters_out(counters_out, dev)
     with _on(dev):
         rc = lib.lcrec_extend_nearest_free(_ptr(idx), n, n_frozen, L, _ints(ks), _ptr(resid_new), resid_new.shape[1], _ptr(cb_last),
                                            _ptr(members), _ptr(offsets), n_buckets, _ptr(counters), _stream_ptr())
     _lib.check(rc, "lcrec_extend_nearest_free")
+    if counters_out is not None:
+        return None
     moved, unresolved = counters.tolist()
     return moved, unresolved
 
 
-def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, ks, tuple_groups, super_groups):
+def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, ks, tuple_groups, super_groups, counters_out=None,
+                       workspace=None):
     """Spill to a sibling bucket (lcrec_spill_nearest_free of include/lcrec.h, which states the rule): every item that still
     shares its tuple after finish_nearest_free / extend_nearest_free -- its bucket has more items than the last level has codes --
     takes the nearest code of level L-2 whose row has a free cell in its super-bucket (the items sharing idx[:, :L-2]) and the
@@ -1055,7 +1084,10 @@ def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, 
     idx int64 [n, L], L >= 2, is updated IN PLACE (columns L-2 and L-1 of the items that move); resid_prev / resid_last float32
     [n - n_frozen, e] are the residuals entering levels L-2 / L-1 of the NEW items (row i - n_frozen for item i); cb_prev
     [ks[L-2], e], cb_last [ks[L-1], e]; tuple_groups / super_groups are (members, offsets) pairs of int64 device tensors in
-    collision_groups' "device" layout: the groups of the full idx, and of idx[:, :L-2].  Returns (moved, unresolved)."""
+    collision_groups' "device" layout: the groups of the full idx, and of idx[:, :L-2].  Returns (moved, unresolved).
+    counters_out: as finish_nearest_free -- an int64 [2] device tensor that receives the pair; nothing is read back, None is returned.
+    workspace: a uint8 device tensor of at least lcrec_spill_nearest_free_workspace(n) bytes, passed as the workspace as it is, its
+    size included; None: the binding's own grow-only buffer of the stream, which a captured graph must not point into."""
     lib = _lib.load()
     n, L = _inplace_idx(idx)
     n_frozen = _frozen_count(n_frozen, n, L)
@@ -1078,13 +1110,18 @@ def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, 
                               f"{tuple(cb_last.shape)}")
     (tmem, toff), (smem, soff) = tables
     dev = idx.device
-    counters = torch.empty(2, dtype=torch.int64, device=dev)
+    counters = _counters_out(counters_out, dev)
+    need = lib.lcrec_spill_nearest_free_workspace(n)
+    if workspace is not None:
+        workspace = _own_workspace(workspace, dev, need, "lcrec_spill_nearest_free_workspace")
     with _on(dev):
-        ws = _workspace(lib.lcrec_spill_nearest_free_workspace(n), dev)
+        ws = workspace if workspace is not None else _workspace(need, dev)
         rc = lib.lcrec_spill_nearest_free(_ptr(idx), n, n_frozen, L, _ints(ks), _ptr(resid_prev), _ptr(resid_last), e, _ptr(cb_prev),
                                           _ptr(cb_last), _ptr(tmem), _ptr(toff), max(toff.numel() - 1, 0), _ptr(smem), _ptr(soff),
                                           max(soff.numel() - 1, 0), _ptr(counters), _ptr(ws), ws.numel(), _stream_ptr())
     _lib.check(rc, "lcrec_spill_nearest_free")
+    if counters_out is not None:
+        return None
     moved, unresolved = counters.tolist()
     return moved, unresolved
 
@@ -1115,11 +1152,13 @@ def rq_audit(z, codebooks_flat, ks, idx, want_best=False, want_resid=False):
     return out
 
 
-def rq_audit_into(z, codebooks_flat, ks, idx, out):
+def rq_audit_into(z, codebooks_flat, ks, idx, out, workspace=None):
     """lcrec_rq_audit into buffers the caller owns, as rq_assign_into does for lcrec_rq_assign: `out` holds "d_held", "d_best"
     float32, "rank" int32, "err" float32, "flags" int32 and may hold "best" int64 and "resid" float32 (one that is missing is passed
     as NULL), each contiguous on z's device with at least the elements the call writes -- it may be LARGER, so that a test can look
-    at what lies past the end.  Nothing is returned."""
+    at what lies past the end.  workspace: a uint8 device tensor of at least lcrec_rq_audit_workspace's bytes, passed as the
+    workspace as it is, its size included; None: the binding's own grow-only buffer of the stream, which a captured graph must not
+    point into.  Nothing is returned."""
     lib = _lib.load()
     z = _dev(z, "z")
     cb = _dev(codebooks_flat, "codebooks")
@@ -1144,11 +1183,14 @@ def rq_audit_into(z, codebooks_flat, ks, idx, out):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()
                 and t.numel() >= need):
             raise _lib.LcrecError(f"out[{name!r}] must be a contiguous {dtype} tensor on z's device with at least {need} elements")
+    karr = _ints(ks)
+    need = lib.lcrec_rq_audit_workspace(n, e, karr, L)
+    if workspace is not None:
+        workspace = _own_workspace(workspace, dev, need, "lcrec_rq_audit_workspace")
     if n == 0:                                             # (an empty tensor has no address to pass)
         return
-    karr = _ints(ks)
     with _on(dev):
-        ws = _workspace(lib.lcrec_rq_audit_workspace(n, e, karr, L), dev)
+        ws = workspace if workspace is not None else _workspace(need, dev)
         rc = lib.lcrec_rq_audit(_ptr(z), n, e, _ptr(cb), karr, L, _ptr(idx), idx_stride, _ptr(out["d_held"]), _ptr(out["d_best"]),
                                 _ptr(out["rank"]), _ptr(out.get("best")), _ptr(out["err"]), _ptr(out.get("resid")),
                                 _ptr(out["flags"]), _ptr(ws), ws.numel(), _stream_ptr())

@@ -6,7 +6,11 @@ admits there, the LDS edge)}; n in {1, 63, 64, 65, 257, 1000}: a lone lane, the 
 and several workgroups (none of these makes a second trip of the item loop: LOOPING below does); K below 64, K no multiple of 32 or
 64, K = 1 and the largest admitted level.  To keep the product small every n runs at one ks per e, and every ks at n = 257.
 Inputs: standard-normal latents, level-l codebooks scaled by 0.7^l.  Each shape is audited twice: with the oracle's greedy tuples
-(all ranks 0) and with uniformly random tuples (ranks up to K - 1)."""
+(all ranks 0) and with uniformly random tuples (ranks up to K - 1).
+
+ADDED (at the end of shapes(), so that every earlier row keeps its place): the largest level the entry admits at each e, LARGEST --
+one workgroup resident per CU, the staging loops at their largest number of trips -- and a quantiser of LCREC_MAX_LEVELS = 16
+levels, KS_DEEP: flag bit 15, sixteen launches, the residual through the workspace fifteen times."""
 import functools
 
 import numpy as np
@@ -27,6 +31,39 @@ N_FOR_ALL_KS = 257
 # through the loop too), and the largest level at e = 64 (per_cu = 1).  Random tuples only: the reference costs a second or two.
 LOOPING = ((16, (48, 7), 256 * 256 * 8 + 65), (64, (576,), 256 * 256 + 65))
 N_RANK_SPREAD = 321                                         # random tuples reach rank >= K / 2 at every level with K >= 48
+# The largest level lcrec_rq_audit (and lcrec_rq_beam, and lcrec_rq_assign) admits at L = 1: rq_level_fits of include/lcrec.h,
+#   rows * (4 e + 20) + 32 L <= 160 KB = 163840 with rows = K rounded up to 32
+# so rows <= (163840 - 32) / (4 e + 20) = 1950.09, 1106.8 and 593.5 at e = 16, 32 and 64, rounded down to a multiple of 32.  The
+# kernel's own dynamic LDS, K * (4 e + 20), is then 161280, 161024 and 158976 bytes.  largest_level() is that derivation.
+LDS_PER_CU = 160 * 1024
+LARGEST = {16: 1920, 32: 1088, 64: 576}
+MAX_LEVELS = 16
+KS_DEEP = (2, 1, 2) + (3,) * 13                             # e = 16 only; with a beam of 8 the live count goes 2, 2, 4, 8, 8, ...
+DEEP_E = 16
+
+
+def level_fits(K, e, L=1):
+    rows = (K + 31) & ~31
+    return K >= 1 and rows * (4 * e + 20) + 32 * L <= LDS_PER_CU
+
+
+def largest_level(e, L=1):
+    """the largest K with level_fits(K, e, L), found by walking up"""
+    K = 1
+    while level_fits(K + 1, e, L):
+        K += 1
+    return K
+
+
+def largest_admitted(admits, refused=4096):
+    """The largest K with admits(K), by bisection between 1 (admitted) and `refused`.  admits(K) asks an ENTRY: a call at n = 0, which
+    passes the admission check and launches nothing, is True; a refusal with the "does not fit" text is False."""
+    lo, hi = 1, refused
+    assert admits(lo) and not admits(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if admits(mid) else (lo, mid)
+    return lo
 
 
 def shapes():
@@ -38,7 +75,12 @@ def shapes():
         for ks in KS + ((KS_EDGE,) if e == 64 else ()):
             if (e, ks, N_FOR_ALL_KS) not in rows:
                 rows.append((e, ks, N_FOR_ALL_KS))
-    return rows
+    return rows + added_shapes()
+
+
+def added_shapes():
+    """the largest level at e = 16 and 32 (e = 64: KS_EDGE above) and the 16-level quantiser, at n = 257"""
+    return [(e, (LARGEST[e],), N_FOR_ALL_KS) for e in ES if (LARGEST[e],) != KS_EDGE] + [(DEEP_E, KS_DEEP, N_FOR_ALL_KS)]
 
 
 def shape_id(row):
@@ -83,14 +125,15 @@ def tie_case():
 
 
 def out_of_range_case(L):
-    """Codes -1, K, 2^40 and a valid one, cycling over the items, at level 0 of L = 1 or at level 1 of L = 3 (the other levels hold
-    the greedy code).  -> (z, codebooks, tuples, level, K of that level)"""
+    """Codes -1, K, 2^40 and a valid one, cycling over the items, at level 0 of L = 1, at level 1 of L = 3 or at level 15 of L = 16
+    (KS_DEEP; the other levels hold the greedy code).  -> (z, codebooks, tuples, level, K of that level)
+    (The valid one is code 5 where the level has more than 5 codes, else its last code.)"""
     e, n = 16, 70
-    ks = (48,) if L == 1 else (48, 100, 7)
-    level = 0 if L == 1 else 1
+    ks = {1: (48,), 3: (48, 100, 7), MAX_LEVELS: KS_DEEP}[L]
+    level = {1: 0, 3: 1, MAX_LEVELS: MAX_LEVELS - 1}[L]
     z, cbs, greedy, _, _ = inputs(e, ks, n)
     idx = greedy.copy()
-    idx[:, level] = np.resize(np.array([-1, ks[level], 1 << 40, 5], dtype=np.int64), n)
+    idx[:, level] = np.resize(np.array([-1, ks[level], 1 << 40, min(5, ks[level] - 1)], dtype=np.int64), n)
     return z, cbs, idx, level, ks[level]
 
 

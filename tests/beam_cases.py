@@ -22,6 +22,12 @@ N_FOR_ALL_KS = 257
 # trip's start and a ragged tail at the cheapest shape (two small levels at e = 16: the residuals and links between the levels go
 # through the loop too), at the widest and at a narrow beam.
 LOOPING = ((16, (48, 7), 8, 1024 * 32 + 37), (16, (48, 7), 2, 1024 * 128 + 65))
+# ADDED (at the end of shapes()): the largest level the entry admits at each e (audit_cases.LARGEST, which derives it from the LDS
+# formula: one workgroup per CU, the staging loops at their largest number of trips) at the narrowest and the widest beam; and the
+# 16-level quantiser audit_cases.KS_DEEP at e = 16 -- the link walk-back over 15 earlier launches, both halves of the ping-pong
+# workspace used 7 times each, and at W = 8 the live count going 2, 2, 4, 8, 8, ....
+WS_LARGEST = (1, 8)
+WS_DEEP = (2, 8)
 
 
 def ns_for(W):
@@ -38,7 +44,12 @@ def shapes():
             for ks in KS:
                 if (e, ks, W, N_FOR_ALL_KS) not in rows:
                     rows.append((e, ks, W, N_FOR_ALL_KS))
-    return rows
+    return rows + added_shapes()
+
+
+def added_shapes():
+    rows = [(e, (ac.LARGEST[e],), W, N_FOR_ALL_KS) for e in ES for W in WS_LARGEST]
+    return rows + [(ac.DEEP_E, ac.KS_DEEP, W, N_FOR_ALL_KS) for W in WS_DEEP]
 
 
 def shape_id(row):

@@ -14,6 +14,9 @@ shapes at w = 100.  Widths: at n = 257 (three workgroups of the error kernel, th
                                     stages its tiles float by float instead of in 16-byte pieces (the GEMM's epilogue stores by
                                     single floats too): below a tile, just past one, and two tiles + 6.
 x (the embeddings the error is taken against) is standard normal.
+ADDED, as the table's last row: audit_cases.KS_DEEP, the 16-level quantiser (LCREC_MAX_LEVELS) at e = 16 and n = 257 under the
+single-layer decoder at w = 100; out_of_range_case(16) puts its bad codes at level 15 (flag bit 15).  audit_cases' largest levels
+are left out like KS_EDGE.
 
 LOOPING: one row per new kernel at the smallest n that makes its item loop take a second trip, plus 65, with e = 16 and the decoder
 [16, 8] (random tuples only, and codebooks drawn here without the oracle, so the reference costs a second or two).  The grid rules:
@@ -44,7 +47,7 @@ def rows():
     """(e, ks, n, form, w) rows, without repeats"""
     out = []
     for i, (e, ks, n) in enumerate(ac.shapes()):
-        if ks == ac.KS_EDGE:                                # (the audit's LDS edge: the decode pass stages nothing in LDS)
+        if ks == ac.KS_EDGE or (e, ks, n) in ac.added_shapes():   # (the audit's LDS edges: the decode pass stages nothing in LDS)
             continue
         out.append((e, ks, n, FORMS[i % len(FORMS)], W_REST))
     e, ks = SHAPE_FOR_ALL_W
@@ -52,6 +55,9 @@ def rows():
         for form in FORMS:
             if (e, ks, N_FOR_ALL_W, form, w) not in out:
                 out.append((e, ks, N_FOR_ALL_W, form, w))
+    # ADDED: the 16-level quantiser (LCREC_MAX_LEVELS: the gather's sixteen codebook pointers and sixteen adds per element) under
+    # the single-layer decoder
+    out.append((ac.DEEP_E, ac.KS_DEEP, ac.N_FOR_ALL_KS, "single", W_REST))
     return out
 
 
@@ -102,8 +108,8 @@ def greedy_path(e, ks, n):
 
 
 def out_of_range_case(L):
-    """audit_cases.out_of_range_case: codes -1, K, 2^40 and a valid one, cycling over the 70 items, at level 0 of L = 1 or at level 1
-    of L = 3; decoder [16, 40, 100].  -> (codebooks, tuples, level, K of that level, decoder, x)"""
+    """audit_cases.out_of_range_case: codes -1, K, 2^40 and a valid one, cycling over the 70 items, at level 0 of L = 1, at level 1
+    of L = 3 or at level 15 of L = 16; decoder [16, 40, 100].  -> (codebooks, tuples, level, K of that level, decoder, x)"""
     _, cbs, idx, level, K = ac.out_of_range_case(L)
     return cbs, idx, level, K, decoder(16, "hidden", W_REST), embeddings(len(idx), W_REST)
 

@@ -90,6 +90,30 @@ def test_audit_entry_reports_argument_errors_before_any_launch():
     assert sizes == [512, 0, 128000, 0]
 
 
+@pytest.mark.parametrize("e", ac.ES)
+def test_the_tables_largest_level_follows_from_the_lds_formula_and_the_entry_draws_the_same_line(e):
+    """ac.LARGEST against its own derivation and against the entry's admission check (calls at n = 0: nothing is launched, so no
+    device is needed); the kernel's dynamic LDS at that level, K * (4 e + 20) bytes, is within the CU's 160 KB."""
+    import lcrec_amd
+    lib = lcrec_amd._lib.load()
+    buf = (ctypes.c_double * 8)()
+    p = ctypes.c_void_p((ctypes.cast(buf, ctypes.c_void_p).value + 15) & ~15)
+
+    def admits(K):
+        def call():
+            rc = lib.lcrec_rq_audit(p, 0, e, p, (ctypes.c_int * 1)(K), 1, p, 0, p, p, p, p, p, p, p, None, 0, None)
+            return rc, lib.lcrec_last_error()
+        rc, text = ec.in_thread(call)
+        assert rc == 0 or (rc == -2 and b"level 0 (K=%d, e=%d) does not fit" % (K, e) in text), (rc, text)
+        return rc == 0
+
+    K = ac.LARGEST[e]
+    assert ac.largest_level(e) == K == ac.largest_admitted(admits) and K % 32 == 0
+    assert K * (4 * e + 20) == {16: 161280, 32: 161024, 64: 158976}[e] <= ac.LDS_PER_CU
+    assert (e, (K,), ac.N_FOR_ALL_KS) in ac.shapes() and (ac.DEEP_E, ac.KS_DEEP, ac.N_FOR_ALL_KS) in ac.shapes()
+    assert len(ac.KS_DEEP) == ac.MAX_LEVELS == lcrec_amd._lib.MAX_LEVELS
+
+
 def test_the_binding_refuses_what_is_not_on_a_device():
     """... before the library is called: no last-error text is left in this thread."""
     import lcrec_amd
@@ -132,14 +156,14 @@ def test_reference_on_exact_ties(oracle):
     assert (ref["rank"][:, 0] >= 2).all()                                            # rows 7 and 40 always precede 41 on a tie
 
 
-@pytest.mark.parametrize("L", [1, 3])
+@pytest.mark.parametrize("L", [1, 3, ac.MAX_LEVELS])
 def test_reference_clamps_and_flags_out_of_range_codes(oracle, L):
     z, cbs, idx, level, K = ac.out_of_range_case(L)
     ref = audit_ref(z, cbs, idx)
     want = np.where(np.arange(len(z)) % 4 == 3, 0, 1 << level)
     assert np.array_equal(ref["flags"], want.astype(np.uint32))
     clamped = idx.copy()
-    clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, 5]), len(z))
+    clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, min(5, K - 1)]), len(z))
     same = audit_ref(z, cbs, clamped)
     for k in ("d_held", "d_best", "rank", "best", "err", "resid"):
         assert np.array_equal(ref[k], same[k]), k                                    # the residual followed the clamped code

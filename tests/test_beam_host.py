@@ -103,6 +103,30 @@ def test_beam_entry_reports_argument_errors_before_any_launch():
     assert sizes[5:] == [0] * 7                                                       # refused arguments
 
 
+@pytest.mark.parametrize("e", bc.ES)
+def test_the_tables_largest_level_is_where_the_entry_draws_the_line(e):
+    """audit_cases.LARGEST (derived from the LDS formula there) against lcrec_rq_beam's admission check: calls at n = 0, nothing is
+    launched, no device is needed.  The grid runs that level at the narrowest and the widest beam, and the 16-level quantiser."""
+    import extend_cases as ec
+    import lcrec_amd
+    lib = lcrec_amd._lib.load()
+    buf = (ctypes.c_double * 8)()
+    p = ctypes.c_void_p((ctypes.cast(buf, ctypes.c_void_p).value + 15) & ~15)
+
+    def admits(K):
+        def call():
+            return lib.lcrec_rq_beam(p, 0, e, p, (ctypes.c_int * 1)(K), 1, 8, p, p, p, p, None, 0, None), lib.lcrec_last_error()
+        rc, text = ec.in_thread(call)
+        assert rc == 0 or (rc == -2 and b"level 0 (K=%d, e=%d) does not fit" % (K, e) in text), (rc, text)
+        return rc == 0
+
+    K = ac.LARGEST[e]
+    assert ac.largest_admitted(admits) == K
+    assert all((e, (K,), W, bc.N_FOR_ALL_KS) in bc.shapes() for W in (1, 8))
+    assert all((16, ac.KS_DEEP, W, bc.N_FOR_ALL_KS) in bc.shapes() for W in (2, 8))
+    assert live_counts(ac.KS_DEEP, 8)[:5] == [2, 2, 4, 8, 8] and live_counts(ac.KS_DEEP, 8)[-1] == 8
+
+
 def test_the_binding_refuses_what_is_not_on_a_device():
     """... before the library is called: no last-error text is left in this thread."""
     import lcrec_amd

@@ -115,6 +115,58 @@ def test_a_new_enumerator_without_a_name_is_refused_at_import(binding, header):
         ops._check_names(binding.parse_header(damaged(header, "LCREC_SK_TABLE_RING = 2", "LCREC_SK_TABLE_RING = 4"))[0])
 
 
+def test_the_capturable_forms_refuse_a_wrong_counters_out_or_workspace_before_the_call(binding):
+    """counters_out (finish / extend / spill_nearest_free) and workspace (spill_nearest_free, rq_audit_into) are checked by the two
+    helpers below against the device of the call -- here the CPU stands in for it, so that no GPU is needed: wrong dtype, wrong
+    shape, wrong device, not contiguous and a workspace one byte too small are each an LcrecError of the binding's own, raised
+    before the library is called (its last-error text does not change)."""
+    import inspect
+
+    import torch
+
+    from lcrec_amd import ops
+    lib = binding.load()
+    before = lib.lcrec_last_error()
+    here, elsewhere = torch.device("cpu"), "meta"
+    for f, names in ((ops.finish_nearest_free, ("counters_out",)), (ops.extend_nearest_free, ("counters_out",)),
+                     (ops.spill_nearest_free, ("counters_out", "workspace")), (ops.rq_audit_into, ("workspace",)),
+                     (ops.rq_beam_into, ("workspace",))):
+        params = inspect.signature(f).parameters
+        assert all(params[name].default is None for name in names), f.__name__
+        assert all(name in f.__doc__ for name in names), f.__name__
+
+    mine = torch.zeros(2, dtype=torch.int64)
+    assert ops._counters_out(mine, here) is mine                                      # passed through as it is
+    fresh = ops._counters_out(None, here)
+    assert fresh.dtype == torch.int64 and tuple(fresh.shape) == (2,)
+    for bad in (torch.zeros(2, dtype=torch.int32), torch.zeros(2, dtype=torch.float64), torch.zeros(3, dtype=torch.int64),
+                torch.zeros((1, 2), dtype=torch.int64), torch.zeros(4, dtype=torch.int64)[::2],
+                torch.zeros(2, dtype=torch.int64, device=elsewhere), [0, 0], 0):
+        with pytest.raises(binding.LcrecError, match="counters_out must be a contiguous int64 \\[2\\] tensor"):
+            ops._counters_out(bad, here)
+
+    need = lib.lcrec_spill_nearest_free_workspace(218)
+    assert need == 256 and lib.lcrec_rq_audit_workspace(257, 16, ops._ints([48, 100, 7]), 3) == 16640
+    ws = torch.zeros(need, dtype=torch.uint8)
+    assert ops._own_workspace(ws, here, need, "q") is ws and ops._own_workspace(ws, here, 0, "q") is ws
+    for bad in (torch.zeros(need, dtype=torch.int8), torch.zeros(need // 4, dtype=torch.float32), torch.zeros(2 * need, dtype=torch.uint8)[::2],
+                torch.zeros(need, dtype=torch.uint8, device=elsewhere), bytearray(need)):
+        with pytest.raises(binding.LcrecError, match="workspace must be a contiguous uint8 tensor"):
+            ops._own_workspace(bad, here, need, "q")
+    with pytest.raises(binding.LcrecError, match=r"workspace of 255 bytes, 256 needed \(lcrec_spill_nearest_free_workspace\)"):
+        ops._own_workspace(ws[:255], here, need, "lcrec_spill_nearest_free_workspace")
+    # the entries themselves refuse what is not on a device before anything else
+    idx, r, cb = torch.zeros((4, 2), dtype=torch.int64), torch.zeros((4, 16)), torch.zeros((8, 16))
+    table = (torch.zeros(0, dtype=torch.int64), torch.zeros(1, dtype=torch.int64))
+    for call in (lambda: ops.finish_nearest_free(idx, r, cb, [2, 8], *table, counters_out=mine),
+                 lambda: ops.extend_nearest_free(idx, 0, r, cb, [2, 8], *table, counters_out=mine),
+                 lambda: ops.spill_nearest_free(idx, 0, r, r, cb, cb, [8, 8], table, table, counters_out=mine, workspace=ws),
+                 lambda: ops.rq_audit_into(r, cb, [8], idx[:, :1], {}, workspace=ws)):
+        with pytest.raises(binding.LcrecError, match="device"):
+            call()
+    assert lib.lcrec_last_error() == before
+
+
 def test_linear_bn_supported_answers_as_the_rule_it_restated(binding):
     """The Python expression linear_bn_supported was before it asked the library, as the reference, on a grid around every bound."""
     from lcrec_amd import ops

@@ -212,13 +212,13 @@ def test_sum_of_the_codes_is_the_straight_through_sum_up_to_rounding_and_not_bit
 
 
 def test_reference_clamps_and_flags_out_of_range_codes(oracle):
-    for L in (1, 3):
+    for L in (1, 3, ac.MAX_LEVELS):
         cbs, idx, level, K, (dims, Ws, bs, scs, shs), x = dc.out_of_range_case(L)
         ref = decode_ref(idx, cbs, Ws, bs, scs, shs, x)
         want = np.where(np.arange(len(idx)) % 4 == 3, 0, 1 << level)
         assert np.array_equal(ref["flags"], want.astype(np.uint32))
         clamped = idx.copy()
-        clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, 5]), len(idx))
+        clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, min(5, K - 1)]), len(idx))
         same = decode_ref(clamped, cbs, Ws, bs, scs, shs, x)
         assert (same["flags"] == 0).all()
         for k in ("xq", "out", "err", "err_l1"):

@@ -115,6 +115,34 @@ def test_item_loop_makes_more_than_one_trip(hip, oracle, row):
     check(got, ac.reference(e, ks, n, "random"), (row, "looping"))
 
 
+def _admits(hip, e, K):
+    """whether lcrec_rq_audit takes a lone level of K codes: a call at n = 0, past every check and launching nothing.  (The library
+    itself is called: the binding never passes an empty tensor on.)"""
+    import ctypes
+    import extend_cases as ec
+    lib = hip._lib.load()
+    p = ctypes.c_void_p(torch.zeros(64, device=DEV).data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call():
+        hip._lib.check(lib.lcrec_rq_audit(p, 0, e, p, hip.ops._ints([K]), 1, p, 0, p, p, p, p, p, p, p, None, 0, stream), "lcrec_rq_audit")
+    try:
+        ec.in_thread(call)                                                           # (the last-error text stays in that thread)
+        return True
+    except hip.LcrecError as refusal:
+        assert f"level 0 (K={K}, e={e}) does not fit" in str(refusal), str(refusal)
+        return False
+
+
+@pytest.mark.parametrize("e", ac.ES)
+def test_the_largest_level_of_the_table_is_the_largest_the_entry_admits(hip, e):
+    """ac.LARGEST, derived from the LDS formula, against the entry itself: K is admitted, K + 1 refused as not fitting."""
+    found = ac.largest_admitted(lambda K: _admits(hip, e, K))
+    print("rq_audit e", e, "largest admitted K", found, "(derived:", ac.LARGEST[e], ")")
+    assert found == ac.LARGEST[e] == ac.largest_level(e) and not _admits(hip, e, found + 1)
+    assert (e, (found,), ac.N_FOR_ALL_KS) in ac.shapes()                              # ... and the grid above runs it
+
+
 def test_exact_ties_rank_by_code_order(hip, oracle):
     z, cbs, idx = ac.tie_case()
     got = run(hip, z, cbs, idx)
@@ -123,14 +151,14 @@ def test_exact_ties_rank_by_code_order(hip, oracle):
     assert (got["d_held"][:4, 0] == 0).all() and (got["d_best"][:4, 0] == 0).all()
 
 
-@pytest.mark.parametrize("L", [1, 3])
+@pytest.mark.parametrize("L", [1, 3, ac.MAX_LEVELS])
 def test_out_of_range_codes_are_clamped_and_flagged(hip, oracle, L):
     z, cbs, idx, level, K = ac.out_of_range_case(L)
     got = run(hip, z, cbs, idx)
     check(got, audit_ref(z, cbs, idx), ("out of range", L))
     assert np.array_equal(got["flags"], np.where(np.arange(len(z)) % 4 == 3, 0, 1 << level))
     clamped = idx.copy()
-    clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, 5]), len(z))
+    clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, min(5, K - 1)]), len(z))
     again = run(hip, z, cbs, clamped)
     for name in ("d_held", "d_best", "rank", "best", "err", "resid"):                 # the residual followed the clamped code
         assert same_bits(got[name], again[name]), name

@@ -120,6 +120,37 @@ def test_item_loop_makes_more_than_one_trip(hip, oracle, row):
     check(run(hip, z, cbs, W), bc.reference(e, ks, W, n), (row, "looping"))
 
 
+def _admits(hip, e, K, W):
+    """whether lcrec_rq_beam takes a lone level of K codes: a call at n = 0, past every check and launching nothing.  (The library
+    itself is called: the binding never passes an empty tensor on.)"""
+    import ctypes
+    import extend_cases as ec
+    lib = hip._lib.load()
+    p = ctypes.c_void_p(torch.zeros(64, device=DEV).data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call():
+        hip._lib.check(lib.lcrec_rq_beam(p, 0, e, p, hip.ops._ints([K]), 1, W, p, p, p, p, None, 0, stream), "lcrec_rq_beam")
+    try:
+        ec.in_thread(call)                                                           # (the last-error text stays in that thread)
+        return True
+    except hip.LcrecError as refusal:
+        assert f"level 0 (K={K}, e={e}) does not fit" in str(refusal), str(refusal)
+        return False
+
+
+@pytest.mark.parametrize("e", bc.ES)
+def test_the_largest_level_of_the_table_is_the_largest_the_entry_admits(hip, e):
+    """audit_cases.LARGEST, derived from the LDS formula, against the entry itself at the widest beam: K is admitted, K + 1 refused as
+    not fitting (the width plays no part: the narrowest beam draws the same line)."""
+    import audit_cases as ac
+    found = ac.largest_admitted(lambda K: _admits(hip, e, K, 8))
+    print("rq_beam e", e, "largest admitted K", found, "(derived:", ac.LARGEST[e], ")")
+    assert found == ac.LARGEST[e] == ac.largest_level(e) and not _admits(hip, e, found + 1, 8)
+    assert _admits(hip, e, found, 1) and not _admits(hip, e, found + 1, 1)
+    assert all((e, (found,), W, bc.N_FOR_ALL_KS) in bc.shapes() for W in bc.WS_LARGEST)   # ... and the grid above runs it
+
+
 def test_exact_ties_go_by_parent_then_code(hip, oracle):
     z, cbs = bc.tie_case()
     got = run(hip, z, cbs, 4)

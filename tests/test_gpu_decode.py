@@ -127,14 +127,14 @@ def test_item_loops_make_more_than_one_trip(hip, oracle, row):
     check(got, decode_ref(idx, cbs, decoder[1], decoder[2], None, None, x), row)
 
 
-@pytest.mark.parametrize("L", [1, 3])
+@pytest.mark.parametrize("L", [1, 3, ac.MAX_LEVELS])
 def test_out_of_range_codes_are_clamped_and_flagged(hip, oracle, L):
     cbs, idx, level, K, decoder, x = dc.out_of_range_case(L)
     got = run(hip, idx, cbs, decoder, x)
     check(got, decode_ref(idx, cbs, decoder[1], decoder[2], decoder[3], decoder[4], x), ("out of range", L))
     assert np.array_equal(got["flags"], np.where(np.arange(len(idx)) % 4 == 3, 0, 1 << level))
     clamped = idx.copy()
-    clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, 5]), len(idx))
+    clamped[:, level] = np.resize(np.array([0, K - 1, K - 1, min(5, K - 1)]), len(idx))
     again = run(hip, clamped, cbs, decoder, x)
     for name in ("xq", "out", "err", "err_l1"):
         assert same_bits(got[name], again[name]), name

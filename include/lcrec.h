@@ -808,6 +808,63 @@ int lcrec_rq_beam(const float *z, int64_t n, int e, const float *codebooks, cons
                   int64_t *tuples_out, float *score_out, float *err_out, float *resid_out,
                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* Beam finishing pass: colliding items move to their next-best WHOLE tuple that nobody holds.  lcrec_finish_nearest_free and the
+ * reference's Sinkhorn rounds change the last code of a tuple and lcrec_spill_nearest_free the last two; lcrec_rq_beam lists the
+ * `width` best whole tuples of an item, each with its exact quantisation error.  This entry (opt-in, --finish beam; beyond the
+ * reference) lets every item that shares its tuple walk down that list.  It is purely combinatorial: it compares tuples and the
+ * errors it is given, and computes no distance.
+ *
+ * The rule.  Items 0 .. n-1 hold the tuples idx[i]; codes are clamped into their level for comparison exactly as
+ * lcrec_collision_groups clamps them.  The caller lists the groups of shared tuples in the layout lcrec_collision_groups emits.
+ * M = n_members; member position j is item tuple_members[j], with err_held[j], the error of the tuple it holds (lcrec_rq_audit's
+ * err), and `width` candidates cand[j][b][0 .. L) with cand_err[j][b], b = 0 .. width-1 in preference order (lcrec_rq_beam's
+ * tuples and err of that item's latent).  A candidate with any code outside [0, K[l]) is dead -- lcrec_rq_beam's -1 rows are.
+ * Wherever two errors are compared a NaN counts as +inf.
+ *   1. Keepers and movers.  In each group the member with the smallest err_held keeps the tuple; a tie goes to the lowest item id.
+ *      The others are movers.  A member whose id is outside [0, n) takes no part.
+ *   2. Occupied set O.  It starts as the set of tuples held by any of the n items, those that collide with nobody included.
+ *   3. Rounds.  Every unplaced mover holds a pointer p, initially 0.  In a round it advances p past every candidate that is dead
+ *      or in O -- its own held tuple is in O and is skipped like any other -- and proposes the candidate at p.  A mover whose
+ *      pointer reaches `width` is unresolved and keeps its tuple.  Among the movers that propose the same tuple in a round the one
+ *      with the smallest cand_err of that candidate wins; a tie goes to the lowest item id.  The winner's row of idx becomes the
+ *      candidate, the tuple joins O and the winner is placed; the losers go to the next round with p + 1.  A round is synchronous:
+ *      proposals are read against O as it stood when the round began.  Rounds go on until nobody proposes: at most `width` rounds
+ *      with a proposal, because a loser's pointer strictly grows.
+ * So the rows of non-movers are bit-identical afterwards; a moved item holds a tuple no other item holds; with the groups of idx
+ * itself, n minus the number of distinct tuples afterwards equals `unresolved`; with width 1 a mover can only ever take candidate
+ * 0; and the result is a function of the inputs alone.
+ *
+ *   idx             device [n][L] int64, in/out (the whole row of an item that moves is rewritten); n < 2^32
+ *   K               host [L]; sum of ceil(log2 K[l]) <= 128 as for lcrec_collision_groups, more is LCREC_EUNSUPPORTED; 1 <= L <= 16
+ *   tuple_members, tuple_offsets, n_tuple_groups   device int64, the groups of idx as lcrec_collision_groups emits them: group g =
+ *                   members[off[g] .. off[g+1]), item ids ascending inside a group; n_members = off[n_tuple_groups] < 2^32
+ *   err_held        device [n_members] float
+ *   cand            device [n_members][width][L] int64;  cand_err  device [n_members][width] float
+ *   width           1, 2, 4 or 8
+ *   choice_out      device [n_members] int: -1 a keeper or a member that takes no part, b >= 0 moved to candidate b, -2 an
+ *                   unresolved mover
+ *   counters_out    device int64[4]: {movers, moved, unresolved, rounds with at least one proposal}, zeroed by the call
+ *   workspace       device, lcrec_finish_beam_workspace() bytes.  With N = max(n, 1), C = max(n_members * width, 1) and every part
+ *                   rounded up to 256 bytes: six arrays of N 8-byte words (the held keys: packed, between the two sorts, sorted;
+ *                   a low and a high word each), six arrays of C 8-byte words (the candidate keys likewise; the two between the
+ *                   sorts then hold every candidate's slot and every slot's winning word), C bytes (the slots' claimed flags),
+ *                   max(n_members, 1) ints (the movers' pointers), and behind them what rocPRIM's radix sort asks for max(N, C)
+ *                   pairs on this device
+ * Launches: pack and sort the held keys, pack and sort the candidate keys, one binary search per candidate in each (is it held;
+ * which slot do equal candidates share), one wave per group for the keepers, then the fixed `width` rounds of two launches -- a
+ * round without a proposer does nothing -- and one thread for `unresolved`.  The only atomics are min, max and integer add, so
+ * the result does not depend on the order of arrival.  n_tuple_groups == 0, n_members == 0 or n == 0: no launch, the counters are
+ * zeroed and choice_out is not touched.  The int64 arrays and the workspace 8-byte aligned, the others 4-byte.  The workspace may
+ * hold anything on entry.  No allocation, no host synchronisation, capturable; every launch is on `stream`.  Argument errors
+ * (LCREC_EINVAL: a NULL pointer, width, L, K[l] < 1, a negative count, misalignment; LCREC_EWORKSPACE) are reported before the device
+ * is touched, with a last-error text that names the argument.  Traced as "finish_beam", one bracket per call.
+ * lcrec_finish_beam_workspace returns 0 for arguments lcrec_finish_beam refuses. */
+size_t lcrec_finish_beam_workspace(int64_t n, int64_t n_members, int L, int width);
+int lcrec_finish_beam(int64_t *idx, int64_t n, int L, const int *K, const int64_t *tuple_members, const int64_t *tuple_offsets,
+                      int64_t n_tuple_groups, int64_t n_members, const float *err_held, const int64_t *cand,
+                      const float *cand_err, int width, int *choice_out, int64_t *counters_out, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* Decode pass: GIVEN tuples back to embeddings, and the reconstruction error of every item.  lcrec_encode_assign goes from an
  * embedding to a tuple and lcrec_rq_audit prices a tuple in latent space; this entry goes the way back -- codes, their sum, the
  * decoder MLP (RQVAE.forward's `out = self.decoder(x_q)`, index/models/rqvae.py:57-66, which the reference runs only inside a

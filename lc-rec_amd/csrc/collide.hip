@@ -12,7 +12,7 @@
 //   3. segment heads -> every item learns the id of its tuple's FIRST item (stable sort => minimum id);
 //   4. stable sort of (first id, item id): groups now lie in first-occurrence order, ids ascending;
 //   5. segment sizes, compaction of the members of groups with size >= 2, group offsets, counters.
-#include "common.h"
+#include "tuple_key.h"
 
 #include <cstring>
 
@@ -21,23 +21,12 @@
 
 namespace lcrec {
 
-struct PackDesc {
-    int L;
-    int bits[LCREC_MAX_LEVELS];
-    int K[LCREC_MAX_LEVELS];
-};
-
 __global__ void pack_keys_kernel(const int64_t *__restrict__ idx, int64_t n, PackDesc d, uint64_t *klo, uint64_t *khi,
                                  int64_t *ids)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    unsigned __int128 key = 0;
-    for (int l = 0; l < d.L; ++l) {
-        int64_t v = idx[i * d.L + l];
-        v = v < 0 ? 0 : (v >= d.K[l] ? d.K[l] - 1 : v);
-        key = (key << d.bits[l]) | (unsigned __int128)(uint64_t)v;
-    }
+    const unsigned __int128 key = pack_tuple_key(idx + i * d.L, d);
     klo[i] = (uint64_t)key;
     khi[i] = (uint64_t)(key >> 64);
     ids[i] = i;
@@ -137,13 +126,9 @@ static int collision_plan(int64_t n, int L, const int *K, lcrec_collision_plan *
 {
     *p = lcrec_collision_plan{};
     if (n < 0 || L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "collision_groups: bad n or L");
-    for (int l = 0; K && l < L; ++l) {
+    for (int l = 0; K && l < L; ++l)
         if (K[l] < 1) return fail(LCREC_EINVAL, "collision_groups: K[%d]=%d", l, K[l]);
-        int b = 0;
-        while ((1LL << b) < K[l]) ++b;
-        p->bits[l] = b;
-        p->total_bits += b;
-    }
+    if (K) p->total_bits = key_bits(K, L, p->bits);
     if (p->total_bits > 128)
         return fail(LCREC_EUNSUPPORTED, "collision_groups: tuples need %d bits (> 128)", p->total_bits);
     p->lo_bits = p->total_bits > 64 ? 64 : (p->total_bits > 0 ? p->total_bits : 1);

@@ -28,6 +28,10 @@ Documented divergences from the reference script:
   * --beam W (off by default: W = 1) goes BEYOND the reference, which is greedy throughout: pass 1 walks the quantiser with a beam of
     W partial tuples per item (ops.rq_beam) and every item gets the best whole tuple found, or its greedy one where that is better;
     the rounds and the passes above then run on those tuples and their residuals (assign_all);
+  * --finish beam (off by default) goes BEYOND the reference and beyond --finish nearest_free, which only ever changes a last code:
+    every item that still shares its tuple after the rounds moves to the next-best WHOLE tuple nobody holds, out of a beam of
+    --finish_width tuples of its own latent (beam_finish_collisions); nearest_free then runs on what that leaves.  --rounds N sets
+    the number of conflict rounds before it (20, the reference's; 0 keeps every item that collides with nobody on its pass-1 tuple);
   * it stores tokens in fixed-width numpy unicode arrays (:98-99) which silently truncate a
     replacement longer than anything seen in pass 1; integer tuples are kept here, and a warning is
     logged if a run ever hits that case (the reference's output would be corrupt there).
@@ -49,7 +53,8 @@ from .rqvae import RQVAE
 
 PREFIX = ["<{}_{{}}>".format(chr(ord("a") + i)) for i in range(26)]   # "<a_{}>", "<b_{}>", ... (:83 has a..e)
 MAX_ROUNDS = 20                                                        # :110
-FINISH_MODES = ("none", "nearest_free")
+FINISH_MODES = ("none", "nearest_free", "beam")
+FINISH_WIDTHS = (2, 4, 8)
 log = logging.getLogger(__name__)
 
 
@@ -228,6 +233,50 @@ def finish_collisions(model, idx, resid_last, ks):
     members, offsets, buckets, largest = _prefix_groups(idx, ks, L - 1)
     moved, unresolved = ops.finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets)
     return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
+
+
+# ---- opt-in: what the rounds leave colliding moves to its next-best whole tuple (--finish beam) -----------------------------------
+@torch.no_grad()
+def beam_finish_collisions(model, idx, latents, resid_last, ks, width, resid_prev=None):
+    """Beyond the reference: ops.finish_beam over the shared tuples -- include/lcrec.h, lcrec_finish_beam, states the rule.  The
+    members of the shared tuples, and only they, are walked through ops.rq_beam (their `width` best whole tuples) and ops.rq_audit
+    (the error of the tuple they hold); of every shared tuple the member with the smallest error keeps it and the others move to the
+    first tuple of their list that nobody holds.  latents: pass 1's latents, float32 [n, e] (or the list of its chunks).  Mutates
+    idx (the rows of the items that move) and resid_last -- and resid_prev, the residual entering level L-2, when given -- for those
+    rows: the residuals of the tuple's prefix, as assign_all computes them for a chosen tuple, so that finish_collisions and
+    spill_collisions behind this pass see the right ones.  Returns dict(movers, moved, unresolved, rounds, err_moved_sum): the last
+    the float64 sum of the moved items' new quantisation errors.  A function of its inputs alone."""
+    if width not in ops.BEAM_WIDTHS:
+        raise ValueError(f"width={width!r}: one of {ops.BEAM_WIDTHS}")
+    out = {"movers": 0, "moved": 0, "unresolved": 0, "rounds": 0, "err_moved_sum": 0.0}
+    found = ops.collision_groups(idx, ks, want_groups="device")
+    if found["n_groups"] == 0:
+        return out
+    if isinstance(latents, (list, tuple)):
+        latents = torch.cat(latents)
+    cbs = [q.embedding.weight.detach() for q in model.rq.vq_layers]
+    flat, _ = ops.flatten_codebooks(cbs)
+    members = found["members"]
+    z = latents.index_select(0, members)
+    beams = ops.rq_beam(z, flat, ks, width)
+    err_held = ops.rq_audit(z, flat, ks, idx.index_select(0, members))["err"]
+    choice, counters = ops.finish_beam(idx, ks, members, found["offsets"], err_held, beams["tuples"], beams["err"])
+    out.update(counters)
+    pos = torch.nonzero(choice >= 0).flatten()
+    if pos.numel():
+        items, zm = members[pos], z.index_select(0, pos)
+        out["err_moved_sum"] = float(beams["err"][pos, choice[pos].long()].double().sum())
+        L = idx.shape[1]
+        held = idx.index_select(0, items)
+        for depth, resid in ((L - 1, resid_last), (L - 2, resid_prev)):
+            if resid is None or depth < 0:
+                continue
+            if depth == 0:
+                resid[items] = zm
+            else:
+                pflat, pks = ops.flatten_codebooks(cbs[:depth])
+                resid[items] = ops.rq_audit(zm, pflat, pks, held[:, :depth], want_resid=True)["resid"]
+    return out
 
 
 # ---- opt-in: new items around an index file whose tuples are frozen (--extend BASE.index.json) -------------------------------------
@@ -579,10 +628,17 @@ def sharded_assign(ctx, data, assign_fn, device):
 
 
 def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=True, ctx=None, trust_checkpoint=False,
-             recheck=False, finish="none", extend=None, spill=False, audit=False, beam=1):
+             recheck=False, finish="none", extend=None, spill=False, audit=False, beam=1, rounds=MAX_ROUNDS, finish_width=8):
     """Whole flow of generate_indices.py:51-145.  Returns a dict of the statistics it prints.
     recheck: re-evaluate the near-tie items of pass 1 in the reference's CPU operation order (recheck_neartie).
-    finish: "none" (the reference's bytes) or "nearest_free" (finish_collisions after the rounds; beyond the reference).
+    finish: "none" (the reference's bytes), "nearest_free" (finish_collisions after the rounds; beyond the reference) or "beam":
+        beam_finish_collisions after the rounds with a beam of `finish_width` (2, 4 or 8) tuples per colliding item, then
+        finish_collisions on what it leaves; `spill` stays available behind it.  The statistics gain finish_beam_width,
+        finish_beam_movers, finish_beam_moved, finish_beam_unresolved and finish_beam_rounds; finish_moved and finish_unresolved
+        keep their meaning for the nearest-free step.  `audit` skips the foreign-file warning for such a run: these tuples leave
+        the greedy path early by design.  Refused with ValueError, as `spill` is, with `extend`, `recheck` and under torchrun.
+    rounds: the number of conflict rounds at most (resolve_collisions' max_rounds), 20 = the reference's; 0 runs none, and
+        rounds=0 with finish="beam" moves only the items that collide in pass 1.
 
     extend: path of an existing `.index.json` whose items are the first rows of the data file: their tuples are kept and only
         the new rows are indexed, around them (generate_extended, which says why neither the conflict rounds nor `finish` run).
@@ -619,8 +675,21 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
             raise ValueError("--beam with --recheck_neartie is not supported: the re-evaluation reproduces the reference's greedy walk")
         if ctx.enabled:
             raise ValueError("--beam under torchrun is not supported: run it in a single process")
+    if not (isinstance(rounds, int) and rounds >= 0):
+        raise ValueError(f"--rounds {rounds!r}: an integer >= 0")
+    if finish_width not in FINISH_WIDTHS:
+        raise ValueError(f"--finish_width {finish_width!r}: one of {FINISH_WIDTHS}")
+    if finish == "beam":
+        if extend is not None:
+            raise ValueError("--finish beam with --extend is not supported: the new items are indexed around frozen tuples by the "
+                             "distance rule alone")
+        if recheck:
+            raise ValueError("--finish beam with --recheck_neartie is not supported: the beam starts from the latents of pass 1, which "
+                             "the re-evaluation does not patch")
+        if ctx.enabled:
+            raise ValueError("--finish beam under torchrun is not supported: run it in a single process")
     if spill:
-        if extend is None and finish != "nearest_free":
+        if extend is None and finish not in ("nearest_free", "beam"):
             raise ValueError("--spill runs over what --finish nearest_free or --extend leave unresolved: give one of them")
         if recheck:
             raise ValueError("--spill with --recheck_neartie is not supported: the residuals of level L-2 that the re-evaluation "
@@ -657,7 +726,7 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         print(model)
     ties = {}
     prev = []                                              # spill: the residual entering level L-2 (one process: nothing to gather)
-    latents = [] if audit else None                        # audit: pass 1's latents (one process too)
+    latents = [] if audit or finish == "beam" else None    # audit, finish beam: pass 1's latents (one process too)
     beamed = {} if beam > 1 else None                      # beam: pass 1's greedy tuples and what the beam changed (one process too)
 
     def assign(x):
@@ -697,9 +766,17 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         if verbose:
             print(n_groups)
 
-    idx, history = resolve_collisions(model, idx, resid_last, ks, on_round=show, ctx=ctx)
+    idx, history = resolve_collisions(model, idx, resid_last, ks, max_rounds=rounds, on_round=show, ctx=ctx)
     finished = {"moved": 0, "unresolved": 0}
-    if finish == "nearest_free":
+    beam_finished = {}
+    if finish == "beam":
+        done = beam_finish_collisions(model, idx, latents, resid_last, ks, finish_width, resid_prev=prev[0] if spill else None)
+        beam_finished = {"finish_beam_width": finish_width, "finish_beam_movers": done["movers"], "finish_beam_moved": done["moved"],
+                         "finish_beam_unresolved": done["unresolved"], "finish_beam_rounds": done["rounds"]}
+        log.info("--finish beam: of %d items that share a tuple with a better holder %d moved to a free whole tuple out of a beam of "
+                 "%d (%d rounds, their quantisation error sums to %.6g), %d are left to the nearest free last-level code",
+                 done["movers"], done["moved"], finish_width, done["rounds"], done["err_moved_sum"], done["unresolved"])
+    if finish in ("nearest_free", "beam"):
         finished = finish_collisions(model, idx, resid_last, ks)          # every rank, on its identical copy: no collective
         if lead:
             log.info("--finish nearest_free: %d items moved to the nearest free last-level code, %d unresolved "
@@ -719,12 +796,13 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
              "rounds": len(history), "groups_per_round": history, "neartie_items": neartie_items,
              "neartie_tau": ops.NEARTIE_TAU, "rechecked_items": rechecked[0], "recheck_changed": rechecked[1],
              "finish": finish, "finish_moved": finished["moved"], "finish_unresolved": finished["unresolved"]}
+    stats.update(beam_finished)
     if spill:
         stats.update(spilled)
     stats.update(beam_stats)
     if audit:
         greedy = torch.cat(beamed["greedy"]) if beam > 1 else first_pass
-        _audit_and_log(model, latents, greedy, ties["neartie"], idx, stats, foreign_check=beam == 1)
+        _audit_and_log(model, latents, greedy, ties["neartie"], idx, stats, foreign_check=beam == 1 and finish != "beam")
     if lead:
         log.info("near-tie items in pass 1: %d of %d (top-2 code gap <= %.3g x distance magnitude at some level); only "
                  "these could receive a different tuple from a CPU run of the reference", neartie_items, n, ops.NEARTIE_TAU)
@@ -755,7 +833,16 @@ def parse_args(argv=None):
     ap.add_argument("--finish", choices=FINISH_MODES, default="none",
                     help="after the conflict rounds: none = write what still collides, as the reference does (byte-identical "
                          "output); nearest_free = every item that still shares its tuple gets the nearest free last-level code "
-                         "(goes beyond the reference; only those items' last token changes)")
+                         "(goes beyond the reference; only those items' last token changes); beam = every such item first "
+                         "moves to the next-best whole tuple nobody holds, out of a beam of --finish_width tuples of its own, "
+                         "and nearest_free runs on what that leaves (beyond the reference; not with --extend, --recheck_neartie or "
+                         "torchrun)")
+    ap.add_argument("--finish_width", type=int, choices=FINISH_WIDTHS, default=8, metavar="W",
+                    help="--finish beam: the number of whole tuples listed for every colliding item (2, 4 or 8; default 8).  "
+                         "Independent of --beam, which shapes pass 1; both may be given")
+    ap.add_argument("--rounds", type=int, default=MAX_ROUNDS, metavar="N",
+                    help="the number of Sinkhorn conflict rounds at most (default 20, the reference's; 0 = none: with --finish beam "
+                         "or nearest_free only the items that collide in pass 1 then leave their pass-1 tuple)")
     ap.add_argument("--extend", type=str, default=None, metavar="BASE.index.json",
                     help="the data file holds a catalogue that has grown: its first N0 rows are the items of BASE.index.json, which "
                          "keep their tuples byte for byte; only the rows after them are indexed, each new item keeping its tuple "
@@ -787,7 +874,7 @@ def main(argv=None):
     try:
         return generate(a.ckpt_path, out, device=a.device, data_path=a.data_path, ctx=ctx,
                         trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish, extend=a.extend,
-                        spill=a.spill, audit=a.audit, beam=a.beam)
+                        spill=a.spill, audit=a.audit, beam=a.beam, rounds=a.rounds, finish_width=a.finish_width)
     finally:
         ldist.shutdown(ctx)
 

@@ -1126,6 +1126,65 @@ def spill_nearest_free(idx, n_frozen, resid_prev, resid_last, cb_prev, cb_last, 
     return moved, unresolved
 
 
+def finish_beam(idx, ks, members, offsets, err_held, cand, cand_err, counters_out=None, choice_out=None, workspace=None):
+    """The beam finishing pass (lcrec_finish_beam of include/lcrec.h, which states the rule): of every shared tuple -- group
+    `members[offsets[g]:offsets[g+1]]`, ids ascending -- the member with the smallest err_held keeps it and the others move, in
+    synchronous rounds, to the first candidate of their own list that no item holds and no other mover has taken.
+
+    idx int64 [n, L] is updated IN PLACE (the rows of the items that move); members / offsets are int64 device tensors in
+    collision_groups' "device" layout over the full idx; err_held float32 [M], cand int64 [M, width, L] and cand_err float32
+    [M, width] go by member POSITION (M = members.numel()): rq_audit's err of the held tuple and rq_beam's tuples and err of that
+    item's latent.  width in BEAM_WIDTHS.
+    Returns (choice int32 [M]: -1 keeper or no part, b >= 0 moved to candidate b, -2 unresolved; dict of movers, moved, unresolved,
+    rounds).  counters_out: an int64 [4] tensor on idx's device that receives the four counters instead; the binding then reads
+    nothing back and returns (choice, None) -- the form of the call that a graph capture can record, given choice_out and workspace
+    too.  choice_out: an int32 tensor of at least M elements, written instead of a fresh one (it may be LARGER, so that a test can
+    look at what lies past the end).  workspace: a uint8 device tensor of at least lcrec_finish_beam_workspace's bytes, passed as
+    the workspace as it is, its size included; None: the binding's own grow-only buffer of the stream."""
+    lib = _lib.load()
+    n, L = _inplace_idx(idx)
+    dev = idx.device
+    members, offsets = _group_table(members, offsets)
+    err_held, cand_err = _dev(err_held, "err_held"), _dev(cand_err, "cand_err")
+    M = members.numel()
+    if not (isinstance(cand, torch.Tensor) and cand.is_cuda and cand.dtype == torch.int64 and cand.dim() == 3 and cand.is_contiguous()
+            and cand.shape[0] == M and cand.shape[2] == L):
+        raise _lib.LcrecError(f"cand must be a contiguous int64 [{M}, width, {L}] device tensor (one list per member of idx {(n, L)})")
+    width = int(cand.shape[1])
+    if width not in BEAM_WIDTHS:
+        raise _lib.LcrecError(f"width={width!r} (supported: 1, 2, 4, 8)")
+    if tuple(err_held.shape) != (M,) or tuple(cand_err.shape) != (M, width):
+        raise _lib.LcrecError(f"err_held {tuple(err_held.shape)} and cand_err {tuple(cand_err.shape)} do not go with cand "
+                              f"{tuple(cand.shape)}: one error per member and per candidate")
+    if len(ks) != L:
+        raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}]")
+    if counters_out is None:
+        counters = torch.empty(4, dtype=torch.int64, device=dev)
+    elif (isinstance(counters_out, torch.Tensor) and counters_out.device == dev and counters_out.dtype == torch.int64
+          and tuple(counters_out.shape) == (4,) and counters_out.is_contiguous()):
+        counters = counters_out
+    else:
+        raise _lib.LcrecError(f"counters_out must be a contiguous int64 [4] tensor on idx's device ({dev})")
+    if choice_out is None:
+        choice_out = torch.full((M,), -1, dtype=torch.int32, device=dev)   # (no group: the library does not touch it)
+    elif not (isinstance(choice_out, torch.Tensor) and choice_out.device == dev and choice_out.dtype == torch.int32
+              and choice_out.dim() == 1 and choice_out.is_contiguous() and choice_out.numel() >= M):
+        raise _lib.LcrecError(f"choice_out must be a contiguous int32 tensor on idx's device with at least {M} elements")
+    need = lib.lcrec_finish_beam_workspace(n, M, L, width)
+    if workspace is not None:
+        workspace = _own_workspace(workspace, dev, need, "lcrec_finish_beam_workspace")
+    with _on(dev):
+        ws = workspace if workspace is not None else _workspace(need, dev)
+        rc = lib.lcrec_finish_beam(_ptr(idx), n, L, _ints(ks), _ptr(members), _ptr(offsets), max(offsets.numel() - 1, 0), M,
+                                   _ptr(err_held), _ptr(cand), _ptr(cand_err), width, _ptr(choice_out), _ptr(counters), _ptr(ws),
+                                   ws.numel(), _stream_ptr())
+    _lib.check(rc, "lcrec_finish_beam")
+    if counters_out is not None:
+        return choice_out[:M], None
+    movers, moved, unresolved, rounds = counters.tolist()
+    return choice_out[:M], {"movers": movers, "moved": moved, "unresolved": unresolved, "rounds": rounds}
+
+
 def rq_audit(z, codebooks_flat, ks, idx, want_best=False, want_resid=False):
     """The index audit (lcrec_rq_audit of include/lcrec.h, which states the rule): the GIVEN tuples `idx` walked through the
     residual quantiser from the latents z.  Per item and level: the distance of the held code, the best distance and the held

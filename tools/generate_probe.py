@@ -8,6 +8,7 @@ pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing
     python tools/generate_probe.py --audit                     # then the index audit of the tuples about to be written (--audit)
     python tools/generate_probe.py --decode                    # then the decode pass over them: tuples -> embeddings -> error per item
     python tools/generate_probe.py --beam 2,4,8                # then the beam-search quantiser (--beam W) at each width over pass 1's latents
+    python tools/generate_probe.py --finish_beam 2,4,8         # then the beam finishing step (--rounds 0 --finish beam) at each width on pass 1's tuples
 """
 import argparse
 import os
@@ -86,6 +87,11 @@ def main():
                     "--beam W) over pass 1's latents at each width given: one warm-up call, then --audit_runs timed ones, the median "
                     "of the rq_beam trace brackets reported beside pass 1's rq_assign and one rq_audit over the same rows in the same "
                     "run, the achieved fma rate against the fp32 vector peak, and what the chosen tuples change")
+    ap.add_argument("--finish_beam", type=str, default="", metavar="W[,W...]", help="time the beam finishing step (generate --rounds 0 "
+                    "--finish beam --finish_width W) on pass 1's tuples at each width given: one warm-up, then --audit_runs timed runs "
+                    "on fresh copies, medians of the whole step (beam_finish_collisions), of lcrec_finish_beam alone and of the "
+                    "members-only rq_beam by the trace brackets, beside the conflict rounds and the nearest-free pass of this run, "
+                    "and the quantisation error of both flows against the greedy tuples'")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.manual_seed(2024)
@@ -314,6 +320,53 @@ def main():
                 f"{int(info['kept_greedy'].sum())}, collision rate of the chosen tuples {rate1:.6f}")
             del chosen, info
         del latent
+    fbeam_lines = []
+    if a.finish_beam:
+        lat = []
+        (greedy, resid0, _), _ = timed(lambda: gen.assign_all(model, x, latents=lat))
+        flat, _ = ops.flatten_codebooks([q.embedding.weight.detach() for q in model.rq.vq_layers])
+        latent = torch.cat(lat)
+        del lat
+        err_sum = lambda t: float(torch.nan_to_num(ops.rq_audit(latent, flat, ks, t)["err"], nan=0.0, posinf=0.0).double().sum())
+        e_greedy, e_today = err_sum(greedy), err_sum(idx)
+        shared = ops.collision_groups(greedy, ks, want_groups="device")
+        fbeam_lines = [f"finish beam: pass 1 leaves {int(shared['members'].numel())} items in {shared['n_groups']} shared tuples "
+                       f"(collision rate {first['collision_rate']:.6f}); yardsticks of this run: conflict rounds {t_rounds * 1e3:.1f} ms, finish "
+                       f"nearest_free {t_finish * 1e3:.2f} ms; quantisation error of today's rounds + nearest_free"
+                       f"{' (+ spill)' if a.spill else ''}: {e_today / e_greedy:.4f} x greedy"]
+        del shared
+        for W in [int(w) for w in a.finish_beam.split(",") if w]:
+            def step():
+                i, r = greedy.clone(), resid0.clone()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                done = gen.beam_finish_collisions(model, i, latent, r, ks, W)
+                torch.cuda.synchronize()
+                return i, r, done, time.perf_counter() - t0
+            step()                                         # warm-up
+            walls, runs = [], []
+            for _ in range(max(a.audit_runs, 1)):
+                ops.trace_enable(True)
+                i, r, done, t = step()
+                runs.append(ops.trace_collect())
+                ops.trace_enable(False)
+                walls.append(t)
+            med = lambda name: float(np.median([q.get(name, (0, 0.0))[1] for q in runs]))
+            e_beam = err_sum(i)
+            fin2, t_fin2 = timed(lambda: gen.finish_collisions(model, i, r, ks))
+            rate2 = ops.collision_groups(i, ks, want_groups=False)["collision_rate"]
+            whole = float(np.median(walls)) * 1e3
+            parts = {name: med(name) for name in ("finish_beam", "rq_beam", "rq_audit", "collision_groups")}
+            fbeam_lines.append(
+                f"  --finish_width {W}: whole step {whole:.2f} ms (median of {len(walls)}, min {min(walls) * 1e3:.2f}, max "
+                f"{max(walls) * 1e3:.2f}) = {whole / (t_rounds * 1e3):.2f} x the conflict rounds; by the trace brackets lcrec_finish_beam "
+                f"{parts['finish_beam']:.3f} ms, members-only rq_beam {parts['rq_beam']:.3f} ms, rq_audit {parts['rq_audit']:.3f} ms, "
+                f"collision_groups {parts['collision_groups']:.3f} ms (largest: {max(parts, key=parts.get)}); movers {done['movers']}, moved "
+                f"{done['moved']}, unresolved {done['unresolved']}, rounds {done['rounds']}; error {e_beam / e_greedy:.4f} x greedy; then "
+                f"nearest_free {t_fin2 * 1e3:.2f} ms moved {fin2['moved']}, unresolved {fin2['unresolved']}: collision rate {rate2:.6f}, "
+                f"error {err_sum(i) / e_greedy:.4f} x greedy")
+            del i, r
+        del latent, greedy, resid0
     _, t_json = timed(lambda: gen.dump_index_json(idx, a.out))
     size = os.path.getsize(a.out)
     extend_lines = []
@@ -341,7 +394,7 @@ def main():
           f"largest {fin['largest_bucket']} items, moved {fin['moved']}, unresolved {fin['unresolved']}")
     print("  kernels: " + ", ".join(f"{k} {v[1]:.2f} ms/{v[0]}" for k, v in sorted(ftrace.items(), key=lambda kv: -kv[1][1])))
     print(f"  collision rate {final['collision_rate']:.6f} -> {finished['collision_rate']:.6f}")
-    for line in spill_lines + audit_lines + decode_lines + beam_lines:
+    for line in spill_lines + audit_lines + decode_lines + beam_lines + fbeam_lines:
         print(line)
     print(f".index.json ({size / 1e6:.0f} MB)     {t_json * 1e3:9.1f} ms   {a.items / t_json / 1e6:7.2f} M items/s (D2H + text + write)")
     for line in extend_lines:

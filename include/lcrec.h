@@ -865,6 +865,41 @@ int lcrec_finish_beam(int64_t *idx, int64_t n, int L, const int *K, const int64_
                       const float *cand_err, int width, int *choice_out, int64_t *counters_out, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* Beam finishing pass for a catalogue that grows: lcrec_finish_beam with the first n_frozen items frozen (opt-in, --extend with
+ * --extend_finish beam; beyond the reference).  The frozen items are the base file's: their tuples are the vocabulary something
+ * downstream was trained on, and no latent, error or candidate exists for them.  A new item that meets a taken tuple walks down its
+ * own list of whole tuples, where lcrec_extend_nearest_free can only give it another last code; that pass then runs on what this
+ * one counts as unresolved.
+ *
+ * The rule is lcrec_finish_beam's, with these changes.  Items with id < n_frozen are frozen: they never move, and nothing is read
+ * for them from err_held, cand or cand_err -- the rows of a frozen member there may hold anything, and its candidates are dead.
+ *   1. Keepers and movers.  Per group, among the members whose id lies in [0, n) (the holders): if any holder is frozen, every new
+ *      holder is a mover.  Otherwise the new holder with the smallest err_held keeps the tuple (a NaN counts as +inf, a tie goes to
+ *      the lowest item id) and the others are movers.  A group with no new holder has no mover, however its frozen items collide;
+ *      a group with fewer than two holders has none.
+ *   2. Occupied set O, unchanged: every tuple held by any of the n items, the frozen ones included.
+ *   3. Rounds, unchanged: only movers propose.
+ * So rows below n_frozen, and the rows of non-movers, are bit-identical afterwards; a moved item holds a tuple no other item holds;
+ * with the groups of idx itself, n minus the number of distinct tuples afterwards equals the number colliding among the frozen
+ * items alone plus `unresolved`; with n_frozen == 0, idx, choice_out and all four counters are lcrec_finish_beam's, bit for bit.
+ *
+ * Arguments as lcrec_finish_beam, except:
+ *   n_frozen        0 .. n
+ *   err_held, cand, cand_err   by member position as there; the positions of frozen members are never read
+ *   choice_out      a frozen member gets -1
+ *   workspace       lcrec_extend_finish_beam_workspace() bytes: lcrec_finish_beam_workspace's formula
+ * n_frozen == n: no launch, the counters are zeroed and choice_out is not touched, as for n_tuple_groups == 0.  Otherwise the same
+ * launches on `stream`: the candidate kernels look up the member a candidate belongs to before they look at its row, and the
+ * keepers' wave reduction also counts the frozen holders and picks the keeper among the new ones.  The only atomics are min, max
+ * and integer add.  No allocation, no host synchronisation, capturable.  Argument errors as lcrec_finish_beam, and n_frozen outside
+ * 0 .. n (LCREC_EINVAL), are reported before the device is touched, with a last-error text that names the argument.  Traced as
+ * "extend_finish_beam", one bracket per call.  lcrec_extend_finish_beam_workspace returns 0 for arguments the entry refuses. */
+size_t lcrec_extend_finish_beam_workspace(int64_t n, int64_t n_members, int L, int width);
+int lcrec_extend_finish_beam(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const int64_t *tuple_members,
+                             const int64_t *tuple_offsets, int64_t n_tuple_groups, int64_t n_members, const float *err_held,
+                             const int64_t *cand, const float *cand_err, int width, int *choice_out, int64_t *counters_out,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* Decode pass: GIVEN tuples back to embeddings, and the reconstruction error of every item.  lcrec_encode_assign goes from an
  * embedding to a tuple and lcrec_rq_audit prices a tuple in latent space; this entry goes the way back -- codes, their sum, the
  * decoder MLP (RQVAE.forward's `out = self.decoder(x_q)`, index/models/rqvae.py:57-66, which the reference runs only inside a

@@ -30,7 +30,7 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
                                            "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free",
                                            "spill_nearest_free", "spill_keepers", "rq_audit", "rq_decode_gather",
-                                           "recon_row_error", "rq_beam", "finish_beam"};
+                                           "recon_row_error", "rq_beam", "finish_beam", "extend_finish_beam"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;
@@ -671,7 +671,7 @@ LCREC_API int lcrec_rq_beam(const float *z, int64_t n, int e, const float *codeb
 
 LCREC_API size_t lcrec_finish_beam_workspace(int64_t n, int64_t n_members, int L, int width)
 {
-    return finish_beam_workspace(n, n_members, L, width);
+    return finish_beam_workspace(false, n, n_members, L, width);
 }
 
 LCREC_API int lcrec_finish_beam(int64_t *idx, int64_t n, int L, const int *K, const int64_t *tuple_members, const int64_t *tuple_offsets,
@@ -679,8 +679,22 @@ LCREC_API int lcrec_finish_beam(int64_t *idx, int64_t n, int L, const int *K, co
                                 const float *cand_err, int width, int *choice_out, int64_t *counters_out, void *workspace,
                                 size_t workspace_bytes, void *stream)
 {
-    return finish_beam(idx, n, L, K, tuple_members, tuple_offsets, n_tuple_groups, n_members, err_held, cand, cand_err, width,
-                       choice_out, counters_out, workspace, workspace_bytes, (hipStream_t)stream);
+    return finish_beam(false, idx, n, 0, L, K, tuple_members, tuple_offsets, n_tuple_groups, n_members, err_held, cand, cand_err,
+                       width, choice_out, counters_out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+LCREC_API size_t lcrec_extend_finish_beam_workspace(int64_t n, int64_t n_members, int L, int width)
+{
+    return finish_beam_workspace(true, n, n_members, L, width);
+}
+
+LCREC_API int lcrec_extend_finish_beam(int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const int64_t *tuple_members,
+                                       const int64_t *tuple_offsets, int64_t n_tuple_groups, int64_t n_members,
+                                       const float *err_held, const int64_t *cand, const float *cand_err, int width,
+                                       int *choice_out, int64_t *counters_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return finish_beam(true, idx, n, n_frozen, L, K, tuple_members, tuple_offsets, n_tuple_groups, n_members, err_held, cand,
+                       cand_err, width, choice_out, counters_out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 LCREC_API int lcrec_bn_relu_forward(const float *t, int64_t n, int features, const float *gamma, const float *beta, float eps,

@@ -33,7 +33,8 @@ enum KernelId { K_LINEAR_128x128 = 0, K_LINEAR_128x64, K_LINEAR_128x32, K_RQ_ASS
                 K_VQ_DISTANCE, K_SINKHORN, K_SINKHORN_SMALL, K_APPLY_LEVEL, K_CODE_STATS, K_EMA_UPDATE, K_COLLISION,
                 K_LINEAR_PP, K_LINEAR_64x64, K_SINKHORN_SLAB, K_SINKHORN_TINY, K_BN_FWD, K_BN_BWD, K_RELU_BIAS_BWD, K_LOSS,
                 K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_FINISH, K_EXTEND, K_SPILL,
-                K_SPILL_KEEPERS, K_RQ_AUDIT, K_RQ_DECODE_GATHER, K_RECON_ROW_ERROR, K_RQ_BEAM, K_FINISH_BEAM, K_COUNT };
+                K_SPILL_KEEPERS, K_RQ_AUDIT, K_RQ_DECODE_GATHER, K_RECON_ROW_ERROR, K_RQ_BEAM, K_FINISH_BEAM,
+                K_EXTEND_FINISH_BEAM, K_COUNT };
 extern const char *const kKernelNames[K_COUNT];
 bool trace_on();
 void trace_begin(int kernel, hipStream_t stream);
@@ -293,10 +294,12 @@ int rq_audit(const float *z, int64_t n, int e, const float *codebooks, const int
 size_t rq_beam_workspace(int64_t n, int e, const int *K, int L, int width);
 int rq_beam(const float *z, int64_t n, int e, const float *codebooks, const int *K, int L, int width, int64_t *tuples_out,
             float *score_out, float *err_out, float *resid_out, void *workspace, size_t workspace_bytes, hipStream_t stream);
-size_t finish_beam_workspace(int64_t n, int64_t n_members, int L, int width);
-int finish_beam(int64_t *idx, int64_t n, int L, const int *K, const int64_t *tuple_members, const int64_t *tuple_offsets,
-                int64_t n_groups, int64_t n_members, const float *err_held, const int64_t *cand, const float *cand_err, int width,
-                int *choice_out, int64_t *counters_out, void *workspace, size_t workspace_bytes, hipStream_t stream);
+size_t finish_beam_workspace(bool frozen, int64_t n, int64_t n_members, int L, int width);
+// both entries: `frozen` selects lcrec_extend_finish_beam's checks, texts and trace name; lcrec_finish_beam passes n_frozen = 0
+int finish_beam(bool frozen, int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const int64_t *tuple_members,
+                const int64_t *tuple_offsets, int64_t n_groups, int64_t n_members, const float *err_held, const int64_t *cand,
+                const float *cand_err, int width, int *choice_out, int64_t *counters_out, void *workspace, size_t workspace_bytes,
+                hipStream_t stream);
 // decode.hip: the two kernels of lcrec_decode_tuples (abi.hip checks the arguments and walks the chunks)
 int rq_decode_gather(const int64_t *idx, int64_t idx_stride, int64_t n, int e, const float *codebooks, const int *K, int L,
                      float *q_out, uint32_t *flags_out, hipStream_t stream);

@@ -1,5 +1,6 @@
 // Beam finishing pass: colliding items move to their next-best WHOLE tuple nobody holds (lcrec_finish_beam; opt-in, generate
-// --finish beam).
+// --finish beam), and its frozen-aware form for a catalogue that grows (lcrec_extend_finish_beam; generate --extend --extend_finish
+// beam): one body, lcrec_finish_beam is n_frozen = 0.
 //
 // lcrec_finish_nearest_free changes a last code and lcrec_spill_nearest_free the last two; lcrec_rq_beam lists the W best whole
 // tuples of an item with their exact errors.  This pass brings the two together and goes BEYOND the reference: of every shared tuple
@@ -20,6 +21,10 @@
 //   5. unresolved = movers - moved.
 // The only atomics are min (the slots), max (the round count) and integer add (the counters): the result does not depend on the
 // order in which anything arrives.
+//
+// lcrec_extend_finish_beam: items with id < n_frozen never move and nothing of theirs is read from err_held, cand or cand_err.  Their
+// held tuples are packed and sorted with the others (O is every tuple held); their candidates are packed as dead without a look at
+// the row; in keepers a frozen holder is counted, takes no part in the reduction, and a group with one has no keeper.
 #include "rq_walk.h"
 #include "tuple_key.h"
 
@@ -71,13 +76,28 @@ __device__ __forceinline__ bool fb_live(const int64_t *__restrict__ row, const P
     return live;
 }
 
+// The three kernels that know of frozen items are compiled twice: FROZEN = false is the code for n_frozen == 0, without a trace of
+// them, and n_frozen is an argument of these three alone -- the 2 * width launches of the rounds take the arguments they took before
+// there was a frozen form, and lcrec_finish_beam costs what it cost.
+// the candidates of a frozen member are dead, whatever their rows hold: the row is not read.  W is 1, 2, 4 or 8: candidate c belongs
+// to member c >> log2(W)
+template <bool FROZEN>
+__device__ __forceinline__ bool fb_owner_frozen(const int64_t *__restrict__ members, int64_t c, int W, int64_t n_frozen)
+{
+    if constexpr (!FROZEN) return false;
+    else return members[c >> (__ffs(W) - 1)] < n_frozen;
+}
+
 // candidates: a dead one gets key 0 (any key will do: it is never looked up, and the sort only has to stay within the key's bits)
-__global__ void fb_pack_cand_kernel(const int64_t *__restrict__ cand, int64_t count, PackDesc d, uint64_t *klo, uint64_t *khi)
+template <bool FROZEN>
+__global__ void fb_pack_cand_kernel(const int64_t *__restrict__ cand, const int64_t *__restrict__ members, int64_t count, int W,
+                                    int64_t n_frozen, PackDesc d, uint64_t *klo, uint64_t *khi)
 {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= count) return;
     const int64_t *row = cand + c * d.L;
-    const unsigned __int128 key = fb_live(row, d) ? pack_tuple_key(row, d) : (unsigned __int128)0;
+    const bool live = !fb_owner_frozen<FROZEN>(members, c, W, n_frozen) && fb_live(row, d);
+    const unsigned __int128 key = live ? pack_tuple_key(row, d) : (unsigned __int128)0;
     klo[c] = (uint64_t)key;
     khi[c] = (uint64_t)(key >> 64);
 }
@@ -94,11 +114,12 @@ __device__ __forceinline__ int64_t fb_lower_bound(const uint64_t *lo, const uint
     return a;
 }
 
-__global__ void fb_mark_kernel(BeamFinishParams p, PackDesc d)
+template <bool FROZEN>
+__global__ void fb_mark_kernel(BeamFinishParams p, PackDesc d, int64_t n_frozen)
 {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= p.MW) return;
-    if (!fb_live(p.cand + c * d.L, d)) { p.cslot[c] = -1; return; }
+    if (fb_owner_frozen<FROZEN>(p.members, c, p.W, n_frozen) || !fb_live(p.cand + c * d.L, d)) { p.cslot[c] = -1; return; }
     const uint64_t klo = p.clo[c], khi = p.wide ? p.chi[c] : 0;
     const int64_t h = fb_lower_bound(p.hlo, p.hhi, p.wide, p.n, klo, khi);
     if (h < p.n && p.hlo[h] == klo && (!p.wide || p.hhi[h] == khi)) { p.cslot[c] = -1; return; }   // some item holds it
@@ -113,8 +134,10 @@ __global__ void fb_init_kernel(BeamFinishParams p)
     p.choice[j] = -1;
 }
 
-// one wave per group, as spill_keepers_kernel: the keeper is a wave reduction on {ordered error bits, item id}
-__global__ __launch_bounds__(FB_THREADS) void fb_keepers_kernel(BeamFinishParams p, int64_t n_groups)
+// one wave per group, as spill_keepers_kernel: the keeper is a wave reduction on {ordered error bits, item id} over the NEW holders;
+// frozen holders are counted only, and one of them leaves the group without a keeper (ki stays ~0u, which is no item id: n < 2^32)
+template <bool FROZEN>
+__global__ __launch_bounds__(FB_THREADS) void fb_keepers_kernel(BeamFinishParams p, int64_t n_groups, int64_t n_frozen)
 {
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * FB_WAVES + (threadIdx.x >> 6);
@@ -124,11 +147,12 @@ __global__ __launch_bounds__(FB_THREADS) void fb_keepers_kernel(BeamFinishParams
     hi = hi > p.M ? p.M : hi;                                                     // nothing past the member table is touched
 
     uint32_t kd = ~0u, ki = ~0u;
-    int holders = 0;
+    int holders = 0, frozen = 0;
     for (int64_t pos = lo + lane; pos < hi; pos += 64) {
         const int64_t id = p.members[pos];
         if (id < 0 || id >= p.n) continue;
         ++holders;
+        if (FROZEN && id < n_frozen) { ++frozen; continue; }                      // (err_held[pos] is not read)
         const uint32_t d = ordered_bits(p.err_held[pos]);
         if (d < kd || (d == kd && (uint32_t)id < ki)) { kd = d; ki = (uint32_t)id; }
     }
@@ -137,15 +161,17 @@ __global__ __launch_bounds__(FB_THREADS) void fb_keepers_kernel(BeamFinishParams
         const uint32_t od = __shfl_xor(kd, o, 64), oi = __shfl_xor(ki, o, 64);
         if (od < kd || (od == kd && oi < ki)) { kd = od; ki = oi; }
         holders += __shfl_xor(holders, o, 64);
+        if (FROZEN) frozen += __shfl_xor(frozen, o, 64);
     }
-    if (holders < 2) return;
+    if (holders < 2 || frozen == holders) return;                                 // (no new holder: no mover)
+    if (frozen > 0) ki = ~0u;
     for (int64_t pos = lo + lane; pos < hi; pos += 64) {
         const int64_t id = p.members[pos];
-        if (id < 0 || id >= p.n || (uint32_t)id == ki) continue;
+        if ((FROZEN && id < n_frozen) || id < 0 || id >= p.n || (uint32_t)id == ki) continue;
         p.ptr[pos] = 0;
         p.choice[pos] = -2;
     }
-    if (lane == 0) atomicAdd(&p.counters[0], (unsigned long long)(holders - 1));
+    if (lane == 0) atomicAdd(&p.counters[0], (unsigned long long)(holders - frozen - (frozen > 0 ? 0 : 1)));
 }
 
 __device__ __forceinline__ unsigned long long fb_word(float err, int64_t id)
@@ -202,9 +228,8 @@ struct BeamFinishPlan {
     size_t stride_n, stride_c, claimed_bytes, ptr_bytes, temp_bytes, workspace_bytes;
 };
 
-static int finish_beam_plan(int64_t n, int64_t n_members, int L, const int *K, int width, BeamFinishPlan *p)
+static int finish_beam_plan(const char *who, int64_t n, int64_t n_members, int L, const int *K, int width, BeamFinishPlan *p)
 {
-    const char *who = "finish_beam";
     *p = BeamFinishPlan{};
     if (L < 1 || L > LCREC_MAX_LEVELS) return fail(LCREC_EINVAL, "%s: L=%d (1 .. %d)", who, L, LCREC_MAX_LEVELS);
     if (n < 0 || n > 0xffffffffLL) return fail(LCREC_EINVAL, "%s: n=%lld (0 .. 2^32 - 1)", who, (long long)n);
@@ -230,10 +255,12 @@ static int finish_beam_plan(int64_t n, int64_t n_members, int L, const int *K, i
     return LCREC_OK;
 }
 
-size_t finish_beam_workspace(int64_t n, int64_t n_members, int L, int width)
+static const char *fb_who(bool frozen) { return frozen ? "extend_finish_beam" : "finish_beam"; }
+
+size_t finish_beam_workspace(bool frozen, int64_t n, int64_t n_members, int L, int width)
 {
     BeamFinishPlan p;   // (the sizes do not depend on the key)
-    return finish_beam_plan(n, n_members, L, nullptr, width, &p) == LCREC_OK ? p.workspace_bytes : 0;
+    return finish_beam_plan(fb_who(frozen), n, n_members, L, nullptr, width, &p) == LCREC_OK ? p.workspace_bytes : 0;
 }
 
 // (lo, hi) -> (out_lo, out_hi) ordered by the pair: a stable sort by the low word, then (a key wider than 64 bits) by the high word
@@ -248,33 +275,36 @@ static hipError_t fb_sort_keys(const BeamFinishPlan &plan, uint64_t *lo, uint64_
     return rocprim::radix_sort_pairs(temp, tb, tmp_hi, out_hi, tmp_lo, out_lo, (size_t)count, 0, plan.hi_bits, stream, false);
 }
 
-int finish_beam(int64_t *idx, int64_t n, int L, const int *K, const int64_t *tuple_members, const int64_t *tuple_offsets,
-                int64_t n_groups, int64_t n_members, const float *err_held, const int64_t *cand, const float *cand_err, int width,
-                int *choice_out, int64_t *counters_out, void *workspace, size_t workspace_bytes, hipStream_t stream)
+// Both entries: `frozen` selects lcrec_extend_finish_beam's checks, texts and trace name.
+int finish_beam(bool frozen, int64_t *idx, int64_t n, int64_t n_frozen, int L, const int *K, const int64_t *tuple_members,
+                const int64_t *tuple_offsets, int64_t n_groups, int64_t n_members, const float *err_held, const int64_t *cand,
+                const float *cand_err, int width, int *choice_out, int64_t *counters_out, void *workspace, size_t workspace_bytes,
+                hipStream_t stream)
 {
-    const char *who = "finish_beam";
+    const char *who = fb_who(frozen);
     if (int rc = first_null(who, {{counters_out, "counters_out"}, {K, "K"}})) return rc;
     if (n_groups < 0 || n_groups > 0x7fffffffLL)
         return fail(LCREC_EINVAL, "%s: n_tuple_groups=%lld (0 .. 2^31 - 1)", who, (long long)n_groups);
     BeamFinishPlan plan;
-    if (int rc = finish_beam_plan(n, n_members, L, K, width, &plan)) return rc;
+    if (int rc = finish_beam_plan(who, n, n_members, L, K, width, &plan)) return rc;
+    if (n_frozen < 0 || n_frozen > n) return fail(LCREC_EINVAL, "%s: n_frozen=%lld (0 .. n=%lld)", who, (long long)n_frozen, (long long)n);
     if (((uintptr_t)idx | (uintptr_t)tuple_members | (uintptr_t)tuple_offsets | (uintptr_t)cand | (uintptr_t)counters_out |
          (uintptr_t)workspace) & 7)
         return fail(LCREC_EINVAL, "%s: idx, tuple_members, tuple_offsets, cand, counters_out and workspace must be 8-byte aligned", who);
     if (((uintptr_t)err_held | (uintptr_t)cand_err | (uintptr_t)choice_out) & 3)
         return fail(LCREC_EINVAL, "%s: err_held, cand_err and choice_out must be 4-byte aligned", who);
-    const bool work = n_groups > 0 && n_members > 0 && n > 0;
+    const bool work = n_groups > 0 && n_members > 0 && n > 0 && n_frozen < n;
     if (work) {
         if (int rc = first_null(who, {{idx, "idx"}, {tuple_members, "tuple_members"}, {tuple_offsets, "tuple_offsets"},
                                       {err_held, "err_held"}, {cand, "cand"}, {cand_err, "cand_err"}, {choice_out, "choice_out"}}))
             return rc;
         if (!workspace || workspace_bytes < plan.workspace_bytes)
-            return fail(LCREC_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (lcrec_finish_beam_workspace)", who,
-                        workspace ? workspace_bytes : (size_t)0, plan.workspace_bytes);
+            return fail(LCREC_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (lcrec_%s_workspace)", who,
+                        workspace ? workspace_bytes : (size_t)0, plan.workspace_bytes, who);
     }
     hipError_t he = hipMemsetAsync(counters_out, 0, 4 * sizeof(int64_t), stream);
     if (he != hipSuccess) return fail(LCREC_EHIP, "%s: %s", who, hipGetErrorString(he));
-    if (!work) return LCREC_OK;   // (no shared tuple: nothing can move)
+    if (!work) return LCREC_OK;   // (no shared tuple, or no new item: nothing can move)
 
     PackDesc d;
     d.L = L;
@@ -310,26 +340,30 @@ int finish_beam(int64_t *idx, int64_t n, int L, const int *K, const int64_t *tup
     const unsigned grid_c = (unsigned)((plan.mw + FB_THREADS - 1) / FB_THREADS);
     const unsigned grid_m = (unsigned)((n_members + FB_THREADS - 1) / FB_THREADS);
     const unsigned grid_g = (unsigned)((n_groups + FB_WAVES - 1) / FB_WAVES);
-    TraceScope trace(K_FINISH_BEAM, stream);
+    TraceScope trace(frozen ? K_EXTEND_FINISH_BEAM : K_FINISH_BEAM, stream);
     hipLaunchKernelGGL(fb_pack_held_kernel, dim3(grid_n), dim3(FB_THREADS), 0, stream, idx, n, d, h[0], h[1]);
     he = fb_sort_keys(plan, h[0], h[1], h[2], h[3], h[4], h[5], n, temp, stream);
     if (he != hipSuccess) return fail(LCREC_EHIP, "%s: sort: %s", who, hipGetErrorString(he));
-    hipLaunchKernelGGL(fb_pack_cand_kernel, dim3(grid_c), dim3(FB_THREADS), 0, stream, cand, plan.mw, d, c[0], c[1]);
+    const bool fz = n_frozen > 0;
+    hipLaunchKernelGGL(fz ? fb_pack_cand_kernel<true> : fb_pack_cand_kernel<false>, dim3(grid_c), dim3(FB_THREADS), 0, stream, cand,
+                       tuple_members, plan.mw, width, n_frozen, d, c[0], c[1]);
     he = fb_sort_keys(plan, c[0], c[1], c[2], c[3], c[4], c[5], plan.mw, temp, stream);
     if (he != hipSuccess) return fail(LCREC_EHIP, "%s: sort: %s", who, hipGetErrorString(he));
     he = hipMemsetAsync(p.best, 0xff, (size_t)plan.mw * 8, stream);
     if (he == hipSuccess) he = hipMemsetAsync(claimed, 0, (size_t)plan.mw, stream);
     if (he != hipSuccess) return fail(LCREC_EHIP, "%s: %s", who, hipGetErrorString(he));
-    hipLaunchKernelGGL(fb_mark_kernel, dim3(grid_c), dim3(FB_THREADS), 0, stream, p, d);
+    hipLaunchKernelGGL(fz ? fb_mark_kernel<true> : fb_mark_kernel<false>, dim3(grid_c), dim3(FB_THREADS), 0, stream, p, d,
+                       n_frozen);
     hipLaunchKernelGGL(fb_init_kernel, dim3(grid_m), dim3(FB_THREADS), 0, stream, p);
-    hipLaunchKernelGGL(fb_keepers_kernel, dim3(grid_g), dim3(FB_THREADS), 0, stream, p, n_groups);
+    hipLaunchKernelGGL(fz ? fb_keepers_kernel<true> : fb_keepers_kernel<false>, dim3(grid_g), dim3(FB_THREADS), 0, stream, p, n_groups,
+                       n_frozen);
     // the fixed `width` rounds, whatever happens in them: a round without a proposer does nothing, and nothing is read back
     for (int r = 0; r < width; ++r) {
         hipLaunchKernelGGL(fb_propose_kernel, dim3(grid_m), dim3(FB_THREADS), 0, stream, p);
         hipLaunchKernelGGL(fb_resolve_kernel, dim3(grid_m), dim3(FB_THREADS), 0, stream, p, L, r);
     }
     hipLaunchKernelGGL(fb_finalize_kernel, dim3(1), dim3(1), 0, stream, p.counters);
-    return check_launch("finish_beam kernels");
+    return check_launch(frozen ? "extend_finish_beam kernels" : "finish_beam kernels");
 }
 
 }  // namespace lcrec

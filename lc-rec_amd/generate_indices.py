@@ -32,6 +32,9 @@ Documented divergences from the reference script:
     every item that still shares its tuple after the rounds moves to the next-best WHOLE tuple nobody holds, out of a beam of
     --finish_width tuples of its own latent (beam_finish_collisions); nearest_free then runs on what that leaves.  --rounds N sets
     the number of conflict rounds before it (20, the reference's; 0 keeps every item that collides with nobody on its pass-1 tuple);
+  * --extend_finish beam (off by default) is that step for --extend: a new item whose pass-1 tuple is taken, by a frozen item or by
+    a better new holder, first moves to the next-best whole tuple nobody holds (extend_beam_collisions); the nearest-free pass of
+    --extend then runs on what that leaves, and the base's tuples stay byte for byte;
   * it stores tokens in fixed-width numpy unicode arrays (:98-99) which silently truncate a
     replacement longer than anything seen in pass 1; integer tuples are kept here, and a warning is
     logged if a run ever hits that case (the reference's output would be corrupt there).
@@ -55,6 +58,7 @@ PREFIX = ["<{}_{{}}>".format(chr(ord("a") + i)) for i in range(26)]   # "<a_{}>"
 MAX_ROUNDS = 20                                                        # :110
 FINISH_MODES = ("none", "nearest_free", "beam")
 FINISH_WIDTHS = (2, 4, 8)
+EXTEND_FINISH_MODES = ("nearest_free", "beam")
 log = logging.getLogger(__name__)
 
 
@@ -264,19 +268,25 @@ def beam_finish_collisions(model, idx, latents, resid_last, ks, width, resid_pre
     out.update(counters)
     pos = torch.nonzero(choice >= 0).flatten()
     if pos.numel():
-        items, zm = members[pos], z.index_select(0, pos)
         out["err_moved_sum"] = float(beams["err"][pos, choice[pos].long()].double().sum())
-        L = idx.shape[1]
-        held = idx.index_select(0, items)
-        for depth, resid in ((L - 1, resid_last), (L - 2, resid_prev)):
-            if resid is None or depth < 0:
-                continue
-            if depth == 0:
-                resid[items] = zm
-            else:
-                pflat, pks = ops.flatten_codebooks(cbs[:depth])
-                resid[items] = ops.rq_audit(zm, pflat, pks, held[:, :depth], want_resid=True)["resid"]
+        _refresh_moved_residuals(cbs, idx, members[pos], z.index_select(0, pos), members[pos], resid_last, resid_prev)
     return out
+
+
+def _refresh_moved_residuals(cbs, idx, items, zm, rows, resid_last, resid_prev):
+    """Behind a beam step: the moved `items` (latents zm) hold new whole tuples in idx, so rows `rows` of resid_last -- and of
+    resid_prev, the residual entering level L-2, when given -- become the residuals of the new tuple's prefix, as assign_all computes
+    them for a chosen tuple."""
+    L = idx.shape[1]
+    held = idx.index_select(0, items)
+    for depth, resid in ((L - 1, resid_last), (L - 2, resid_prev)):
+        if resid is None or depth < 0:
+            continue
+        if depth == 0:
+            resid[rows] = zm
+        else:
+            pflat, pks = ops.flatten_codebooks(cbs[:depth])
+            resid[rows] = ops.rq_audit(zm, pflat, pks, held[:, :depth], want_resid=True)["resid"]
 
 
 # ---- opt-in: new items around an index file whose tuples are frozen (--extend BASE.index.json) -------------------------------------
@@ -352,6 +362,53 @@ def extend_collisions(model, idx, n_frozen, resid_new, ks):
     return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
 
 
+# ---- opt-in: a new item that meets a taken tuple first moves to its next-best whole tuple (--extend --extend_finish beam) ----------
+@torch.no_grad()
+def extend_beam_collisions(model, idx, n_frozen, latents_new, resid_new, ks, width, resid_prev=None):
+    """ops.extend_finish_beam over the shared tuples of ALL items -- include/lcrec.h, lcrec_extend_finish_beam, states the rule:
+    beam_finish_collisions around a frozen catalogue.  Rows 0 .. n_frozen-1 of idx never change.  latents_new: pass 1's latents of
+    the NEW items only, float32 [n - n_frozen, e] (or the list of its chunks), row i - n_frozen for item i; resid_new and resid_prev
+    likewise.  Only the new members of the shared tuples are walked through ops.rq_beam and ops.rq_audit; their results are
+    scattered to the members' positions, and the positions of frozen members stay unwritten: the entry never reads them.  Mutates
+    idx (the rows of the new items that move) and resid_new -- and resid_prev when given -- for those rows, as
+    beam_finish_collisions does, so that extend_collisions and spill_collisions behind this pass see the right residuals.
+    Returns dict(movers, moved, unresolved, rounds, err_moved_sum).  A function of its inputs alone."""
+    if width not in ops.BEAM_WIDTHS:
+        raise ValueError(f"width={width!r}: one of {ops.BEAM_WIDTHS}")
+    out = {"movers": 0, "moved": 0, "unresolved": 0, "rounds": 0, "err_moved_sum": 0.0}
+    n, L = idx.shape
+    found = ops.collision_groups(idx, ks, want_groups="device")
+    if found["n_groups"] == 0:
+        return out
+    members = found["members"]
+    M = members.numel()
+    fresh = torch.nonzero(members >= n_frozen).flatten()          # the positions of the new members
+    if fresh.numel() == 0:
+        return out                                                  # (the base collides with itself only: nobody can move)
+    if isinstance(latents_new, (list, tuple)):
+        latents_new = torch.cat(latents_new)
+    cbs = [q.embedding.weight.detach() for q in model.rq.vq_layers]
+    flat, _ = ops.flatten_codebooks(cbs)
+    items = members[fresh]
+    z = latents_new.index_select(0, items - n_frozen)
+    beams = ops.rq_beam(z, flat, ks, width)
+    dev = idx.device
+    err_held = torch.empty(M, dtype=torch.float32, device=dev)
+    cand = torch.empty((M, width, L), dtype=torch.int64, device=dev)
+    cand_err = torch.empty((M, width), dtype=torch.float32, device=dev)
+    err_held[fresh] = ops.rq_audit(z, flat, ks, idx.index_select(0, items))["err"]
+    cand[fresh] = beams["tuples"]
+    cand_err[fresh] = beams["err"]
+    choice, counters = ops.extend_finish_beam(idx, n_frozen, ks, members, found["offsets"], err_held, cand, cand_err)
+    out.update(counters)
+    took = choice[fresh]                                            # (a frozen member's choice is -1)
+    pos = torch.nonzero(took >= 0).flatten()
+    if pos.numel():
+        out["err_moved_sum"] = float(beams["err"][pos, took[pos].long()].double().sum())
+        _refresh_moved_residuals(cbs, idx, items[pos], z.index_select(0, pos), items[pos] - n_frozen, resid_new, resid_prev)
+    return out
+
+
 # ---- opt-in: what the two passes above leave colliding moves to a sibling bucket (--spill) ---------------------------------------
 @torch.no_grad()
 def spill_collisions(model, idx, n_frozen, resid_prev, resid_last, ks):
@@ -419,7 +476,7 @@ def _colliding(rows):
 
 
 def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_path=None, verbose=True, trust_checkpoint=False,
-                      spill=False, audit=False):
+                      spill=False, audit=False, extend_finish="nearest_free", finish_width=8):
     """--extend: the data file holds the whole catalogue, its first N0 rows are the items of `base_file` (keys "0" .. "N0-1") and
     rows N0 .. N-1 are new.  The output holds all N items; the first N0 entries carry exactly the base file's tuples (and, for a
     base written by this project or by the reference, the output's first len(base) - 1 bytes are the base file's without its
@@ -429,8 +486,18 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
     The Sinkhorn conflict rounds are NOT run here: they re-assign within a group of colliding items and know nothing of codes held
     outside it, so beside a frozen catalogue most of their work would be undone again.  The distance rule alone decides.
     --finish is ignored for the same reason.  N == N0 launches nothing and rewrites the base.
+    extend_finish: "nearest_free" is the flow above.  "beam": a new item whose pass-1 tuple is taken first moves to the next-best
+        whole tuple nobody holds, out of a beam of `finish_width` (2, 4 or 8) tuples of its own (extend_beam_collisions), and
+        extend_collisions runs on what that leaves.  The statistics then gain extend_beam_width, extend_beam_movers,
+        extend_beam_moved, extend_beam_unresolved and extend_beam_rounds; extend_moved and extend_unresolved keep their meaning, the
+        nearest-free pass.  N == N0: the five are 0 (and the width).
     spill: the new items that extend_collisions leaves unresolved go through spill_collisions.
     audit: stats["audit"] is the index audit of the NEW rows' tuples (no latents exist for the frozen items); N == N0: no report."""
+    if extend_finish not in EXTEND_FINISH_MODES:
+        raise ValueError(f"extend_finish={extend_finish!r}: one of {EXTEND_FINISH_MODES}")
+    if finish_width not in FINISH_WIDTHS:
+        raise ValueError(f"--finish_width {finish_width!r}: one of {FINISH_WIDTHS}")
+    beam_step = extend_finish == "beam"
     ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
     args = ckpt["args"]
     if spill:
@@ -446,6 +513,9 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
                          "catalogue, the base's items first")
     stats = {"items": n, "base_items": n0, "new_items": n - n0, "extend_moved": 0, "extend_unresolved": 0, "buckets": 0,
              "largest_bucket": 0, "neartie_items": 0, "neartie_tau": ops.NEARTIE_TAU}
+    if beam_step:
+        stats.update(extend_beam_width=finish_width, extend_beam_movers=0, extend_beam_moved=0, extend_beam_unresolved=0,
+                     extend_beam_rounds=0)
     if spill:
         stats.update(spill_moved=0, spill_unresolved=0, spill_super_buckets=0, largest_super_bucket=0)
     if n == n0:
@@ -457,13 +527,20 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
         dev = torch.device(device)
         model = model.to(dev).eval()
         ties = {}
-        latents = [] if audit else None
+        latents = [] if audit or beam_step else None
         idx_new, resid_new, ks, *prev = assign_all(model, data.to_device(dev, rows=(n0, n)), audit=ties, want_prev=spill, latents=latents)
         stats["neartie_items"] = int((ties["neartie"] != 0).sum())
         base_dev = torch.from_numpy(base).to(dev)
         stats["base_colliding"] = n0 - ops.collision_groups(base_dev, ks, want_groups=False)["unique"] if n0 else 0
         idx = torch.cat([base_dev, idx_new])
         first_pass = idx.clone()
+        if beam_step:
+            done = extend_beam_collisions(model, idx, n0, latents, resid_new, ks, finish_width, resid_prev=prev[0] if spill else None)
+            stats.update(extend_beam_movers=done["movers"], extend_beam_moved=done["moved"], extend_beam_unresolved=done["unresolved"],
+                         extend_beam_rounds=done["rounds"])
+            log.info("--extend_finish beam: of %d new items whose tuple is taken %d moved to a free whole tuple out of a beam of %d "
+                     "(%d rounds, their quantisation error sums to %.6g), %d are left to the nearest free last-level code",
+                     done["movers"], done["moved"], finish_width, done["rounds"], done["err_moved_sum"], done["unresolved"])
         done = extend_collisions(model, idx, n0, resid_new, ks)
         stats.update(extend_moved=done["moved"], extend_unresolved=done["unresolved"], buckets=done["buckets"],
                      largest_bucket=done["largest_bucket"])
@@ -628,7 +705,8 @@ def sharded_assign(ctx, data, assign_fn, device):
 
 
 def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=True, ctx=None, trust_checkpoint=False,
-             recheck=False, finish="none", extend=None, spill=False, audit=False, beam=1, rounds=MAX_ROUNDS, finish_width=8):
+             recheck=False, finish="none", extend=None, spill=False, audit=False, beam=1, rounds=MAX_ROUNDS, finish_width=8,
+             extend_finish="nearest_free"):
     """Whole flow of generate_indices.py:51-145.  Returns a dict of the statistics it prints.
     recheck: re-evaluate the near-tie items of pass 1 in the reference's CPU operation order (recheck_neartie).
     finish: "none" (the reference's bytes), "nearest_free" (finish_collisions after the rounds; beyond the reference) or "beam":
@@ -642,6 +720,9 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
 
     extend: path of an existing `.index.json` whose items are the first rows of the data file: their tuples are kept and only
         the new rows are indexed, around them (generate_extended, which says why neither the conflict rounds nor `finish` run).
+    extend_finish: with `extend` only (ValueError without it): "nearest_free" (the default, today's bytes) or "beam": the new items
+        that meet a taken tuple first move to their next-best whole tuple out of a beam of `finish_width` tuples
+        (generate_extended names the statistics this adds).
     spill: after finish="nearest_free" or `extend`, the items that pass leaves unresolved move to a sibling bucket
         (spill_collisions; beyond the reference).  Refused with ValueError before the checkpoint is opened: without one of those two
         passes, with `recheck` (the level L-2 residuals it patches are not kept) and under torchrun; and as soon as the checkpoint's
@@ -679,10 +760,14 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         raise ValueError(f"--rounds {rounds!r}: an integer >= 0")
     if finish_width not in FINISH_WIDTHS:
         raise ValueError(f"--finish_width {finish_width!r}: one of {FINISH_WIDTHS}")
+    if extend_finish not in EXTEND_FINISH_MODES:
+        raise ValueError(f"extend_finish={extend_finish!r}: one of {EXTEND_FINISH_MODES}")
+    if extend_finish != "nearest_free" and extend is None:
+        raise ValueError(f"--extend_finish {extend_finish} finishes the new items of --extend: give --extend BASE.index.json")
     if finish == "beam":
         if extend is not None:
-            raise ValueError("--finish beam with --extend is not supported: the new items are indexed around frozen tuples by the "
-                             "distance rule alone")
+            raise ValueError("--finish beam with --extend is not supported: the conflict rounds and --finish do not run around frozen "
+                             "tuples; --extend_finish beam is that step for the new items")
         if recheck:
             raise ValueError("--finish beam with --recheck_neartie is not supported: the beam starts from the latents of pass 1, which "
                              "the re-evaluation does not patch")
@@ -709,7 +794,8 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
         if ctx.enabled:
             raise ValueError("--extend under torchrun is not supported: run it in a single process")
         return generate_extended(ckpt_path, output_file, extend, device=device, data_path=data_path, verbose=verbose,
-                                 trust_checkpoint=trust_checkpoint, spill=spill, audit=audit)
+                                 trust_checkpoint=trust_checkpoint, spill=spill, audit=audit, extend_finish=extend_finish,
+                                 finish_width=finish_width)
     lead = ctx.rank == 0
     verbose = verbose and lead
     if finish not in FINISH_MODES:
@@ -848,6 +934,11 @@ def parse_args(argv=None):
                          "keep their tuples byte for byte; only the rows after them are indexed, each new item keeping its tuple "
                          "unless it is taken and then moving to the nearest free last-level code (goes beyond the reference).  The "
                          "conflict rounds are not run and --finish is ignored; not with --recheck_neartie or torchrun")
+    ap.add_argument("--extend_finish", choices=EXTEND_FINISH_MODES, default="nearest_free",
+                    help="--extend: what a new item does whose pass-1 tuple is taken.  nearest_free = the nearest free last-level code "
+                         "of its bucket (the default).  beam = it first moves to the next-best whole tuple nobody holds, out of a "
+                         "beam of --finish_width tuples of its own, and nearest_free runs on what that leaves (beyond the reference; "
+                         "the base's tuples stay byte for byte either way)")
     ap.add_argument("--spill", action="store_true",
                     help="after --finish nearest_free or --extend: an item that pass leaves colliding, because its bucket holds more "
                          "items than the last level has codes, takes the next-nearest code one level up and the nearest free "
@@ -874,7 +965,8 @@ def main(argv=None):
     try:
         return generate(a.ckpt_path, out, device=a.device, data_path=a.data_path, ctx=ctx,
                         trust_checkpoint=a.trust_checkpoint, recheck=a.recheck_neartie, finish=a.finish, extend=a.extend,
-                        spill=a.spill, audit=a.audit, beam=a.beam, rounds=a.rounds, finish_width=a.finish_width)
+                        spill=a.spill, audit=a.audit, beam=a.beam, rounds=a.rounds, finish_width=a.finish_width,
+                        extend_finish=a.extend_finish)
     finally:
         ldist.shutdown(ctx)
 

@@ -1141,8 +1141,28 @@ def finish_beam(idx, ks, members, offsets, err_held, cand, cand_err, counters_ou
     too.  choice_out: an int32 tensor of at least M elements, written instead of a fresh one (it may be LARGER, so that a test can
     look at what lies past the end).  workspace: a uint8 device tensor of at least lcrec_finish_beam_workspace's bytes, passed as
     the workspace as it is, its size included; None: the binding's own grow-only buffer of the stream."""
+    return _finish_beam(None, idx, ks, members, offsets, err_held, cand, cand_err, counters_out, choice_out, workspace)
+
+
+def extend_finish_beam(idx, n_frozen, ks, members, offsets, err_held, cand, cand_err, counters_out=None, choice_out=None,
+                       workspace=None):
+    """The frozen-aware beam finishing pass (lcrec_extend_finish_beam of include/lcrec.h, which states the rule): finish_beam with
+    items 0 .. n_frozen-1 of idx frozen.  They never move; a new item that shares its tuple with a frozen one moves, and among new
+    holders only the one with the smallest err_held keeps the tuple.  The positions of frozen members in err_held, cand and
+    cand_err are never read: they may hold anything.
+
+    Arguments, return value and the capturable form (counters_out, choice_out and workspace given) as finish_beam; members / offsets
+    list the groups over all n items; the workspace query is lcrec_extend_finish_beam_workspace."""
+    return _finish_beam(n_frozen, idx, ks, members, offsets, err_held, cand, cand_err, counters_out, choice_out, workspace)
+
+
+def _finish_beam(n_frozen, idx, ks, members, offsets, err_held, cand, cand_err, counters_out, choice_out, workspace):
+    """finish_beam (n_frozen None) and extend_finish_beam: one set of checks, the entry and its workspace query differ"""
     lib = _lib.load()
     n, L = _inplace_idx(idx)
+    entry = "lcrec_finish_beam" if n_frozen is None else "lcrec_extend_finish_beam"
+    if n_frozen is not None:
+        n_frozen = _frozen_count(n_frozen, n, L)
     dev = idx.device
     members, offsets = _group_table(members, offsets)
     err_held, cand_err = _dev(err_held, "err_held"), _dev(cand_err, "cand_err")
@@ -1170,15 +1190,16 @@ def finish_beam(idx, ks, members, offsets, err_held, cand, cand_err, counters_ou
     elif not (isinstance(choice_out, torch.Tensor) and choice_out.device == dev and choice_out.dtype == torch.int32
               and choice_out.dim() == 1 and choice_out.is_contiguous() and choice_out.numel() >= M):
         raise _lib.LcrecError(f"choice_out must be a contiguous int32 tensor on idx's device with at least {M} elements")
-    need = lib.lcrec_finish_beam_workspace(n, M, L, width)
+    need = getattr(lib, entry + "_workspace")(n, M, L, width)
     if workspace is not None:
-        workspace = _own_workspace(workspace, dev, need, "lcrec_finish_beam_workspace")
+        workspace = _own_workspace(workspace, dev, need, entry + "_workspace")
     with _on(dev):
         ws = workspace if workspace is not None else _workspace(need, dev)
-        rc = lib.lcrec_finish_beam(_ptr(idx), n, L, _ints(ks), _ptr(members), _ptr(offsets), max(offsets.numel() - 1, 0), M,
-                                   _ptr(err_held), _ptr(cand), _ptr(cand_err), width, _ptr(choice_out), _ptr(counters), _ptr(ws),
-                                   ws.numel(), _stream_ptr())
-    _lib.check(rc, "lcrec_finish_beam")
+        head = (_ptr(idx), n) + (() if n_frozen is None else (n_frozen,))
+        rc = getattr(lib, entry)(*head, L, _ints(ks), _ptr(members), _ptr(offsets), max(offsets.numel() - 1, 0), M, _ptr(err_held),
+                                 _ptr(cand), _ptr(cand_err), width, _ptr(choice_out), _ptr(counters), _ptr(ws), ws.numel(),
+                                 _stream_ptr())
+    _lib.check(rc, entry)
     if counters_out is not None:
         return choice_out[:M], None
     movers, moved, unresolved, rounds = counters.tolist()

@@ -9,6 +9,7 @@ pass 1 (encode + assign), the conflict rounds, the opt-in nearest-free finishing
     python tools/generate_probe.py --decode                    # then the decode pass over them: tuples -> embeddings -> error per item
     python tools/generate_probe.py --beam 2,4,8                # then the beam-search quantiser (--beam W) at each width over pass 1's latents
     python tools/generate_probe.py --finish_beam 2,4,8         # then the beam finishing step (--rounds 0 --finish beam) at each width on pass 1's tuples
+    python tools/generate_probe.py --extend_new 10000,100000 --extend_finish_beam 2,4,8   # --extend's beam step (--extend_finish beam) at each width, beside the plain --extend step
 """
 import argparse
 import os
@@ -65,6 +66,66 @@ def extend_probe(model, x_new, base_file, n0, timed, spill=False):
             f"{done['unresolved']}, collision rate afterwards {after['collision_rate']:.6f}"] + more
 
 
+def extend_beam_probe(model, x_new, base_file, n0, widths, runs):
+    """--extend --extend_finish beam on a base file of n0 items and the rows x_new: per width one warm-up, then `runs` timed runs on
+    fresh copies of pass 1's tuples and residuals; medians of the whole step (gen.extend_beam_collisions), of lcrec_extend_finish_beam
+    alone and of the new-members-only rq_beam by the trace brackets; the plain --extend step (gen.extend_collisions on pass 1's
+    tuples) timed the same way in the same run as the yardstick; and the NEW items' quantisation error against their greedy tuples'
+    for both flows.  Returns the lines to print."""
+    dev = x_new.device
+    ks = [int(q.embedding.weight.shape[0]) for q in model.rq.vq_layers]
+    base_dev = torch.from_numpy(gen.load_index_json(base_file, ks)).to(dev)
+    lat = []
+    idx_new, resid0, ks = gen.assign_all(model, x_new, latents=lat)
+    latent = torch.cat(lat)
+    flat, _ = ops.flatten_codebooks([q.embedding.weight.detach() for q in model.rq.vq_layers])
+    union = torch.cat([base_dev, idx_new])
+    err_sum = lambda t: float(torch.nan_to_num(ops.rq_audit(latent, flat, ks, t[n0:].contiguous())["err"], nan=0.0, posinf=0.0).double().sum())
+    e_greedy = err_sum(union)
+
+    def timed_on_copies(fn):
+        """fn(idx, resid) on fresh copies: one warm-up, then `runs` timed and traced runs -> (idx, resid, result, walls, traces)"""
+        walls, traces = [], []
+        for k in range(runs + 1):
+            i, r = union.clone(), resid0.clone()
+            ops.trace_enable(k > 0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            done = fn(i, r)
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            if k > 0:
+                walls.append(t)
+                traces.append(ops.trace_collect())
+            ops.trace_enable(False)
+        return i, r, done, walls, traces
+
+    med = lambda traces, name: float(np.median([q.get(name, (0, 0.0))[1] for q in traces]))
+    spread = lambda walls: f"{np.median(walls) * 1e3:.2f} ms (median of {len(walls)}, min {min(walls) * 1e3:.2f}, max {max(walls) * 1e3:.2f})"
+    i, _, plain, walls, traces = timed_on_copies(lambda i, r: gen.extend_collisions(model, i, n0, r, ks))
+    assert bool((i[:n0] == base_dev).all())
+    rate = ops.collision_groups(i, ks, want_groups=False)["collision_rate"]
+    lines = [f"--extend_finish beam, {n0} base + {x_new.shape[0]} new items; yardstick of this run, the plain --extend step "
+             f"(extend_collisions): {spread(walls)}, collision_groups {med(traces, 'collision_groups'):.3f} ms, extend_nearest_free "
+             f"{med(traces, 'extend_nearest_free'):.3f} ms by the trace brackets; moved {plain['moved']}, unresolved {plain['unresolved']}, "
+             f"collision rate afterwards {rate:.6f}, error of the new items {err_sum(i) / e_greedy:.4f} x greedy"]
+    for W in widths:
+        i, r, done, walls, traces = timed_on_copies(lambda i, r: gen.extend_beam_collisions(model, i, n0, latent, r, ks, W))
+        assert bool((i[:n0] == base_dev).all())
+        e_beam = err_sum(i)
+        j, _, fin, walls2, _ = timed_on_copies(lambda a, b: (a.copy_(i), b.copy_(r), gen.extend_collisions(model, a, n0, b, ks))[2])
+        rate = ops.collision_groups(j, ks, want_groups=False)["collision_rate"]
+        parts = {name: med(traces, name) for name in ("extend_finish_beam", "rq_beam", "rq_audit", "collision_groups")}
+        lines.append(
+            f"  --finish_width {W}: whole step {spread(walls)}; by the trace brackets lcrec_extend_finish_beam {parts['extend_finish_beam']:.3f} "
+            f"ms, new-members-only rq_beam {parts['rq_beam']:.3f} ms, rq_audit {parts['rq_audit']:.3f} ms, collision_groups "
+            f"{parts['collision_groups']:.3f} ms (largest: {max(parts, key=parts.get)}); movers {done['movers']}, placed {done['moved']}, "
+            f"left to nearest_free {done['unresolved']}, rounds {done['rounds']}; error of the new items {e_beam / e_greedy:.4f} x greedy; "
+            f"then extend_collisions (with the copies) {spread(walls2)} moved {fin['moved']}, unresolved {fin['unresolved']}: collision "
+            f"rate {rate:.6f}, error of the new items {err_sum(j) / e_greedy:.4f} x greedy")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=1_000_000)
@@ -92,7 +153,14 @@ def main():
                     "on fresh copies, medians of the whole step (beam_finish_collisions), of lcrec_finish_beam alone and of the "
                     "members-only rq_beam by the trace brackets, beside the conflict rounds and the nearest-free pass of this run, "
                     "and the quantisation error of both flows against the greedy tuples'")
+    ap.add_argument("--extend_finish_beam", type=str, default="", metavar="W[,W...]", help="with --extend_new: time --extend's beam step "
+                    "(generate --extend --extend_finish beam --finish_width W) at each width given, for each count of new items: one "
+                    "warm-up, then --audit_runs timed runs on fresh copies, medians of the whole step (extend_beam_collisions), of "
+                    "lcrec_extend_finish_beam alone and of the new-members-only rq_beam by the trace brackets, beside the plain "
+                    "--extend step of the same run, and the new items' quantisation error of both flows against their greedy tuples'")
     a = ap.parse_args()
+    if a.extend_finish_beam and not a.extend_new:
+        ap.error("--extend_finish_beam times a step of --extend: give --extend_new N[,N...]")
     dev = "cuda:0"
     torch.manual_seed(2024)
     model = lcrec_amd.RQVAE(in_dim=a.in_dim, num_emb_list=[a.codes] * a.levels, e_dim=32,
@@ -374,6 +442,9 @@ def main():
         x_new = torch.randn((count, a.in_dim), generator=g, device=dev)
         extend_probe(model, x_new[:min(count, 4096)], a.out, a.items, timed, a.spill)       # warm-up of the small-launch forms
         extend_lines += extend_probe(model, x_new, a.out, a.items, timed, a.spill)
+        if a.extend_finish_beam:
+            extend_lines += extend_beam_probe(model, x_new, a.out, a.items, [int(w) for w in a.extend_finish_beam.split(",") if w],
+                                              max(a.audit_runs, 1))
         # the yardstick: what a user does today, the whole flow again over all N items (without the file's text)
         x_all = torch.cat([x, x_new])
         def full():

@@ -24,9 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .checkpoint import load_checkpoint
-from .datasets import EmbDataset
-from .generate_indices import build_model_from_args, load_index_json
+from .generate_indices import load_index_json, open_run
 
 CHUNK_ROWS = 1 << 20
 WORST = 10
@@ -156,11 +154,7 @@ def audit(ckpt_path, index_file, device="cuda:0", data_path=None, trust_checkpoi
     is not the data's row count.  recon: the report also holds, under the key "recon", what the tuples cost in reconstruction loss
     (decode_indices.recon_for: the file's and the greedy tuples through the decoder, against the embeddings)."""
     _refuse_torchrun()
-    ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
-    args = ckpt["args"]
-    data = EmbDataset(data_path or args.data_path, mmap=str(device).startswith("cuda"))
-    model = build_model_from_args(args, data.dim)
-    model.load_state_dict(ckpt["state_dict"])
+    _, data, model = open_run(ckpt_path, data_path, device, trust=trust_checkpoint)
     ks = [int(q.embedding.weight.shape[0]) for q in model.rq.vq_layers]
     held_host = load_index_json(index_file, ks)
     n = len(data)

@@ -231,11 +231,18 @@ def finish_collisions(model, idx, resid_last, ks):
     items that move changes.  Mutates idx; returns dict(moved, unresolved, buckets, largest_bucket).  Afterwards exactly
     `unresolved` items still collide: 0 unless a bucket with a shared code holds more items than the last level has codes.
     A function of its inputs alone: under torchrun every rank runs it on its identical copy, with no collective."""
-    levels = list(model.rq.vq_layers)
-    cb_last = levels[-1].embedding.weight.detach().contiguous()
-    L = idx.shape[1]
-    members, offsets, buckets, largest = _prefix_groups(idx, ks, L - 1)
-    moved, unresolved = ops.finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets)
+    return _nearest_free_pass(model, idx, None, resid_last, ks)
+
+
+def _nearest_free_pass(model, idx, n_frozen, resid, ks):
+    """finish_collisions (n_frozen None: ops.finish_nearest_free, resid holds a row per item) and extend_collisions
+    (ops.extend_nearest_free, a row per new item): the buckets are listed and the result is named the same way."""
+    cb_last = list(model.rq.vq_layers)[-1].embedding.weight.detach().contiguous()
+    members, offsets, buckets, largest = _prefix_groups(idx, ks, idx.shape[1] - 1)
+    if n_frozen is None:
+        moved, unresolved = ops.finish_nearest_free(idx, resid, cb_last, ks, members, offsets)
+    else:
+        moved, unresolved = ops.extend_nearest_free(idx, n_frozen, resid, cb_last, ks, members, offsets)
     return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
 
 
@@ -250,26 +257,49 @@ def beam_finish_collisions(model, idx, latents, resid_last, ks, width, resid_pre
     rows: the residuals of the tuple's prefix, as assign_all computes them for a chosen tuple, so that finish_collisions and
     spill_collisions behind this pass see the right ones.  Returns dict(movers, moved, unresolved, rounds, err_moved_sum): the last
     the float64 sum of the moved items' new quantisation errors.  A function of its inputs alone."""
+    return _beam_step(model, idx, None, latents, resid_last, ks, width, resid_prev)
+
+
+def _beam_step(model, idx, n_frozen, latents, resid_last, ks, width, resid_prev):
+    """beam_finish_collisions (n_frozen None) and extend_beam_collisions, whose docstrings say what happens.  `items` are the
+    members that are walked and `rows` their rows in latents, resid_last and resid_prev: all members, by id, for a whole file; the
+    new members, by id - n_frozen, around a frozen catalogue.  The whole-file entry takes the walk's results as they are (they
+    go by member position already); the frozen-aware one takes them scattered to the positions of the new members."""
     if width not in ops.BEAM_WIDTHS:
         raise ValueError(f"width={width!r}: one of {ops.BEAM_WIDTHS}")
     out = {"movers": 0, "moved": 0, "unresolved": 0, "rounds": 0, "err_moved_sum": 0.0}
     found = ops.collision_groups(idx, ks, want_groups="device")
     if found["n_groups"] == 0:
         return out
+    members = items = rows = found["members"]
+    if n_frozen is not None:
+        fresh = torch.nonzero(members >= n_frozen).flatten()      # the positions of the new members
+        if fresh.numel() == 0:
+            return out                                              # (the base collides with itself only: nobody can move)
+        items = members[fresh]
+        rows = items - n_frozen
     if isinstance(latents, (list, tuple)):
         latents = torch.cat(latents)
     cbs = [q.embedding.weight.detach() for q in model.rq.vq_layers]
     flat, _ = ops.flatten_codebooks(cbs)
-    members = found["members"]
-    z = latents.index_select(0, members)
+    z = latents.index_select(0, rows)
     beams = ops.rq_beam(z, flat, ks, width)
-    err_held = ops.rq_audit(z, flat, ks, idx.index_select(0, members))["err"]
-    choice, counters = ops.finish_beam(idx, ks, members, found["offsets"], err_held, beams["tuples"], beams["err"])
+    err_held = ops.rq_audit(z, flat, ks, idx.index_select(0, items))["err"]
+    if n_frozen is None:
+        took, counters = ops.finish_beam(idx, ks, members, found["offsets"], err_held, beams["tuples"], beams["err"])
+    else:
+        M, L, dev = members.numel(), idx.shape[1], idx.device
+        held_at = torch.empty(M, dtype=torch.float32, device=dev)
+        cand = torch.empty((M, width, L), dtype=torch.int64, device=dev)
+        cand_err = torch.empty((M, width), dtype=torch.float32, device=dev)
+        held_at[fresh], cand[fresh], cand_err[fresh] = err_held, beams["tuples"], beams["err"]
+        choice, counters = ops.extend_finish_beam(idx, n_frozen, ks, members, found["offsets"], held_at, cand, cand_err)
+        took = choice[fresh]                                        # (a frozen member's choice is -1)
     out.update(counters)
-    pos = torch.nonzero(choice >= 0).flatten()
+    pos = torch.nonzero(took >= 0).flatten()
     if pos.numel():
-        out["err_moved_sum"] = float(beams["err"][pos, choice[pos].long()].double().sum())
-        _refresh_moved_residuals(cbs, idx, members[pos], z.index_select(0, pos), members[pos], resid_last, resid_prev)
+        out["err_moved_sum"] = float(beams["err"][pos, took[pos].long()].double().sum())
+        _refresh_moved_residuals(cbs, idx, items[pos], z.index_select(0, pos), rows[pos], resid_last, resid_prev)
     return out
 
 
@@ -354,12 +384,7 @@ def extend_collisions(model, idx, n_frozen, resid_new, ks):
     """ops.extend_nearest_free over the buckets of ALL items sharing idx[:, :L-1] -- include/lcrec.h, lcrec_extend_nearest_free,
     states the rule.  Rows 0 .. n_frozen-1 of idx never change; resid_new holds the rows of the new items only.  Mutates idx;
     returns dict(moved, unresolved, buckets, largest_bucket)."""
-    levels = list(model.rq.vq_layers)
-    cb_last = levels[-1].embedding.weight.detach().contiguous()
-    L = idx.shape[1]
-    members, offsets, buckets, largest = _prefix_groups(idx, ks, L - 1)
-    moved, unresolved = ops.extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets)
-    return {"moved": moved, "unresolved": unresolved, "buckets": buckets, "largest_bucket": largest}
+    return _nearest_free_pass(model, idx, int(n_frozen), resid_new, ks)
 
 
 # ---- opt-in: a new item that meets a taken tuple first moves to its next-best whole tuple (--extend --extend_finish beam) ----------
@@ -373,40 +398,7 @@ def extend_beam_collisions(model, idx, n_frozen, latents_new, resid_new, ks, wid
     idx (the rows of the new items that move) and resid_new -- and resid_prev when given -- for those rows, as
     beam_finish_collisions does, so that extend_collisions and spill_collisions behind this pass see the right residuals.
     Returns dict(movers, moved, unresolved, rounds, err_moved_sum).  A function of its inputs alone."""
-    if width not in ops.BEAM_WIDTHS:
-        raise ValueError(f"width={width!r}: one of {ops.BEAM_WIDTHS}")
-    out = {"movers": 0, "moved": 0, "unresolved": 0, "rounds": 0, "err_moved_sum": 0.0}
-    n, L = idx.shape
-    found = ops.collision_groups(idx, ks, want_groups="device")
-    if found["n_groups"] == 0:
-        return out
-    members = found["members"]
-    M = members.numel()
-    fresh = torch.nonzero(members >= n_frozen).flatten()          # the positions of the new members
-    if fresh.numel() == 0:
-        return out                                                  # (the base collides with itself only: nobody can move)
-    if isinstance(latents_new, (list, tuple)):
-        latents_new = torch.cat(latents_new)
-    cbs = [q.embedding.weight.detach() for q in model.rq.vq_layers]
-    flat, _ = ops.flatten_codebooks(cbs)
-    items = members[fresh]
-    z = latents_new.index_select(0, items - n_frozen)
-    beams = ops.rq_beam(z, flat, ks, width)
-    dev = idx.device
-    err_held = torch.empty(M, dtype=torch.float32, device=dev)
-    cand = torch.empty((M, width, L), dtype=torch.int64, device=dev)
-    cand_err = torch.empty((M, width), dtype=torch.float32, device=dev)
-    err_held[fresh] = ops.rq_audit(z, flat, ks, idx.index_select(0, items))["err"]
-    cand[fresh] = beams["tuples"]
-    cand_err[fresh] = beams["err"]
-    choice, counters = ops.extend_finish_beam(idx, n_frozen, ks, members, found["offsets"], err_held, cand, cand_err)
-    out.update(counters)
-    took = choice[fresh]                                            # (a frozen member's choice is -1)
-    pos = torch.nonzero(took >= 0).flatten()
-    if pos.numel():
-        out["err_moved_sum"] = float(beams["err"][pos, took[pos].long()].double().sum())
-        _refresh_moved_residuals(cbs, idx, items[pos], z.index_select(0, pos), items[pos] - n_frozen, resid_new, resid_prev)
-    return out
+    return _beam_step(model, idx, int(n_frozen), latents_new, resid_new, ks, width, resid_prev)
 
 
 # ---- opt-in: what the two passes above leave colliding moves to a sibling bucket (--spill) ---------------------------------------
@@ -475,6 +467,132 @@ def _colliding(rows):
     return int(rows.shape[0] - np.unique(rows, axis=0).shape[0]) if rows.shape[0] else 0
 
 
+def open_run(ckpt_path, data_path=None, device="cuda:0", trust=False, spill=False, sharded=False):
+    """How every run over a checkpoint and its data file opens -> (checkpoint dict, EmbDataset, model): the checkpoint is read
+    (load_checkpoint, `trust` as its unrestricted unpickler); with `spill` a one-level model is refused as soon as the checkpoint's
+    arguments are read, before the data file is opened; the data file is `data_path` or the one the checkpoint names,
+    memory-mapped when its rows go to a GPU range by range (a cuda `device`, or `sharded` ranks); the model is built from the
+    checkpoint's arguments with the state dict loaded, still on the host and in training mode."""
+    ckpt = load_checkpoint(ckpt_path, trust=trust)
+    args = ckpt["args"]
+    if spill:
+        _refuse_one_level(args)
+    data = EmbDataset(data_path or args.data_path, mmap=sharded or str(device).startswith("cuda"))
+    model = build_model_from_args(args, data.dim)
+    model.load_state_dict(ckpt["state_dict"])
+    return ckpt, data, model
+
+
+def _refusals(beam=1, finish="none", extend=None, extend_finish="nearest_free", spill=False, audit=False, recheck=False,
+              sharded=False, rounds=MAX_ROUNDS, finish_width=8):
+    """What generate() refuses before it opens any file: (condition, message) pairs in the order in which they win when several
+    apply (tests/golden/f13_generate_refusals.json records which does, for every combination).  `finish` is looked at last and
+    only without `extend`, which ignores it."""
+    beamed = beam in ops.BEAM_WIDTHS and beam > 1
+    extended = extend is not None
+    return [
+        (beam not in ops.BEAM_WIDTHS, f"--beam {beam!r}: one of {ops.BEAM_WIDTHS}"),
+        (beamed and extended, "--beam with --extend is not supported: the new items are indexed around frozen tuples by the distance "
+                              "rule alone"),
+        (beamed and recheck, "--beam with --recheck_neartie is not supported: the re-evaluation reproduces the reference's greedy walk"),
+        (beamed and sharded, "--beam under torchrun is not supported: run it in a single process"),
+        (not (isinstance(rounds, int) and rounds >= 0), f"--rounds {rounds!r}: an integer >= 0"),
+        (finish_width not in FINISH_WIDTHS, f"--finish_width {finish_width!r}: one of {FINISH_WIDTHS}"),
+        (extend_finish not in EXTEND_FINISH_MODES, f"extend_finish={extend_finish!r}: one of {EXTEND_FINISH_MODES}"),
+        (extend_finish != "nearest_free" and not extended,
+         f"--extend_finish {extend_finish} finishes the new items of --extend: give --extend BASE.index.json"),
+        (finish == "beam" and extended, "--finish beam with --extend is not supported: the conflict rounds and --finish do not run around "
+                                        "frozen tuples; --extend_finish beam is that step for the new items"),
+        (finish == "beam" and recheck, "--finish beam with --recheck_neartie is not supported: the beam starts from the latents of pass 1, "
+                                       "which the re-evaluation does not patch"),
+        (finish == "beam" and sharded, "--finish beam under torchrun is not supported: run it in a single process"),
+        (spill and not extended and finish not in ("nearest_free", "beam"),
+         "--spill runs over what --finish nearest_free or --extend leave unresolved: give one of them"),
+        (spill and recheck, "--spill with --recheck_neartie is not supported: the residuals of level L-2 that the re-evaluation "
+                            "patches are not kept"),
+        (spill and sharded, "--spill under torchrun is not supported: run it in a single process"),
+        (audit and recheck, "--audit with --recheck_neartie is not supported: the audit starts from the latents of pass 1, which the "
+                            "re-evaluation does not patch"),
+        (audit and sharded, "--audit under torchrun is not supported: run it in a single process"),
+        (extended and recheck, "--extend with --recheck_neartie is not supported: the re-evaluation works on the reference's 64-row "
+                               "batches of a whole file"),
+        (extended and sharded, "--extend under torchrun is not supported: run it in a single process"),
+        (not extended and finish not in FINISH_MODES, f"finish={finish!r}: one of {FINISH_MODES}"),
+    ]
+
+
+def _refuse(**flags):
+    for refused, message in _refusals(**flags):
+        if refused:
+            raise ValueError(message)
+
+
+# the finishing pipeline's log lines, by the prefix of its statistics: `finish` for a whole file, `extend` around a frozen catalogue
+_WORDING = {
+    "finish": {"beam": "--finish beam: of %d items that share a tuple with a better holder %d moved to a free whole tuple out of a beam of "
+                       "%d (%d rounds, their quantisation error sums to %.6g), %d are left to the nearest free last-level code",
+               "nearest_free": "--finish nearest_free: %d items moved to the nearest free last-level code, %d unresolved "
+                               "(%d buckets listed, largest %d items)",
+               "left": "--finish nearest_free: %d items still collide: the largest bucket (items sharing all codes but the "
+                       "last) holds %d items, the last level has %d codes"},
+    "extend": {"beam": "--extend_finish beam: of %d new items whose tuple is taken %d moved to a free whole tuple out of a beam of %d "
+                       "(%d rounds, their quantisation error sums to %.6g), %d are left to the nearest free last-level code",
+               "nearest_free": "--extend: %d base items kept, %d new items, %d of them moved to the nearest free last-level code, "
+                               "%d unresolved (%d buckets listed, largest %d items)",
+               "left": "--extend: %d new items still collide: the largest bucket (items sharing all codes but the last) holds %d "
+                       "items, the last level has %d codes"},
+}
+
+
+def _finish_passes(model, idx, ks, resid_last, resid_prev, latents, first_pass, stats, prefix, n_frozen=None, beam_width=None,
+                   nearest_free=True, audit=None, lead=True):
+    """The finishing pipeline behind pass 1 (and the conflict rounds), the same for a whole file and for --extend: the beam step
+    (beam_width: 2, 4 or 8; None: not asked for), the nearest-free pass (unless nearest_free is False: --finish none), --spill
+    (resid_prev, the residual entering level L-2, is given), the truncation warning against `first_pass`, --audit, and the
+    collision statistics of what is left.  Mutates idx and the residuals; fills stats -- `prefix`_beam_*, `prefix`_moved,
+    `prefix`_unresolved, spill_*, audit, max_conflicts, collision_rate -- and logs under _WORDING[prefix].
+    n_frozen: None for a whole file (the whole-file kernels); N0 around a frozen catalogue, where resid_last, resid_prev and
+    latents hold the rows of the new items only and the audit covers those.  audit: None, or dict(greedy, neartie, what,
+    foreign_check) for _audit_and_log.  lead: False on the ranks of a torchrun that leave the nearest-free pass's log lines to
+    rank 0.  Returns the nearest-free pass's dict, or None."""
+    says, n, first = _WORDING[prefix], idx.shape[0], n_frozen or 0
+    done = None
+    if beam_width is not None:
+        done = _beam_step(model, idx, n_frozen, latents, resid_last, ks, beam_width, resid_prev)
+        stats.update({f"{prefix}_beam_width": beam_width, f"{prefix}_beam_movers": done["movers"], f"{prefix}_beam_moved": done["moved"],
+                      f"{prefix}_beam_unresolved": done["unresolved"], f"{prefix}_beam_rounds": done["rounds"]})
+        log.info(says["beam"], done["movers"], done["moved"], beam_width, done["rounds"], done["err_moved_sum"], done["unresolved"])
+        done = None
+    if nearest_free:
+        done = _nearest_free_pass(model, idx, n_frozen, resid_last, ks)      # every rank, on its identical copy: no collective
+        stats.update({f"{prefix}_moved": done["moved"], f"{prefix}_unresolved": done["unresolved"]})
+        if lead:
+            counts = () if n_frozen is None else (n_frozen, n - n_frozen)
+            log.info(says["nearest_free"], *counts, done["moved"], done["unresolved"], done["buckets"], done["largest_bucket"])
+            if done["unresolved"]:
+                log.warning(says["left"], done["unresolved"], done["largest_bucket"], ks[-1])
+    if resid_prev is not None:
+        _spill_and_log(model, idx, first, resid_prev, resid_last, ks, stats)
+    _warn_if_reference_would_truncate(first_pass, idx)
+    if audit is not None:
+        _audit_and_log(model, latents, audit["greedy"], audit["neartie"], idx[first:], stats, audit["what"], first_item=first,
+                       foreign_check=audit["foreign_check"])
+    final = ops.collision_groups(idx, ks, want_groups=False)
+    stats.update(max_conflicts=final["max_count"], collision_rate=(n - final["unique"]) / n if n else 0.0)
+    return done
+
+
+def _print_and_write(final, stats, output_file, verbose, lead=True):
+    """The reference's three closing lines (:131-136) and the file (rank 0's, under torchrun)."""
+    if verbose:
+        print("All indices number: ", stats["items"])
+        print("Max number of conflicts: ", stats["max_conflicts"])
+        print("Collision Rate", stats["collision_rate"])
+    if lead:
+        os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
+        dump_index_json(final, output_file)
+
+
 def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_path=None, verbose=True, trust_checkpoint=False,
                       spill=False, audit=False, extend_finish="nearest_free", finish_width=8):
     """--extend: the data file holds the whole catalogue, its first N0 rows are the items of `base_file` (keys "0" .. "N0-1") and
@@ -493,18 +611,9 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
         nearest-free pass.  N == N0: the five are 0 (and the width).
     spill: the new items that extend_collisions leaves unresolved go through spill_collisions.
     audit: stats["audit"] is the index audit of the NEW rows' tuples (no latents exist for the frozen items); N == N0: no report."""
-    if extend_finish not in EXTEND_FINISH_MODES:
-        raise ValueError(f"extend_finish={extend_finish!r}: one of {EXTEND_FINISH_MODES}")
-    if finish_width not in FINISH_WIDTHS:
-        raise ValueError(f"--finish_width {finish_width!r}: one of {FINISH_WIDTHS}")
+    _refuse(extend=base_file, extend_finish=extend_finish, spill=spill, audit=audit, finish_width=finish_width)
     beam_step = extend_finish == "beam"
-    ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
-    args = ckpt["args"]
-    if spill:
-        _refuse_one_level(args)
-    data = EmbDataset(data_path or args.data_path, mmap=str(device).startswith("cuda"))
-    model = build_model_from_args(args, data.dim)
-    model.load_state_dict(ckpt["state_dict"])
+    _, data, model = open_run(ckpt_path, data_path, device, trust=trust_checkpoint, spill=spill)
     ks = [int(q.embedding.weight.shape[0]) for q in model.rq.vq_layers]
     base = load_index_json(base_file, ks)
     n0, n = base.shape[0], len(data)
@@ -533,38 +642,12 @@ def generate_extended(ckpt_path, output_file, base_file, device="cuda:0", data_p
         base_dev = torch.from_numpy(base).to(dev)
         stats["base_colliding"] = n0 - ops.collision_groups(base_dev, ks, want_groups=False)["unique"] if n0 else 0
         idx = torch.cat([base_dev, idx_new])
-        first_pass = idx.clone()
-        if beam_step:
-            done = extend_beam_collisions(model, idx, n0, latents, resid_new, ks, finish_width, resid_prev=prev[0] if spill else None)
-            stats.update(extend_beam_movers=done["movers"], extend_beam_moved=done["moved"], extend_beam_unresolved=done["unresolved"],
-                         extend_beam_rounds=done["rounds"])
-            log.info("--extend_finish beam: of %d new items whose tuple is taken %d moved to a free whole tuple out of a beam of %d "
-                     "(%d rounds, their quantisation error sums to %.6g), %d are left to the nearest free last-level code",
-                     done["movers"], done["moved"], finish_width, done["rounds"], done["err_moved_sum"], done["unresolved"])
-        done = extend_collisions(model, idx, n0, resid_new, ks)
-        stats.update(extend_moved=done["moved"], extend_unresolved=done["unresolved"], buckets=done["buckets"],
-                     largest_bucket=done["largest_bucket"])
-        log.info("--extend: %d base items kept, %d new items, %d of them moved to the nearest free last-level code, %d unresolved "
-                 "(%d buckets listed, largest %d items)", n0, n - n0, done["moved"], done["unresolved"], done["buckets"],
-                 done["largest_bucket"])
-        if done["unresolved"]:
-            log.warning("--extend: %d new items still collide: the largest bucket (items sharing all codes but the last) holds %d "
-                        "items, the last level has %d codes", done["unresolved"], done["largest_bucket"], ks[-1])
-        if spill:
-            _spill_and_log(model, idx, n0, prev[0], resid_new, ks, stats)
-        _warn_if_reference_would_truncate(first_pass, idx)
-        if audit:
-            _audit_and_log(model, latents, idx_new, ties["neartie"], idx[n0:], stats, " (new items)", first_item=n0)
-        after = ops.collision_groups(idx, ks, want_groups=False)
-        stats["collision_rate"] = (n - after["unique"]) / n
-        stats["max_conflicts"] = after["max_count"]
+        report = dict(greedy=idx_new, neartie=ties["neartie"], what=" (new items)", foreign_check=True) if audit else None
+        done = _finish_passes(model, idx, ks, resid_new, prev[0] if spill else None, latents, idx.clone(), stats, "extend", n_frozen=n0,
+                              beam_width=finish_width if beam_step else None, audit=report)
+        stats.update(buckets=done["buckets"], largest_bucket=done["largest_bucket"])
         final = idx
-    if verbose:
-        print("All indices number: ", n)
-        print("Max number of conflicts: ", stats["max_conflicts"])
-        print("Collision Rate", stats["collision_rate"])
-    os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
-    dump_index_json(final, output_file)
+    _print_and_write(final, stats, output_file, verbose)
     return stats
 
 
@@ -746,67 +829,16 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
     groups are sharded too (resolve_collisions); rank 0 writes the file."""
     from . import dist as ldist
     ctx = ctx or ldist.current()
-    if beam not in ops.BEAM_WIDTHS:
-        raise ValueError(f"--beam {beam!r}: one of {ops.BEAM_WIDTHS}")
-    if beam > 1:
-        if extend is not None:
-            raise ValueError("--beam with --extend is not supported: the new items are indexed around frozen tuples by the distance "
-                             "rule alone")
-        if recheck:
-            raise ValueError("--beam with --recheck_neartie is not supported: the re-evaluation reproduces the reference's greedy walk")
-        if ctx.enabled:
-            raise ValueError("--beam under torchrun is not supported: run it in a single process")
-    if not (isinstance(rounds, int) and rounds >= 0):
-        raise ValueError(f"--rounds {rounds!r}: an integer >= 0")
-    if finish_width not in FINISH_WIDTHS:
-        raise ValueError(f"--finish_width {finish_width!r}: one of {FINISH_WIDTHS}")
-    if extend_finish not in EXTEND_FINISH_MODES:
-        raise ValueError(f"extend_finish={extend_finish!r}: one of {EXTEND_FINISH_MODES}")
-    if extend_finish != "nearest_free" and extend is None:
-        raise ValueError(f"--extend_finish {extend_finish} finishes the new items of --extend: give --extend BASE.index.json")
-    if finish == "beam":
-        if extend is not None:
-            raise ValueError("--finish beam with --extend is not supported: the conflict rounds and --finish do not run around frozen "
-                             "tuples; --extend_finish beam is that step for the new items")
-        if recheck:
-            raise ValueError("--finish beam with --recheck_neartie is not supported: the beam starts from the latents of pass 1, which "
-                             "the re-evaluation does not patch")
-        if ctx.enabled:
-            raise ValueError("--finish beam under torchrun is not supported: run it in a single process")
-    if spill:
-        if extend is None and finish not in ("nearest_free", "beam"):
-            raise ValueError("--spill runs over what --finish nearest_free or --extend leave unresolved: give one of them")
-        if recheck:
-            raise ValueError("--spill with --recheck_neartie is not supported: the residuals of level L-2 that the re-evaluation "
-                             "patches are not kept")
-        if ctx.enabled:
-            raise ValueError("--spill under torchrun is not supported: run it in a single process")
-    if audit:
-        if recheck:
-            raise ValueError("--audit with --recheck_neartie is not supported: the audit starts from the latents of pass 1, which the "
-                             "re-evaluation does not patch")
-        if ctx.enabled:
-            raise ValueError("--audit under torchrun is not supported: run it in a single process")
+    _refuse(beam=beam, finish=finish, extend=extend, extend_finish=extend_finish, spill=spill, audit=audit, recheck=recheck,
+            sharded=ctx.enabled, rounds=rounds, finish_width=finish_width)
     if extend is not None:
-        if recheck:
-            raise ValueError("--extend with --recheck_neartie is not supported: the re-evaluation works on the reference's 64-row "
-                             "batches of a whole file")
-        if ctx.enabled:
-            raise ValueError("--extend under torchrun is not supported: run it in a single process")
         return generate_extended(ckpt_path, output_file, extend, device=device, data_path=data_path, verbose=verbose,
                                  trust_checkpoint=trust_checkpoint, spill=spill, audit=audit, extend_finish=extend_finish,
                                  finish_width=finish_width)
     lead = ctx.rank == 0
     verbose = verbose and lead
-    if finish not in FINISH_MODES:
-        raise ValueError(f"finish={finish!r}: one of {FINISH_MODES}")
-    ckpt = load_checkpoint(ckpt_path, trust=trust_checkpoint)
+    ckpt, data, model = open_run(ckpt_path, data_path, device, trust=trust_checkpoint, spill=spill, sharded=ctx.enabled)
     args = ckpt["args"]
-    if spill:
-        _refuse_one_level(args)
-    data = EmbDataset(data_path or args.data_path, mmap=ctx.enabled or str(device).startswith("cuda"))
-    model = build_model_from_args(args, data.dim)
-    model.load_state_dict(ckpt["state_dict"])
     model = model.to(torch.device(device)).eval()
     if verbose:
         print(model)
@@ -853,52 +885,21 @@ def generate(ckpt_path, output_file, device="cuda:0", data_path=None, verbose=Tr
             print(n_groups)
 
     idx, history = resolve_collisions(model, idx, resid_last, ks, max_rounds=rounds, on_round=show, ctx=ctx)
-    finished = {"moved": 0, "unresolved": 0}
-    beam_finished = {}
-    if finish == "beam":
-        done = beam_finish_collisions(model, idx, latents, resid_last, ks, finish_width, resid_prev=prev[0] if spill else None)
-        beam_finished = {"finish_beam_width": finish_width, "finish_beam_movers": done["movers"], "finish_beam_moved": done["moved"],
-                         "finish_beam_unresolved": done["unresolved"], "finish_beam_rounds": done["rounds"]}
-        log.info("--finish beam: of %d items that share a tuple with a better holder %d moved to a free whole tuple out of a beam of "
-                 "%d (%d rounds, their quantisation error sums to %.6g), %d are left to the nearest free last-level code",
-                 done["movers"], done["moved"], finish_width, done["rounds"], done["err_moved_sum"], done["unresolved"])
-    if finish in ("nearest_free", "beam"):
-        finished = finish_collisions(model, idx, resid_last, ks)          # every rank, on its identical copy: no collective
-        if lead:
-            log.info("--finish nearest_free: %d items moved to the nearest free last-level code, %d unresolved "
-                     "(%d buckets listed, largest %d items)", finished["moved"], finished["unresolved"], finished["buckets"],
-                     finished["largest_bucket"])
-            if finished["unresolved"]:
-                log.warning("--finish nearest_free: %d items still collide: the largest bucket (items sharing all codes but the "
-                            "last) holds %d items, the last level has %d codes", finished["unresolved"],
-                            finished["largest_bucket"], ks[-1])
-    spilled = {}
-    if spill:
-        _spill_and_log(model, idx, 0, prev[0], resid_last, ks, spilled)
-    _warn_if_reference_would_truncate(first_pass, idx)
-    final = ops.collision_groups(idx, ks, want_groups=False)
     n = idx.shape[0]
-    stats = {"items": n, "max_conflicts": final["max_count"], "collision_rate": (n - final["unique"]) / n if n else 0.0,
-             "rounds": len(history), "groups_per_round": history, "neartie_items": neartie_items,
+    stats = {"items": n, "rounds": len(history), "groups_per_round": history, "neartie_items": neartie_items,
              "neartie_tau": ops.NEARTIE_TAU, "rechecked_items": rechecked[0], "recheck_changed": rechecked[1],
-             "finish": finish, "finish_moved": finished["moved"], "finish_unresolved": finished["unresolved"]}
-    stats.update(beam_finished)
-    if spill:
-        stats.update(spilled)
+             "finish": finish, "finish_moved": 0, "finish_unresolved": 0}
     stats.update(beam_stats)
-    if audit:
-        greedy = torch.cat(beamed["greedy"]) if beam > 1 else first_pass
-        _audit_and_log(model, latents, greedy, ties["neartie"], idx, stats, foreign_check=beam == 1 and finish != "beam")
+    report = None
+    if audit:                                              # (--beam: the report's greedy side stays pass 1's greedy tuples)
+        report = dict(greedy=torch.cat(beamed["greedy"]) if beam > 1 else first_pass, neartie=ties["neartie"], what="",
+                      foreign_check=beam == 1 and finish != "beam")
+    _finish_passes(model, idx, ks, resid_last, prev[0] if spill else None, latents, first_pass, stats, "finish",
+                   beam_width=finish_width if finish == "beam" else None, nearest_free=finish != "none", audit=report, lead=lead)
     if lead:
         log.info("near-tie items in pass 1: %d of %d (top-2 code gap <= %.3g x distance magnitude at some level); only "
                  "these could receive a different tuple from a CPU run of the reference", neartie_items, n, ops.NEARTIE_TAU)
-    if verbose:
-        print("All indices number: ", n)
-        print("Max number of conflicts: ", stats["max_conflicts"])
-        print("Collision Rate", stats["collision_rate"])
-    if lead:
-        os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
-        dump_index_json(idx, output_file)
+    _print_and_write(idx, stats, output_file, verbose, lead)
     ctx.barrier()
     return stats
 

@@ -989,21 +989,27 @@ def _group_table(members, offsets, what=""):
     return members.contiguous(), offsets.contiguous()
 
 
-def _counters_out(counters_out, device):
-    """The (moved, unresolved) pair of a nearest-free pass as the caller's own int64 [2] tensor on `device`, or (None) a fresh one."""
+def _counters_out(counters_out, device, count=2):
+    """The counters of a pass -- the (moved, unresolved) pair of a nearest-free pass, or the `count` = 4 of a beam finishing pass --
+    as the caller's own int64 [count] tensor on `device`, or (None) a fresh one."""
     if counters_out is None:
-        return torch.empty(2, dtype=torch.int64, device=device)
+        return torch.empty(count, dtype=torch.int64, device=device)
     if not (isinstance(counters_out, torch.Tensor) and counters_out.device == device and counters_out.dtype == torch.int64
-            and tuple(counters_out.shape) == (2,) and counters_out.is_contiguous()):
-        raise _lib.LcrecError(f"counters_out must be a contiguous int64 [2] tensor on idx's device ({device})")
+            and tuple(counters_out.shape) == (count,) and counters_out.is_contiguous()):
+        raise _lib.LcrecError(f"counters_out must be a contiguous int64 [{count}] tensor on idx's device ({device})")
     return counters_out
+
+
+def _is_workspace(workspace, device):
+    """whether `workspace` can go to the library as it is: a contiguous uint8 tensor on `device`"""
+    return (isinstance(workspace, torch.Tensor) and workspace.device == device and workspace.dtype == torch.uint8
+            and workspace.is_contiguous())
 
 
 def _own_workspace(workspace, device, need, query):
     """A workspace the caller owns, passed to the library as it is: a contiguous uint8 tensor on `device` of at least the `need`
     bytes that `query` (the entry's workspace function) states for this call."""
-    if not (isinstance(workspace, torch.Tensor) and workspace.device == device and workspace.dtype == torch.uint8
-            and workspace.is_contiguous()):
+    if not _is_workspace(workspace, device):
         raise _lib.LcrecError(f"workspace must be a contiguous uint8 tensor on the call's device ({device})")
     if workspace.numel() < need:
         raise _lib.LcrecError(f"workspace of {workspace.numel()} bytes, {int(need)} needed ({query})")
@@ -1021,25 +1027,7 @@ def finish_nearest_free(idx, resid_last, cb_last, ks, members, offsets, counters
     Returns (moved, unresolved); afterwards exactly `unresolved` items of the listed buckets still collide.
     counters_out: an int64 [2] tensor on idx's device that receives (moved, unresolved) instead; the binding then reads nothing
     back and returns None -- the form of the call that a graph capture can record (it allocates nothing and never waits)."""
-    lib = _lib.load()
-    n, L = _inplace_idx(idx)
-    resid_last, cb_last = _dev(resid_last, "resid_last"), _dev(cb_last, "cb_last")
-    members, offsets = _group_table(members, offsets)
-    if resid_last.dim() != 2 or cb_last.dim() != 2 or resid_last.shape[0] != n or resid_last.shape[1] != cb_last.shape[1]:
-        raise _lib.LcrecError(f"resid_last {tuple(resid_last.shape)} and cb_last {tuple(cb_last.shape)} do not go with idx {(n, L)}")
-    if len(ks) != L or int(ks[-1]) != cb_last.shape[0]:
-        raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}] and cb_last [{cb_last.shape[0]}, *]")
-    n_buckets = max(offsets.numel() - 1, 0)
-    dev = idx.device
-    counters = _counters_out(counters_out, dev)
-    with _on(dev):
-        rc = lib.lcrec_finish_nearest_free(_ptr(idx), n, L, _ints(ks), _ptr(resid_last), resid_last.shape[1], _ptr(cb_last),
-                                           _ptr(members), _ptr(offsets), n_buckets, _ptr(counters), _stream_ptr())
-    _lib.check(rc, "lcrec_finish_nearest_free")
-    if counters_out is not None:
-        return None
-    moved, unresolved = counters.tolist()
-    return moved, unresolved
+    return _nearest_free(None, idx, resid_last, cb_last, ks, members, offsets, counters_out)
 
 
 def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets, counters_out=None):
@@ -1051,23 +1039,33 @@ def extend_nearest_free(idx, n_frozen, resid_new, cb_last, ks, members, offsets,
     entering the last level of the NEW items only (row i - n_frozen for item i); cb_last float32 [K_last, e]; members / offsets
     are int64 device tensors in collision_groups' "device" layout over all n items.  Returns (moved, unresolved).
     counters_out: as finish_nearest_free -- an int64 [2] device tensor that receives the pair; nothing is read back, None is returned."""
+    return _nearest_free(n_frozen, idx, resid_new, cb_last, ks, members, offsets, counters_out)
+
+
+def _nearest_free(n_frozen, idx, resid, cb_last, ks, members, offsets, counters_out):
+    """finish_nearest_free (n_frozen None) and extend_nearest_free: one set of checks; the entry differs, and the name and the
+    number of the residual rows it takes"""
     lib = _lib.load()
     n, L = _inplace_idx(idx)
-    n_frozen = _frozen_count(n_frozen, n, L)
-    resid_new, cb_last = _dev(resid_new, "resid_new"), _dev(cb_last, "cb_last")
+    entry, name, rows, per_new = "lcrec_finish_nearest_free", "resid_last", n, ""
+    if n_frozen is not None:
+        n_frozen = _frozen_count(n_frozen, n, L)
+        entry, name, rows = "lcrec_extend_nearest_free", "resid_new", n - n_frozen
+        per_new = f" and n_frozen={n_frozen}: one row per new item"
+    resid, cb_last = _dev(resid, name), _dev(cb_last, "cb_last")
     members, offsets = _group_table(members, offsets)
-    if resid_new.dim() != 2 or cb_last.dim() != 2 or resid_new.shape[0] != n - n_frozen or resid_new.shape[1] != cb_last.shape[1]:
-        raise _lib.LcrecError(f"resid_new {tuple(resid_new.shape)} and cb_last {tuple(cb_last.shape)} do not go with idx {(n, L)} "
-                              f"and n_frozen={n_frozen}: one row per new item")
+    if resid.dim() != 2 or cb_last.dim() != 2 or resid.shape[0] != rows or resid.shape[1] != cb_last.shape[1]:
+        raise _lib.LcrecError(f"{name} {tuple(resid.shape)} and cb_last {tuple(cb_last.shape)} do not go with idx {(n, L)}{per_new}")
     if len(ks) != L or int(ks[-1]) != cb_last.shape[0]:
         raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}] and cb_last [{cb_last.shape[0]}, *]")
     n_buckets = max(offsets.numel() - 1, 0)
     dev = idx.device
     counters = _counters_out(counters_out, dev)
     with _on(dev):
-        rc = lib.lcrec_extend_nearest_free(_ptr(idx), n, n_frozen, L, _ints(ks), _ptr(resid_new), resid_new.shape[1], _ptr(cb_last),
-                                           _ptr(members), _ptr(offsets), n_buckets, _ptr(counters), _stream_ptr())
-    _lib.check(rc, "lcrec_extend_nearest_free")
+        head = (_ptr(idx), n) + (() if n_frozen is None else (n_frozen,))
+        rc = getattr(lib, entry)(*head, L, _ints(ks), _ptr(resid), resid.shape[1], _ptr(cb_last), _ptr(members), _ptr(offsets),
+                                 n_buckets, _ptr(counters), _stream_ptr())
+    _lib.check(rc, entry)
     if counters_out is not None:
         return None
     moved, unresolved = counters.tolist()
@@ -1178,13 +1176,7 @@ def _finish_beam(n_frozen, idx, ks, members, offsets, err_held, cand, cand_err, 
                               f"{tuple(cand.shape)}: one error per member and per candidate")
     if len(ks) != L:
         raise _lib.LcrecError(f"ks {list(ks)} does not go with idx [*, {L}]")
-    if counters_out is None:
-        counters = torch.empty(4, dtype=torch.int64, device=dev)
-    elif (isinstance(counters_out, torch.Tensor) and counters_out.device == dev and counters_out.dtype == torch.int64
-          and tuple(counters_out.shape) == (4,) and counters_out.is_contiguous()):
-        counters = counters_out
-    else:
-        raise _lib.LcrecError(f"counters_out must be a contiguous int64 [4] tensor on idx's device ({dev})")
+    counters = _counters_out(counters_out, dev, 4)
     if choice_out is None:
         choice_out = torch.full((M,), -1, dtype=torch.int32, device=dev)   # (no group: the library does not touch it)
     elif not (isinstance(choice_out, torch.Tensor) and choice_out.device == dev and choice_out.dtype == torch.int32
@@ -1342,8 +1334,7 @@ def rq_beam_into(z, codebooks_flat, ks, width, out, workspace=None):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()
                 and t.numel() >= n * per):
             raise _lib.LcrecError(f"out[{name!r}] must be a contiguous {dtype} tensor on z's device with at least {n * per} elements")
-    if workspace is not None and not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == dev
-                                      and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+    if workspace is not None and not _is_workspace(workspace, dev):                    # (one call over all rows: no size to ask for)
         raise _lib.LcrecError("workspace must be a contiguous uint8 tensor on z's device")
     if n == 0:                                             # (an empty tensor has no address to pass)
         return

@@ -112,6 +112,35 @@ def toy_items(seed, n=3000, d=128):
     return x
 
 
+def toy_checkpoint(directory, cut_last=None):
+    """The F6 toy model as a checkpoint on disk, the way the trainer writes one: `directory`/Toy.emb.npy holds toy_items of the
+    fixture's seed, `directory`/toy.pth the model arguments of tests/golden/f6_generate.npz (an argparse.Namespace whose data_path
+    is that file) and its state dict (the sd__ arrays).  cut_last: the last codebook keeps its first `cut_last` rows only, and
+    num_emb_list says so -- with 16 the buckets overflow, so that --spill has work.  Returns (items, path of toy.pth)."""
+    import argparse
+    import json
+    import os
+
+    import torch
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    g = np.load(os.path.join(gold, "f6_generate.npz"))
+    with open(os.path.join(gold, "manifest.json")) as fh:
+        meta = json.load(fh)["fixtures"]["f6_generate.npz"]
+    items = toy_items(meta["seed"])
+    npy = os.path.join(str(directory), "Toy.emb.npy")
+    np.save(npy, items)
+    kw = {k: v for k, v in meta["model"].items() if k != "in_dim"}
+    sd = {k[4:]: torch.from_numpy(g[k].copy()) for k in g.files if k.startswith("sd__")}
+    if cut_last is not None:
+        kw["num_emb_list"] = list(kw["num_emb_list"][:-1]) + [cut_last]
+        last = state_dict_names(len(kw["layers"]) + 1, kw["bn"], len(kw["num_emb_list"]))["codebooks"][-1]
+        sd[last] = sd[last][:cut_last].clone()
+    ckpt = os.path.join(str(directory), "toy.pth")
+    torch.save({"args": argparse.Namespace(data_path=npy, num_workers=0, **kw), "epoch": 0, "best_loss": 0.0,
+                "best_collision_rate": 0.0, "state_dict": sd, "optimizer": {}}, ckpt, pickle_protocol=4)
+    return items, ckpt
+
+
 # ---------------------------------------------------------------- F9: near-tie audit at bench scale
 NEARTIE_CASES = {"c3": (1_000_000, 768), "c2": (16_859, 4096)}   # BASELINE.json configs[2], configs[1]
 

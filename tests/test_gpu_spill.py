@@ -9,7 +9,6 @@ Buffers: idx carries 64 pre-filled guard rows past n, which must come back untou
 larger allocations with NaN-filled guard rows before them (n_frozen + 64) and after them.  A kernel that indexed the residuals by id
 instead of id - n_frozen, in either direction, would read allocated NaNs and produce a wrong tuple; it could not read outside an
 allocation."""
-import argparse
 import json
 import types
 
@@ -357,21 +356,8 @@ def test_spill_collisions_lists_both_tables_itself(hip, oracle):
 
 # ---- end to end: the F6 checkpoint with its last codebook cut to its first 16 rows ------------------------------------------------
 def _cut_checkpoint(tmp_path):
-    f = sc.f6_cut()
-    g, meta = f["fixture"], f["meta"]
-    items = gi.toy_items(meta["seed"])
-    npy = str(tmp_path / "Toy.emb.npy")
-    np.save(npy, items)
-    kw = {k: v for k, v in meta["model"].items() if k != "in_dim"}
-    kw["num_emb_list"] = [48, 48, sc.F6_CUT]
-    args = argparse.Namespace(data_path=npy, num_workers=0, **kw)
-    sd = {k[4:]: torch.from_numpy(g[k].copy()) for k in g.files if k.startswith("sd__")}
-    last = f["last_name"][4:]
-    sd[last] = sd[last][:sc.F6_CUT].clone()
-    ckpt = str(tmp_path / "toy.pth")
-    torch.save({"args": args, "epoch": 0, "best_loss": 0.0, "best_collision_rate": 0.0, "state_dict": sd, "optimizer": {}}, ckpt,
-               pickle_protocol=4)
-    return f, items, ckpt
+    items, ckpt = gi.toy_checkpoint(tmp_path, cut_last=sc.F6_CUT)
+    return sc.f6_cut(), items, ckpt
 
 
 def test_generate_with_spill_separates_every_item_of_the_cut_f6_model(hip, oracle, tmp_path):

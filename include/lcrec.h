@@ -950,6 +950,70 @@ int lcrec_decode_tuples(const int64_t *idx, int64_t idx_stride, int64_t n, const
                         float *xq_out, float *out, const float *x, int l1, float *err_out, uint32_t *flags_out,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* Index trie: the prefix trie over the tuples of an index matrix, for the two consumers of an index file -- the exact set of
+ * tokens a constrained generation may emit after a prefix, and the items that hold a tuple or its longest prefix.  Beyond the
+ * reference, which builds one set of allowed tokens per POSITION (data.py:67-89), so that every combination of codes that occur
+ * anywhere at their level is admitted, and which has no way back from a tuple to its items.  Opt-in: nothing else calls it.
+ *
+ * The three rules.
+ *   Build.  Tuples are compared by the key of lcrec_collision_plan: codes clamped as lcrec_collision_groups clamps them (v < 0
+ *      counts as 0, v >= K[l] as K[l] - 1), level 0 in the highest bits, at most 128 bits.  Items are sorted by key ascending, then
+ *      id ascending.  The nodes of depth d are the distinct clamped prefixes of length d, numbered in key order; depth 0 has the
+ *      one node 0.  A node's children are contiguous at the next depth, in ascending code order.
+ *   Find.  Longest-prefix descent from (depth 0, node 0): for l = 0 .. depth-1 take c = prefix[b][l]; a code outside [0, K[l])
+ *      stops the descent -- query codes are NOT clamped, an out-of-range code is simply absent --, otherwise c is searched among
+ *      the node's children, and the descent stops if it is absent.
+ *   Mask.  Row b at a live node (0 <= node[b] < counts[depth]) with depth < L may emit { token_ids[c] : c a child code of
+ *      node[b] }; with depth == L, or at a dead node, it may emit { eos } (nothing when eos < 0).  Every element of columns [0, V)
+ *      outside that set becomes -inf.  Allowed elements are neither read nor written.
+ *
+ * lcrec_index_trie is a HOST record of DEVICE pointers which the caller allocates; lcrec_index_trie_build fills n, L and K.
+ *   order    int64 [n]        item ids by key ascending, then id ascending
+ *   counts   int64 [L+1]      counts[d] = nodes of depth d; counts[0] = 1 always
+ *   child    int64 [L][n+1]   row d < L: child[d][j] = the index at depth d+1 of node j's first child; child[d][counts[d]] =
+ *                             counts[d+1], so node j's children are child[d][j] .. child[d][j+1] - 1
+ *   code     int32 [L][n]     row d-1: the last code of every depth-d node
+ *   first    int64 [n+1]      leaf j (a node of depth L) holds items order[first[j] .. first[j+1]); first[counts[L]] = n
+ * Only those prefixes of each row are written.  n == 0: counts = {1, 0, ...}, child[d][0] = 0 and first[0] = 0 (a row of child then
+ * has the one element, and the root has no child).  The int64 arrays are 8-byte aligned, code 4-byte.
+ *
+ * lcrec_index_trie_build: idx device int64, read only, item i's code of level l at idx[i*idx_stride + l]; idx_stride >= L, 0 = L;
+ * K host [L].  Keys are packed and sorted stably by rocPRIM's radix sort, one kernel finds every sorted item's common-prefix length
+ * with its predecessor, and per depth a scan of the flags "a node starts here" and one scatter fill the arrays.  The workspace
+ * (16-byte aligned, at least lcrec_index_trie_build_workspace(n, L) bytes, 0 for refused arguments) may hold anything.
+ *
+ * lcrec_index_trie_find: prefix device int64, row b's code of level l at prefix[b*prefix_stride + l]; prefix_stride >= depth,
+ * 0 = depth; may be NULL when depth == 0.  node_out device int64 [B], depth_out device int32 [B] or NULL: the node and the depth
+ * reached.  With depth_out == NULL, node_out[b] is -1 unless the full depth was reached.  depth == L gives the leaf.
+ *
+ * lcrec_index_trie_mask_logits: logits device fp32 [B][ld], ld >= V, 4-byte aligned, masked in place; node device int64 [B];
+ * token_ids device int32 [K[depth]] or NULL for the identity map (NULL is also what depth == L takes).  Token ids outside [0, V)
+ * and columns [V, ld) are never touched.  The kernel only stores: one workgroup per chunk of 4096 columns of a row marks the
+ * chunk's allowed tokens in an LDS bitmap and then stores 16 bytes of -inf wherever four columns on a 16-byte boundary are all
+ * disallowed, single floats elsewhere and at a row's unaligned head and tail (rows need not start on 16 bytes: odd ld).
+ *
+ * All four check their arguments before the device is touched: NULL pointers, n < 0, B < 0, L outside 1 .. LCREC_MAX_LEVELS,
+ * K[l] < 1, more than 128 key bits, depth outside [0, L], V < 1, ld < V, misalignment (LCREC_EINVAL) and a small workspace
+ * (LCREC_EWORKSPACE), each with a text that names the argument.  n == 0 (build) and B == 0 launch nothing.  No allocation, no host
+ * synchronisation, capturable.  Traced as "trie_build", "trie_find" and "trie_mask", one bracket per call. */
+typedef struct {
+    int64_t n;
+    int L;
+    int K[LCREC_MAX_LEVELS];
+    int64_t *order;
+    int64_t *counts;
+    int64_t *child;
+    int *code;
+    int64_t *first;
+} lcrec_index_trie;
+size_t lcrec_index_trie_build_workspace(int64_t n, int L);
+int lcrec_index_trie_build(const int64_t *idx, int64_t idx_stride, int64_t n, int L, const int *K, lcrec_index_trie *trie,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int lcrec_index_trie_find(const lcrec_index_trie *trie, const int64_t *prefix, int64_t prefix_stride, int64_t B, int depth,
+                          int64_t *node_out, int *depth_out, void *stream);
+int lcrec_index_trie_mask_logits(const lcrec_index_trie *trie, const int64_t *node, int64_t B, int depth, const int *token_ids,
+                                 int eos, float *logits, int64_t ld, int64_t V, void *stream);
+
 /* Text of the `.index.json` entries for a run of items (host-side; no device work).  Replaces the
  * per-item Python of index/generate_indices.py:83-92 (token strings "<a_{i}>", "<b_{j}>", ...) and the
  * json.dump of :138-145, whose default separators (", " and ": ") every consumer relies on

@@ -13,5 +13,6 @@ from .layers import MLPLayers, kmeans, sinkhorn_algorithm  # noqa: F401
 from .vq import VectorQuantizer  # noqa: F401
 from .rq import ResidualVectorQuantizer  # noqa: F401
 from .rqvae import RQVAE  # noqa: F401
+from .trie import IndexTrie  # noqa: F401
 
 __version__ = "0.1.0"

@@ -135,6 +135,7 @@ BnPlan = STRUCTS["lcrec_bn_plan"]
 StepTailPlan = STRUCTS["lcrec_step_tail_plan"]
 OptimPlan = STRUCTS["lcrec_optim_plan"]
 CollisionPlan = STRUCTS["lcrec_collision_plan"]
+IndexTrie = STRUCTS["lcrec_index_trie"]
 GemmLaunch = STRUCTS["lcrec_gemm_launch"]
 TraceEntry = STRUCTS["lcrec_trace_entry"]
 

@@ -30,7 +30,8 @@ const char *const kKernelNames[K_COUNT] = {"linear_fwd_128x128", "linear_fwd_128
                                            "recon_loss_grad", "grad_norm_clip", "adamw_step", "linear_fwd_32x64",
                                            "optim_step", "dropout", "cast_rows", "finish_nearest_free", "extend_nearest_free",
                                            "spill_nearest_free", "spill_keepers", "rq_audit", "rq_decode_gather",
-                                           "recon_row_error", "rq_beam", "finish_beam", "extend_finish_beam"};
+                                           "recon_row_error", "rq_beam", "finish_beam", "extend_finish_beam", "trie_build",
+                                           "trie_find", "trie_mask"};
 
 struct TraceRec { int kernel; hipEvent_t start, stop; };
 static std::mutex g_trace_mu;

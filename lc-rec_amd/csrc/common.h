@@ -34,7 +34,7 @@ enum KernelId { K_LINEAR_128x128 = 0, K_LINEAR_128x64, K_LINEAR_128x32, K_RQ_ASS
                 K_LINEAR_PP, K_LINEAR_64x64, K_SINKHORN_SLAB, K_SINKHORN_TINY, K_BN_FWD, K_BN_BWD, K_RELU_BIAS_BWD, K_LOSS,
                 K_GRAD_NORM, K_ADAMW, K_LINEAR_32x64, K_OPTIM_STEP, K_DROPOUT, K_CAST, K_FINISH, K_EXTEND, K_SPILL,
                 K_SPILL_KEEPERS, K_RQ_AUDIT, K_RQ_DECODE_GATHER, K_RECON_ROW_ERROR, K_RQ_BEAM, K_FINISH_BEAM,
-                K_EXTEND_FINISH_BEAM, K_COUNT };
+                K_EXTEND_FINISH_BEAM, K_TRIE_BUILD, K_TRIE_FIND, K_TRIE_MASK, K_COUNT };
 extern const char *const kKernelNames[K_COUNT];
 bool trace_on();
 void trace_begin(int kernel, hipStream_t stream);

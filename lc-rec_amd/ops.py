@@ -1468,6 +1468,127 @@ def decode_tuples(idx, codebooks_flat, ks, weights, biases, bn_scales=None, bn_s
     return res
 
 
+TRIE_ARRAYS = (("order", torch.int64), ("counts", torch.int64), ("child", torch.int64), ("code", torch.int32), ("first", torch.int64))
+
+
+def trie_array_sizes(n, L):
+    """Elements of the five arrays of lcrec_index_trie for n items of L levels (an array is never empty: it has an address)."""
+    n, L = int(n), int(L)
+    return {"order": max(n, 1), "counts": L + 1, "child": L * (n + 1), "code": max(L * n, 1), "first": n + 1}
+
+
+class Trie:
+    """lcrec_index_trie of include/lcrec.h with the device tensors its pointers name: `record` (the ctypes record the library
+    reads), `arrays` (name -> tensor), n, L, ks, device."""
+    __slots__ = ("record", "arrays", "n", "L", "ks", "device")
+
+
+def trie_build(idx, ks, arrays=None, workspace=None):
+    """lcrec_index_trie_build: the prefix trie of an int64 [n, L] device matrix (include/lcrec.h states the layout).
+
+    idx may be a view of a wider matrix -- rows idx.stride(0) apart, columns adjacent; it is never written.  arrays: the five
+    tensors to fill (trie_array_sizes; each contiguous on idx's device, of its dtype, at least that large), None: fresh ones.
+    workspace: a uint8 device tensor passed as it is, None: the binding's own.  Returns a Trie; nothing is read back."""
+    lib = _lib.load()
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 2):
+        raise _lib.LcrecError("idx must be an int64 [n, L] tensor on a HIP device (lcrec_amd has no CPU path)")
+    n, L = idx.shape
+    if L != len(ks):
+        raise _lib.LcrecError(f"idx has {L} columns but ks {len(ks)} levels")
+    if n > 1 and idx.stride(1) != 1 or (n > 1 and idx.stride(0) < L):
+        idx = idx.contiguous()
+    stride = idx.stride(0) if n > 1 else L
+    dev = idx.device
+    sizes = trie_array_sizes(n, L)
+    if arrays is None:
+        arrays = {name: torch.empty(sizes[name], dtype=dtype, device=dev) for name, dtype in TRIE_ARRAYS}
+    for name, dtype in TRIE_ARRAYS:
+        t = arrays.get(name)
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and t.is_contiguous() and t.numel() >= sizes[name]):
+            raise _lib.LcrecError(f"arrays[{name!r}] must be a contiguous {dtype} tensor on idx's device with at least {sizes[name]} elements")
+    trie = Trie()
+    trie.record = _lib.IndexTrie()
+    for name, _ in TRIE_ARRAYS:
+        setattr(trie.record, name, arrays[name].data_ptr())
+    trie.arrays, trie.n, trie.L, trie.ks, trie.device = arrays, n, L, [int(k) for k in ks], dev
+    karr = _ints(ks)
+    with _on(dev):
+        need = lib.lcrec_index_trie_build_workspace(n, L)
+        ws = _workspace(need, dev) if workspace is None else _own_workspace(workspace, dev, need, "lcrec_index_trie_build_workspace")
+        rc = lib.lcrec_index_trie_build(_ptr(idx) if n else _ptr(None), stride, n, L, karr, ctypes.addressof(trie.record),
+                                        _ptr(ws) if ws.numel() else _ptr(None), ws.numel(), _stream_ptr())
+    _lib.check(rc, "lcrec_index_trie_build")
+    return trie
+
+
+def _trie_rows(t, name, trie):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == trie.device and t.dtype == torch.int64):
+        raise _lib.LcrecError(f"{name} must be an int64 tensor on the trie's device ({trie.device})")
+    return t
+
+
+def trie_find(trie, prefix, depth, longest=False, node_out=None, depth_out=None, rows=None):
+    """lcrec_index_trie_find: longest-prefix descent of every row of `prefix` (int64 [B, >= depth] on the trie's device, rows
+    prefix.stride(0) apart; None with rows=B when depth == 0).  Returns node int64 [B] -- -1 where the full depth was not
+    reached -- or, with longest, (node, depth reached int32 [B]).  node_out / depth_out: contiguous buffers of at least B
+    elements to write into (they may be larger); they are returned as given."""
+    lib = _lib.load()
+    depth = int(depth)
+    if prefix is None:
+        B, stride = int(rows or 0), 0
+    else:
+        _trie_rows(prefix, "prefix", trie)
+        if prefix.dim() != 2 or prefix.shape[1] < depth:
+            raise _lib.LcrecError(f"prefix must be [B, >= {depth}], got {tuple(prefix.shape)}")
+        if prefix.shape[0] > 1 and prefix.shape[1] > 0 and (prefix.stride(1) != 1 or prefix.stride(0) < depth):
+            prefix = prefix.contiguous()
+        B = prefix.shape[0]
+        stride = prefix.stride(0) if B > 1 and prefix.shape[1] > 0 else max(depth, 0)
+    dev = trie.device
+    if node_out is None:
+        node_out = torch.empty(max(B, 1), dtype=torch.int64, device=dev)[:B]
+    if longest and depth_out is None:
+        depth_out = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B]
+    for name, t, dtype in (("node_out", node_out, torch.int64), ("depth_out", depth_out, torch.int32)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and t.is_contiguous()
+                                  and t.numel() >= B):
+            raise _lib.LcrecError(f"{name} must be a contiguous {dtype} tensor on the trie's device with at least {B} elements")
+    with _on(dev):
+        rc = lib.lcrec_index_trie_find(ctypes.addressof(trie.record), _ptr(prefix) if prefix is not None and B and depth else _ptr(None),
+                                       stride, B, depth, _ptr(node_out) if B else _ptr(None),
+                                       _ptr(depth_out) if longest and B else _ptr(None), _stream_ptr())
+    _lib.check(rc, "lcrec_index_trie_find")
+    return (node_out, depth_out) if longest else node_out
+
+
+def trie_mask_logits_(trie, logits, node, depth, token_ids=None, eos=-1):
+    """lcrec_index_trie_mask_logits, in place: logits float32 [B, V] on the trie's device, columns adjacent and rows
+    logits.stride(0) >= V apart (a view of a wider or offset buffer goes as it is); node int64 [B]; token_ids int32 [ks[depth]] or
+    None for the identity map.  Everything outside the allowed set of a row becomes -inf; nothing is returned."""
+    lib = _lib.load()
+    dev = trie.device
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.device == dev and logits.dtype == torch.float32
+            and logits.dim() == 2):
+        raise _lib.LcrecError(f"logits must be a float32 [B, V] tensor on the trie's device ({dev})")
+    B, V = logits.shape
+    if V > 1 and logits.stride(1) != 1 or (B > 1 and logits.stride(0) < V):
+        raise _lib.LcrecError("logits is masked in place: its columns must be adjacent and its rows must not overlap")
+    ld = logits.stride(0) if B > 1 else V
+    _trie_rows(node, "node", trie)
+    if node.dim() != 1 or node.shape[0] != B or not node.is_contiguous():
+        raise _lib.LcrecError(f"node must be a contiguous int64 [{B}] tensor")
+    depth = int(depth)
+    if token_ids is not None:
+        need = trie.ks[depth] if 0 <= depth < trie.L else 0
+        if not (isinstance(token_ids, torch.Tensor) and token_ids.device == dev and token_ids.dtype == torch.int32
+                and token_ids.is_contiguous() and token_ids.numel() >= need):
+            raise _lib.LcrecError(f"token_ids must be a contiguous int32 tensor on the trie's device with at least {need} elements")
+    with _on(dev):
+        rc = lib.lcrec_index_trie_mask_logits(ctypes.addressof(trie.record), _ptr(node) if B else _ptr(None), B, depth, _ptr(token_ids),
+                                              int(eos), _ptr(logits) if B else _ptr(None), ld, V, _stream_ptr())
+    _lib.check(rc, "lcrec_index_trie_mask_logits")
+
+
 def index_json_text(idx_rows, first_item=0):
     """bytes of the `.index.json` entries of items first_item.. for a HOST int64 [n, L] array
     (generate_indices.py:83-92,138-145; see lcrec_index_json_format in include/lcrec.h)."""
